@@ -17,15 +17,26 @@ N GPUs : one process per GPU (torch.distributed, backend nccl = RCCL); the
          (samples x slices are independent; sampling has no
          reduction, so there is no data-path collective); total work per step
          is fixed => "strong".
-extras : (rank 0, N=1) per-kernel HIP-event times of the same calls (roofline),
+--full : a plain run sets up, warms up, times the steps and prints the line;
+         --full adds what the headline does not need: per-kernel HIP-event
+         times of further identical steps (roofline) and, on rank 0 with N=1,
          the single-batch call pattern (`per_call`), the dim-10 kernel against
          its ALU roofline, the loss / value_and_grad steps of BASELINE configs
          3-5, and the CPU baseline (the oracle, timed on a bounded sample).
 --workload cfg3|cfg4|cfg5 : times `update()` (value_and_grad + Adam, with the
          ONE all-reduce of partial sums + gradient when sharded) instead of the
-         headline metric; own metric string.
+         headline metric; own metric string.  With --full, cfg5 on N > 1 ranks
+         also times the blocking all-reduce beside the overlapped one.
+--dump-outputs DIR : after the timed steps, what the last one computed goes to
+         DIR/<name>.npy (float32): `y` and `log_prob` of a fixed sample of the
+         step's samples (all of them up to DUMP_SAMPLES, else a seed-0 draw of
+         DUMP_SAMPLES sorted indices), or for --workload the `loss`, `params`
+         and Adam moments (`adam_mu`, `adam_nu`) after the last update().
+         Inputs are seeded, so two builds can be compared file by file.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs
   python bench.py --gpus N --steps K --warmup W          (starts its own N ranks as child processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
@@ -53,6 +64,7 @@ FLOP_PER_SAMPLE_D10 = 21888 + 2400
 # 12 FMAs per layer (10 softmax logits + the selected bin's 2 slope logits) instead of the 544-FMA MLP
 EXECUTED_FLOP_PER_SAMPLE = 2 * 24 + 400
 BYTES_PER_SAMPLE = 4 * (2 * DIM + 1)  # x in, y out, log_prob out (c is per slice)
+DUMP_SAMPLES = 1 << 21                # --dump-outputs: 24 MB of y and log_prob (a step has 655 M samples, 7.8 GB)
 PEAK_FP32_TFLOPS = 157.3              # MI355X_MICROARCH.md: fp32 vector == fp32 MFMA peak
 PEAK_HBM_GBS = 8000.0
 KERNEL_NAMES = {
@@ -73,9 +85,12 @@ def parse_args():
                   help="time-slices of 65 536 samples per step (the evaluator of utils.py:311-340 has 10 000)")
   ap.add_argument("--param-scale", type=float, default=0.2)
   ap.add_argument("--workload", choices=("sample", "cfg3", "cfg4", "cfg5"), default="sample")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the HIP-event "
+                  "roofline, the per_call / dim-10 / config 3-5 sections, the CPU baseline, cfg5's blocking all-reduce")
+  ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
   ap.add_argument("--cpu-seconds", type=float, default=8.0)
-  ap.add_argument("--no-extras", action="store_true", help="skip per_call / dim-10 / config 3-5 sections")
+  ap.add_argument("--no-extras", action="store_true", help="with --full: skip per_call / dim-10 / config 3-5 sections")
   ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); 'gloo' + "
                   "--share-device rehearses the multi-rank path on a one-GPU box")
   ap.add_argument("--share-device", action="store_true", help="all ranks use cuda:0 (rehearsal only)")
@@ -83,7 +98,18 @@ def parse_args():
                   "the RCCL init / all-reduce / barrier path on a one-GPU box)")
   ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline (0: the fastest of "
                   "{affinity, cgroup quota, 64, 32, 16}, found by a short calibration)")
-  return ap.parse_args()
+  args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
+  return args
+
+
+def write_outputs(out_dir, arrays):
+  """--dump-outputs: every array as out_dir/<name>.npy in float32."""
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in arrays.items():
+    a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def _cgroup_cpus():
@@ -281,6 +307,7 @@ def _config_steps(dev, which, world=1):
     k[0] += 1
     return upd(params, 1000 + k[0], 5000.0, state)[0]
 
+  step.opt_state = state           # Adam's moments, updated in place by every step
   return step, f, params, B, passes, desc
 
 
@@ -315,6 +342,85 @@ def configs_section(dev):
     except Exception as exc:
       out[which] = {"error": repr(exc)[:300]}
   return out
+
+
+def roofline_section(eng, step, n_prof):
+  """--full: per-kernel durations of the SAME calls as the timed ones: HIP events recorded by the library on the
+  launch stream around each kernel (cnf_model_set_profiling), over n_prof further steps -- outside the timed region,
+  so the headline number carries no event overhead."""
+  path = eng.last_path()
+  eng.set_profiling(True)
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  for _ in range(n_prof):
+    step()
+  flow_ms, build_ms, launches, prof_samples = eng.read_profile()
+  prof_wall_ms = (time.perf_counter() - t0) * 1e3 / max(n_prof, 1)      # wall time of a PROFILED step (events recorded between the kernels)
+  eng.set_profiling(False)
+  k_dur = flow_ms * 1e-3 / max(launches, 1)                   # average launch duration of the dominant kernel
+  k_samples = prof_samples / max(launches, 1)
+  b_dur = build_ms * 1e-3 / max(launches, 1)
+  achieved_gbs = BYTES_PER_SAMPLE * k_samples / k_dur / 1e9 if launches else float("nan")
+  exec_flop = EXECUTED_FLOP_PER_SAMPLE if path == "tables" else FLOP_PER_SAMPLE
+  executed_tflops = exec_flop * k_samples / k_dur / 1e12 if launches else float("nan")
+  achieved_tflops = FLOP_PER_SAMPLE * k_samples / k_dur / 1e12 if launches else float("nan")
+  roof = {
+    # HBM: SURVEY.md 8(d)'s algorithmic bytes (20 B per sample: x in, y out, log_prob out) -- the one bound a
+    # reformulation cannot move.  The ALU views are beside it.
+    "bound": "hbm", "achieved": achieved_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+    "frac": achieved_gbs / PEAK_HBM_GBS, "traffic": None,
+    "kernel": KERNEL_NAMES.get(path, path), "path": path,
+    "launch_ms": k_dur * 1e3, "launches_timed": launches,
+    "samples_per_launch": k_samples, "bytes_per_sample": BYTES_PER_SAMPLE,
+    "table_build_ms_per_launch": b_dur * 1e3,
+    # consistency: (launch_ms + table_build_ms_per_launch) x launches per step <= the wall time of a PROFILED step;
+    # a profiled step is a few per cent slower than a timed one (an event record between every two kernels)
+    "profiled_step_ms": prof_wall_ms, "launches_per_step": launches / max(n_prof, 1),
+    "timing": "HIP events recorded by the library on the launch stream around each kernel launch "
+              "(cnf_model_set_profiling, include/cnf_ot_amd_debug.h), same calls as the timed region, run right after it",
+    "alu_executed": {"flop_per_sample": exec_flop, "achieved": executed_tflops,
+                     "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": executed_tflops / PEAK_FP32_TFLOPS},
+    "alu_reference_formulation": {"flop_per_sample": FLOP_PER_SAMPLE, "achieved": achieved_tflops,
+                                  "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                                  "frac": achieved_tflops / PEAK_FP32_TFLOPS},
+    "note": "SURVEY.md 8(d) derived an fp32-ALU bound of 60 G samples/s from the reference formulation (2576 flop "
+            "per sample: 2-16-16-16 MLP conditioner + splines).  The table path reads the same conditioner from "
+            "exact piecewise-linear tables and executes ~448 flop per sample, so that figure is no longer a bound "
+            "(alu_reference_formulation.frac can exceed 1); the bound left is HBM.  What limits the kernel is "
+            "VALU issue (DESIGN.md 5.1d): ~545 vector instructions per 128-sample wave-tile, 96 of them "
+            "quarter-rate transcendentals -> an issue ceiling of ~102 G samples/s for this instruction stream; "
+            "0.22 of the HBM roofline is ~0.85 of that ceiling.",
+  }
+  pmc = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+  if os.path.exists(pmc) and launches:
+    with open(pmc) as f:
+      rec = json.load(f)
+    if rec.get("samples_per_launch"):
+      # PMC counters (separate rocprofv3 --pmc passes of this command) are per launch of the profiled run;
+      # rescaled by samples only when the profiled launch had another size (the kernel streams: bytes ~ samples)
+      roof["traffic"] = rec["bytes_per_launch"] * k_samples / rec["samples_per_launch"]
+      roof["traffic_source"] = rec.get("source", "profiles/hbm_traffic.json")
+      roof["traffic_samples_per_launch"] = rec["samples_per_launch"]
+  return roof
+
+
+def dump_sample_outputs(out_dir, y, lp, first, total, dist, rank):
+  """--dump-outputs of the sample path: y and log_prob of the step's samples at fixed indices (all `total` of them
+  up to DUMP_SAMPLES, else a seed-0 draw of DUMP_SAMPLES sorted ones), gathered from every rank's contiguous block
+  [first, first + lp.numel()) to rank 0, which writes them."""
+  if total <= DUMP_SAMPLES:
+    idx = np.arange(total)
+  else:
+    idx = np.sort(np.random.default_rng(0).choice(total, DUMP_SAMPLES, replace=False))
+  mine = torch.from_numpy(idx[(idx >= first) & (idx < first + lp.numel())] - first).to(lp.device)
+  part = (y[mine].cpu().numpy(), lp[mine].cpu().numpy())
+  parts = [part]
+  if dist is not None:
+    parts = [None] * dist.get_world_size()
+    dist.all_gather_object(parts, part)
+  if rank == 0:
+    write_outputs(out_dir, {"y": np.concatenate([p[0] for p in parts]),
+                            "log_prob": np.concatenate([p[1] for p in parts])})
 
 
 def _free_port():
@@ -435,28 +541,9 @@ def main():
   if dist is not None:
     dist.barrier()
   elapsed = max_over_ranks(elapsed)
-  path = eng.last_path()
   assert torch.isfinite(lp).all(), "non-finite log_prob in the bench output"
-
-  # per-kernel durations of the SAME calls: HIP events recorded by the library on the launch stream around
-  # each kernel (cnf_model_set_profiling), over min(steps, 8) further steps -- outside the timed region, so
-  # the headline number carries no event overhead
-  eng.set_profiling(True)
-  torch.cuda.synchronize()
-  n_prof = min(args.steps, 8)
-  t0 = time.perf_counter()
-  for _ in range(n_prof):
-    step()
-  flow_ms, build_ms, launches, prof_samples = eng.read_profile()
-  prof_wall_ms = (time.perf_counter() - t0) * 1e3 / max(n_prof, 1)      # wall time of a PROFILED step (events recorded between the kernels)
-  eng.set_profiling(False)
-  k_dur = flow_ms * 1e-3 / max(launches, 1)                   # average launch duration of the dominant kernel
-  k_samples = prof_samples / max(launches, 1)
-  b_dur = build_ms * 1e-3 / max(launches, 1)
-  achieved_gbs = BYTES_PER_SAMPLE * k_samples / k_dur / 1e9 if launches else float("nan")
-  exec_flop = EXECUTED_FLOP_PER_SAMPLE if path == "tables" else FLOP_PER_SAMPLE
-  executed_tflops = exec_flop * k_samples / k_dur / 1e12 if launches else float("nan")
-  achieved_tflops = FLOP_PER_SAMPLE * k_samples / k_dur / 1e12 if launches else float("nan")
+  if args.dump_outputs:
+    dump_sample_outputs(args.dump_outputs, y, lp, s_first * BATCH, args.slices * BATCH, dist, rank)
 
   total_samples = args.steps * args.slices * BATCH
   value = total_samples / elapsed
@@ -476,64 +563,30 @@ def main():
       "comm": args._comm,
     },
     "cold_first_call_ms": cold_ms,
-    "roofline": {
-      # HBM: SURVEY.md 8(d)'s algorithmic bytes (20 B per sample: x in, y out, log_prob out) -- the one bound a
-      # reformulation cannot move.  The ALU views are beside it.
-      "bound": "hbm", "achieved": achieved_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-      "frac": achieved_gbs / PEAK_HBM_GBS, "traffic": None,
-      "kernel": KERNEL_NAMES.get(path, path), "path": path,
-      "launch_ms": k_dur * 1e3, "launches_timed": launches,
-      "samples_per_launch": k_samples, "bytes_per_sample": BYTES_PER_SAMPLE,
-      "table_build_ms_per_launch": b_dur * 1e3,
-      # consistency: (launch_ms + table_build_ms_per_launch) x launches per step <= the wall time of a PROFILED step;
-      # a profiled step is a few per cent slower than a timed one (an event record between every two kernels)
-      "profiled_step_ms": prof_wall_ms, "launches_per_step": launches / max(n_prof, 1),
-      "timing": "HIP events recorded by the library on the launch stream around each kernel launch "
-                "(cnf_model_set_profiling, include/cnf_ot_amd_debug.h), same calls as the timed region, run right after it",
-      "alu_executed": {"flop_per_sample": exec_flop, "achieved": executed_tflops,
-                       "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s", "frac": executed_tflops / PEAK_FP32_TFLOPS},
-      "alu_reference_formulation": {"flop_per_sample": FLOP_PER_SAMPLE, "achieved": achieved_tflops,
-                                    "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                                    "frac": achieved_tflops / PEAK_FP32_TFLOPS},
-      "note": "SURVEY.md 8(d) derived an fp32-ALU bound of 60 G samples/s from the reference formulation (2576 flop "
-              "per sample: 2-16-16-16 MLP conditioner + splines).  The table path reads the same conditioner from "
-              "exact piecewise-linear tables and executes ~448 flop per sample, so that figure is no longer a bound "
-              "(alu_reference_formulation.frac can exceed 1); the bound left is HBM.  What limits the kernel is "
-              "VALU issue (DESIGN.md 5.1d): ~545 vector instructions per 128-sample wave-tile, 96 of them "
-              "quarter-rate transcendentals -> an issue ceiling of ~102 G samples/s for this instruction stream; "
-              "0.22 of the HBM roofline is ~0.85 of that ceiling.",
-    },
   }
-  pmc = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-  if os.path.exists(pmc) and launches:
-    with open(pmc) as f:
-      rec = json.load(f)
-    if rec.get("samples_per_launch"):
-      # PMC counters (separate rocprofv3 --pmc passes of this command) are per launch of the profiled run;
-      # rescaled by samples only when the profiled launch had another size (the kernel streams: bytes ~ samples)
-      line["roofline"]["traffic"] = rec["bytes_per_launch"] * k_samples / rec["samples_per_launch"]
-      line["roofline"]["traffic_source"] = rec.get("source", "profiles/hbm_traffic.json")
-      line["roofline"]["traffic_samples_per_launch"] = rec["samples_per_launch"]
+  if args.full:
+    line["roofline"] = roofline_section(eng, step, min(args.steps, 8))
 
-  def extra(name, fn):        # the extra sections are reported, never fatal for the metric
-    try:
-      line[name] = fn()
-    except Exception as exc:
-      line[name] = {"error": repr(exc)[:300]}
+    def extra(name, fn):        # the extra sections are reported, never fatal for the metric
+      try:
+        line[name] = fn()
+      except Exception as exc:
+        line[name] = {"error": repr(exc)[:300]}
 
-  if rank == 0 and world == 1 and not args.no_extras:
-    nb = min(S, 64)
-    extra("per_call", lambda: per_call_section(eng, model, params, noise[:BATCH], t_slices[:nb], y[:BATCH],
-                                               lp[:BATCH], dev))
-    del noise, y, lp
-    torch.cuda.empty_cache()
-    extra("dim10", lambda: dim10_section(dev))
-    extra("configs", lambda: configs_section(dev))
+    if rank == 0 and world == 1 and not args.no_extras:
+      nb = min(S, 64)
+      extra("per_call", lambda: per_call_section(eng, model, params, noise[:BATCH], t_slices[:nb], y[:BATCH],
+                                                 lp[:BATCH], dev))
+      del noise, y, lp
+      torch.cuda.empty_cache()
+      extra("dim10", lambda: dim10_section(dev))
+      extra("configs", lambda: configs_section(dev))
 
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
-    extra("cpu_baseline", lambda: cpu_baseline(params.flat.cpu().double().numpy(), args.cpu_seconds, args.cpu_threads))
-  elif rank == 0:
-    line["cpu_baseline"] = None
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+      extra("cpu_baseline", lambda: cpu_baseline(params.flat.cpu().double().numpy(), args.cpu_seconds,
+                                                 args.cpu_threads))
+    elif rank == 0:
+      line["cpu_baseline"] = None
 
   if rank == 0:
     print(json.dumps(line), flush=True)
@@ -562,7 +615,7 @@ def workload_main(args, dev, dist, world, rank, barrier, max_over_ranks):
     return max_over_ranks(el), loss
 
   modes = None
-  if args.workload == "cfg5" and world > 1:
+  if args.full and args.workload == "cfg5" and world > 1:
     # configs[4] "allreduce/compute overlap": the density-fit terms' all-reduce under the kinetic / obstacle slices
     # (shipped default) against ONE blocking collective at the end -- both timed, the same way
     app.OVERLAP_ALLREDUCE = False
@@ -574,6 +627,9 @@ def workload_main(args, dev, dist, world, rank, barrier, max_over_ranks):
   else:
     elapsed, loss = timed()
   assert torch.isfinite(torch.as_tensor(loss)).all(), "non-finite loss"
+  if args.dump_outputs and rank == 0:      # update() returns (loss, params, opt_state); params are replicated
+    write_outputs(args.dump_outputs, {"loss": torch.as_tensor(loss).reshape(1), "params": params.flat,
+                                      "adam_mu": step.opt_state.mu, "adam_nu": step.opt_state.nu})
   line = {
     "metric": "flow passes/sec through update() (value_and_grad + Adam) of " + args.workload,
     "value": passes * args.steps / elapsed, "unit": "flow passes/s", "n_gpus": world, "steps": args.steps,

@@ -1,5 +1,5 @@
 #!/bin/bash
-# rocprofv3 passes over bench.py: (1) kernel trace + stats of the DRIVER'S command, (2..) PMC counters, each in its
+# rocprofv3 passes over bench.py: (1) kernel trace + stats of `bench.py --full`, (2..) PMC counters, each in its
 # own run (no trace domains other than --kernel-trace next to --pmc).  Usage: scripts/gpu_profile.sh <tag>
 TAG=${1:-r03}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -7,8 +7,8 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/trace.log 2>&1
+BENCH="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit $rc; fi
 grep '^{' $OUT/trace.log > $OUT/bench_line.json
 # the same without the per_call / config / evaluator sections (which launch the metric kernel at other sizes and pull

@@ -152,3 +152,55 @@ def test_bench_starts_its_own_ranks_as_child_processes(monkeypatch):
   with pytest.raises(SystemExit) as exc:
     bench.main()
   assert exc.value.code == 2 and not seen
+
+
+def test_bench_dump_outputs_are_a_fixed_float32_sample(tmp_path):
+  """`bench.py --dump-outputs`: y / log_prob of the last step at fixed indices -- every sample up to DUMP_SAMPLES,
+  else the same seeded draw on every run -- in float32 and within 64 MB; a multi-rank step gathers the ranks'
+  contiguous blocks into the very files one rank writes."""
+  import sys
+  sys.path.insert(0, ROOT)
+  import bench
+
+  def step_outputs(n):       # values encode the sample index (exact in float32 below 2^24)
+    return torch.arange(2 * n, dtype=torch.float32).reshape(n, 2), torch.arange(n, dtype=torch.float32)
+
+  def load(d):
+    return np.load(d / "y.npy"), np.load(d / "log_prob.npy")
+
+  n = 3 * bench.BATCH
+  y, lp = step_outputs(n)
+  bench.dump_sample_outputs(str(tmp_path / "small"), y, lp, 0, n, None, 0)
+  ys, ls = load(tmp_path / "small")
+  assert ys.dtype == ls.dtype == np.float32 and np.array_equal(ys, y.numpy()) and np.array_equal(ls, lp.numpy())
+
+  n = 2 * bench.DUMP_SAMPLES + 12345
+  y, lp = step_outputs(n)
+  for run in ("a", "b"):
+    bench.dump_sample_outputs(str(tmp_path / run), y, lp, 0, n, None, 0)
+  (ya, la), (yb, lb) = load(tmp_path / "a"), load(tmp_path / "b")
+  assert np.array_equal(ya, yb) and np.array_equal(la, lb)
+  idx = la.astype(np.int64)
+  assert len(idx) == bench.DUMP_SAMPLES and np.all(np.diff(idx) > 0) and idx[-1] < n
+  assert np.array_equal(ya, np.stack([2 * idx, 2 * idx + 1], 1).astype(np.float32))
+  assert ya.nbytes + la.nbytes <= 64 << 20
+
+  gathered = {}
+
+  class TwoRanks:            # all_gather_object of two ranks, rank 1 called first
+    def __init__(self, rank):
+      self.rank = rank
+
+    def get_world_size(self):
+      return 2
+
+    def all_gather_object(self, out, part):
+      gathered[self.rank] = part
+      out[:] = [gathered.get(r) for r in range(2)]
+
+  half = n // 2
+  bench.dump_sample_outputs(str(tmp_path / "ranks"), y[half:], lp[half:], half, n, TwoRanks(1), 1)
+  assert not (tmp_path / "ranks").exists()
+  bench.dump_sample_outputs(str(tmp_path / "ranks"), y[:half], lp[:half], 0, n, TwoRanks(0), 0)
+  yr, lr = load(tmp_path / "ranks")
+  assert np.array_equal(yr, ya) and np.array_equal(lr, la)
