@@ -165,6 +165,12 @@ __device__ __forceinline__ bool maybe_outside(v2f v, float lo, float hi) {
   const v2f d = v - mid;
   return !(fmaxf(fabsf(d.x), fabsf(d.y)) < half);     // NaN counts as outside
 }
+// The same for the two sample pairs a layer reads (both splines' inputs).
+__device__ __forceinline__ bool maybe_outside(v2f v, v2f w, float lo, float hi) {
+  const float mid = 0.5f * (lo + hi), half = 0.5f * (hi - lo) * 0.99999f;
+  const v2f d = v - mid, e = w - mid;
+  return !(fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fmaxf(fabsf(e.x), fabsf(e.y))) < half);
+}
 
 // ---------------------------------------------------------------------------
 // Math policy.  FAST=false: ocml expf/logf/sqrtf and IEEE division.
@@ -256,7 +262,9 @@ __device__ __forceinline__ T knot_slope(T t, const SplineConstsT<typename Lanes<
 // (the prepared table); otherwise it is folded into the one logarithm.
 // ARG: `ld` receives the ARGUMENT of that logarithm (the spline's derivative f'), not +-log of it: a caller that
 // evaluates several splines multiplies the arguments and takes one logarithm.
-template <bool INV, bool FAST, class T, bool L2S_GIVEN = true, bool ARG = false>
+// NEWTON=false (the flow kernel's sampling direction): the root's quotient is one v_rcp_f32 product,
+// 1 ulp instead of 0.5 -- z in [0, 1] only enters x0 + bw z and the derivative's polynomial.
+template <bool INV, bool FAST, class T, bool L2S_GIVEN = true, bool ARG = false, bool NEWTON = true>
 __device__ __forceinline__ void rqs_bin_eval(T v, T x0, T y0, T bw, T bh, T ibw, T s, T st,
                                              T d0, T d1, T l2s, T& out, T& ld) {
   using M = Math<FAST>;
@@ -267,7 +275,8 @@ __device__ __forceinline__ void rqs_bin_eval(T v, T x0, T y0, T bw, T bh, T ibw,
     const T b = vfma(-st, dy, d0 * bh);
     const T a = vfma(s, bh, -b);
     const T disc = vfma(b, b, a * c * -4.0f);
-    z = clip01(M::div(c * -2.0f, b + M::sqrt(disc)));
+    if constexpr (NEWTON) z = clip01(M::div(c * -2.0f, b + M::sqrt(disc)));
+    else z = clip01(c * -2.0f * M::rcp(b + M::sqrt(disc)));
     out = vfma(bw, z, x0);
   } else {
     z = clip01((v - x0) * ibw);
@@ -352,9 +361,12 @@ template <> struct BinRow<v2f> {
   template <int K> __device__ __forceinline__ v2f get(int f) const { return v2f{px[tab_off(f, K)], py[tab_off(f, K)]}; }
 };
 
-template <int K, bool INV, bool FAST, class T, bool ARG = false>
+// LEAN (flow_pwl_kernel's sampling direction): the root without its Newton step (rqs_bin_eval NEWTON=false), and
+// the linear tails guarded by the caller's wave-uniform `tails` instead of this spline's own test.
+template <int K, bool INV, bool FAST, class T, bool ARG = false, bool LEAN = false>
 __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab, T v,
-                                             const SplineConstsT<typename Lanes<T>::real> sc, T& out, T& ld) {
+                                             const SplineConstsT<typename Lanes<T>::real> sc, T& out, T& ld,
+                                             bool tails = true) {
   typedef typename Lanes<T>::real R;
   typename Lanes<T>::index k;
   if constexpr (std::is_same<T, v2f>::value) k = bin_of_pairs<K>(tab + tab_off(INV ? F_YKB : F_XKB, K), v);
@@ -364,16 +376,16 @@ __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab,
   const T bw = INV ? row.template get<K>(F_BW) : splat<T>(0.0f);          // the inverse never divides by bw ...
   const T ibw = INV ? splat<T>(0.0f) : row.template get<K>(F_IBW);        // ... the forward map only does
   if constexpr (ARG)
-    rqs_bin_eval<INV, FAST, T, false, true>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
+    rqs_bin_eval<INV, FAST, T, false, true, !LEAN>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
                                             row.template get<K>(F_BH), ibw,
                                             row.template get<K>(F_S), row.template get<K>(F_ST), row.template get<K>(F_D0),
                                             row.template get<K>(F_D1), splat<T>(0.0f), out, ld);
   else
-    rqs_bin_eval<INV, FAST, T>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
+    rqs_bin_eval<INV, FAST, T, true, false, !LEAN>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
                                row.template get<K>(F_BH), ibw,
                                row.template get<K>(F_S), row.template get<K>(F_ST), row.template get<K>(F_D0),
                                row.template get<K>(F_D1), row.template get<K>(F_L2S), out, ld);
-  if (maybe_outside(v, sc.lo, sc.hi)) {   // linear tails (rare: |v| >= 10)
+  if (LEAN ? tails : maybe_outside(v, sc.lo, sc.hi)) {   // linear tails (rare: |v| >= 10)
     const auto below = vle(v, sc.lo);
     const auto above = vge(v, sc.hi);
     const R* tl = tab + tab_off(F_TAIL, K);
@@ -502,9 +514,11 @@ __device__ __forceinline__ void cond_spline_masked(const v2f (&th)[3 * K + 1], v
 // The slope logits are not evaluated for all K + 1 knots and then selected with masks: the bin index (the sum of
 // the 0/1 masks) addresses the row a second time and `slopes(ka, kb, ta, tb)` returns (t_k, t_k+1) of each sample
 // from one packed FMA.  Same values bit for bit as cond_spline_masked on the same rows.
-template <int K, bool INV, bool FAST, bool SHIFT_FREE, bool ARG = false, class SlopeFetch>
+// LEAN (flow_pwl_kernel's sampling direction): in shift-free cells the root without its Newton step (rqs_bin_eval
+// NEWTON=false); the linear tails guarded by the caller's wave-uniform `tails` instead of this spline's own test.
+template <int K, bool INV, bool FAST, bool SHIFT_FREE, bool ARG = false, bool LEAN = false, class SlopeFetch>
 __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (&qb)[K], SlopeFetch&& slopes, v2f v,
-                                                 const SplineConsts sc, v2f& out, v2f& ld) {
+                                                 const SplineConsts sc, v2f& out, v2f& ld, bool tails = true) {
   using M = Math<FAST>;
   typedef v2f T;
   auto la = [&](int j) { return qa[j >> 1][j & 1]; };
@@ -579,8 +593,8 @@ __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (
   const T ibw = M::rcp(bw);
   const T s = bh * ibw;
   const T st = d1 + d0 - s * 2.0f;
-  rqs_bin_eval<INV, FAST, T, false, ARG>(v, x0, y0, bw, bh, ibw, s, st, d0, d1, s, out, ld);
-  if (maybe_outside(v, sc.lo, sc.hi)) {
+  rqs_bin_eval<INV, FAST, T, false, ARG, !(LEAN && SHIFT_FREE)>(v, x0, y0, bw, bh, ibw, s, st, d0, d1, s, out, ld);
+  if (LEAN ? tails : maybe_outside(v, sc.lo, sc.hi)) {
     const auto below = vle(v, sc.lo);          // bin 0 was selected: d0 = slope[0]
     const auto above = vge(v, sc.hi);          // bin K-1 was selected: d1 = slope[K]
     const T lo_out = INV ? M::div(v - sc.lo, d0) + sc.lo : vfma(v - sc.lo, d0, splat<T>(sc.lo));

@@ -659,12 +659,17 @@ __global__ void cond_uniform_kernel(const float* __restrict__ c, int64_t B, uint
 // LFIX > 0: the number of flow layers is this compile-time constant -- the layer loop is unrolled, the layer's
 // parity (which coordinate is conditioned on which) and its table's LDS offset are literals instead of per-layer
 // selects and address arithmetic.
-template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, bool SHIFT_FREE_OK = false, int LROWS = PWL_LROWS, int LFIX = 0>
+// LEAN_OK (flow_pwl_kernel): the sampling direction takes the shorter instruction stream of DESIGN 5.1d -- the
+// quadratic's root without a Newton step (the `first` spline everywhere, the conditioned one in shift-free waves),
+// one logarithm per layer, one tail test per layer.  The loss kernel keeps its arithmetic.
+template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, bool SHIFT_FREE_OK = false, int LROWS = PWL_LROWS, int LFIX = 0,
+          bool LEAN_OK = false>
 __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, const float* __restrict__ gtbl,
                                             int L, const SplineConsts sc, v2f& u0, v2f& u1,
                                             const PreciseConsts* pc = nullptr, const double* e2tab = nullptr,
                                             const double* tabd = nullptr, BaseAcc<v2f>* bacc = nullptr) {
   constexpr bool INV = !TO_BASE;
+  constexpr bool LEAN = LEAN_OK && INV && FAST;
   static_assert(!PRECISE || TO_BASE, "precise path: data -> base");
   v2f acc = splat<v2f>(0.0f);
   [[maybe_unused]] v2f lo0 = splat<v2f>(0.0f), lo1 = lo0;      // precise path: what rounding u0 / u1 to fp32 dropped
@@ -702,12 +707,15 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       // their log|f'| (the derivative itself) and the product goes through one v_log_f32.  The conditioned
       // factor is bounded there (slope logits in [-3, 40], bins >= 1e-4 of a range of 20: ~1e-9 .. 1e6), so the
       // product leaves the fp32 range only for a `first` spline with derivatives beyond 1e-29 .. 1e32.
-      constexpr bool LOGPROD = false;     // (measured within noise: 1.477 vs 1.480 ms per launch -- off)
+      constexpr bool LOGPROD = LEAN;
+      // Both splines read the layer's inputs (uf, uo): one wave-level test guards both linear-tail fix-ups.
+      bool tails = true;
+      if constexpr (LEAN) tails = __builtin_amdgcn_ballot_w64(maybe_outside(uf, uo, sc.lo, sc.hi)) != 0;
       v2f larg = splat<v2f>(1.0f);
       if constexpr (LOGPROD) {
-        table_spline<K, INV, FAST, v2f, true>(tab, uf, sc, of, larg);
+        table_spline<K, INV, FAST, v2f, true, LEAN>(tab, uf, sc, of, larg, tails);
       } else {
-        table_spline<K, INV, FAST, v2f>(tab, uf, sc, of, ld);
+        table_spline<K, INV, FAST, v2f, false, LEAN>(tab, uf, sc, of, ld, tails);
         acc += ld;
       }
       if (TO_BASE) {
@@ -721,10 +729,10 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       };
       if (!SHIFT_FREE_OK || __builtin_amdgcn_ballot_w64(general) != 0)      // wave-uniform: a lane's cell is marked
       {       // marked cells (ill-conditioned pieces, far-out inputs): the general form, and its own logarithm
-        cond_spline_rows<K, INV, FAST, false, false>(qa, qb, slopes, uo, sc, oo, ld);
+        cond_spline_rows<K, INV, FAST, false, false, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
         if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg); ld += INV ? -lg : lg; }
       } else {
-        cond_spline_rows<K, INV, FAST, true, LOGPROD>(qa, qb, slopes, uo, sc, oo, ld);
+        cond_spline_rows<K, INV, FAST, true, LOGPROD, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
         if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg * ld); ld = INV ? -lg : lg; }
       }
     }
@@ -764,19 +772,25 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   // Tile geometry is wave-uniform (scalar registers): the slice, the tile's first sample and how many of its
   // PWL_TS samples exist.  A lane's share is then a 32-bit offset from a scalar base address, and a full tile
   // -- every tile but the last of a slice of odd size -- takes the unmasked path.
-  struct Tile { int slice; int valid; int64_t g0; int64_t st0; int64_t gin; };
-  auto tile_of = [&](int tile) {
+  // A block's tiles are contiguous: only its first tile's slice takes a division, each next tile steps (slice, ti).
+  struct Tile { int slice; int ti; int valid; int64_t g0; int64_t st0; int64_t gin; };
+  auto tile_at = [&](int slice, int ti) {
     Tile t;
-    t.slice = tile / a.tiles_per_slice;
+    t.slice = slice;
+    t.ti = ti;
     const int64_t s0 = (int64_t)t.slice * a.slice_len;
     const int64_t len = a.B - s0 < a.slice_len ? a.B - s0 : a.slice_len;
-    const int64_t jt = (int64_t)(tile - t.slice * a.tiles_per_slice) * PWL_TS;
+    const int64_t jt = (int64_t)ti * PWL_TS;
     const int64_t left = len - jt;
     t.valid = left >= PWL_TS ? PWL_TS : (left > 0 ? (int)left : 0);
     t.g0 = s0 + jt;
     t.gin = a.in_shared ? jt : t.g0;
     t.st0 = a.first_sample + (int64_t)t.slice * a.slice_stride + jt;      // (seeded calls: the tile's first stream sample)
     return t;
+  };
+  auto tile_of = [&](int tile) { const int sl = tile / a.tiles_per_slice; return tile_at(sl, tile - sl * a.tiles_per_slice); };
+  auto tile_next = [&](const Tile& t) {
+    return t.ti + 1 < a.tiles_per_slice ? tile_at(t.slice, t.ti + 1) : tile_at(t.slice + 1, 0);
   };
   const uint32_t lane2 = 2u * (uint32_t)tid;             // the lane's first sample within the tile
   auto tile_points = [&](const Tile& t) {
@@ -806,9 +820,10 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   // The points of tile i + 1 are requested before tile i is computed: measured (r02e PMC) a wave spent half its
   // time in s_waitcnt, much of it on this one load issued right in front of its first use.
   [[maybe_unused]] f4 xn = {0.f, 0.f, 0.f, 0.f};
-  if (t0 < t1) xn = tile_points(tile_of(t0));
+  Tile tn{};
+  if (t0 < t1) { tn = tile_of(t0); xn = tile_points(tn); }
   for (int tile = t0; tile < t1; ++tile) {
-    const Tile tl = tile_of(tile);
+    const Tile tl = tn;
     const int slice = tl.slice;
     if (slice != cur) {
       __syncthreads();
@@ -819,7 +834,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     const bool full = tl.valid == PWL_TS;
     const bool v0 = (int)lane2 < tl.valid, v1 = (int)lane2 + 1 < tl.valid;
     const f4 x = xn;
-    if (tile + 1 < t1) xn = tile_points(tile_of(tile + 1));
+    if (tile + 1 < t1) { tn = tile_next(tl); xn = tile_points(tn); }
     __builtin_amdgcn_sched_barrier(0);
     v2f u0 = {x[0], x[2]}, u1 = {x[1], x[3]};
     [[maybe_unused]] v2f poison = splat<v2f>(0.0f);      // (flow_kernel: a NaN coordinate must come out as NaN)
@@ -828,7 +843,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     v2f base = splat<v2f>(0.0f);
     if (!TO_BASE && a.aux_mode == AUX_LOGPROB && a.aux) base = (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI);
     BaseAcc<v2f> bacc;
-    const v2f acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
+    const v2f acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX, true>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
                                                             u0, u1, &a.m.scd, e2tab, tabd, &bacc);
     if (a.aux) {
       v2f r = acc;
