@@ -8,12 +8,12 @@
 #include <vector>
 
 #include "cnf_device.h"
+#include "cnf_terms.h"
 #include "../../include/cnf_ot_amd.h"
 
 namespace cnf {
 
 constexpr int TILE = 256;
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
 
 struct ModelArgs {
   const float* prep;     // prepared model buffer
@@ -33,30 +33,6 @@ template <> __device__ __forceinline__ const SplineConstsT<double>& sc_of<double
 template <class R> __device__ __forceinline__ const R* table_of(const ModelArgs& a);
 template <> __device__ __forceinline__ const float* table_of<float>(const ModelArgs& a) { return a.prep; }
 template <> __device__ __forceinline__ const double* table_of<double>(const ModelArgs& a) { return a.tabd; }
-
-// target drift of flow_matching_loss_fn at r (this thread's column `r3`), dim i
-template <class T>
-__device__ __forceinline__ T drift_of(const float* r3, int i, int D, int TS, int subtype, float a) {
-  const T ri = lds_get<T>(r3, i, TS);
-  switch (subtype) {
-    case CNF_DRIFT_SMILE: {          // applications.py:353-357 (2-D)
-      const T x = lds_get<T>(r3, 0, TS), y = lds_get<T>(r3, 1, TS);
-      const T q = x * x + y * y - 4.0f;
-      return (i == 0 ? -q * x : -q * y - (y - 1.0f) * 2.0f) * a;
-    }
-    case CNF_DRIFT_NONGRADIENT: {    // applications.py:358-363: -a r + 0.5 (r @ J), J=[[0,1],[-1,0]]
-      const T x = lds_get<T>(r3, 0, TS), y = lds_get<T>(r3, 1, TS);
-      return i == 0 ? x * -a - y * 0.5f : y * -a + x * 0.5f;
-    }
-    case CNF_DRIFT_LORENZ: {         // applications.py:364-372, _r = 9
-      const T x = lds_get<T>(r3, 0, TS), y = lds_get<T>(r3, 1, TS), z = lds_get<T>(r3, 2, TS);
-      if (i == 0) return (y - x) * 10.0f;
-      if (i == 1) return x * 9.0f * (splat<T>(28.0f / 9.0f) - z) - y;
-      return x * 9.0f * y - z * (8.0f / 3.0f);
-    }
-    default: return ri * -a;         // OU drift, applications.py:310
-  }
-}
 
 }  // namespace cnf
 
@@ -184,6 +160,26 @@ static inline int64_t balanced_grid(int64_t n_tiles, int64_t capacity) {
   if (capacity < 1) capacity = 1;
   if (n_tiles < 1) n_tiles = 1;
   return n_tiles < capacity ? n_tiles : capacity;
+}
+
+// Argument checks of a term spec (cnf_terms.h computes the terms; anything else must never reach a kernel)
+static inline bool potential_ok(int subtype) { return subtype >= CNF_POT_QUADRATIC && subtype <= CNF_POT_OBSTACLE; }
+// the reference raises for the 2-D / 3-D fields at other dimensions (applications.py:359,365); SMILE is 2-D by construction
+static inline bool drift_ok(int subtype, int D) {
+  if (subtype == CNF_DRIFT_SMILE || subtype == CNF_DRIFT_NONGRADIENT) return D == 2;
+  if (subtype == CNF_DRIFT_LORENZ) return D == 3;
+  return subtype == CNF_DRIFT_OU;
+}
+// CNF_OK or CNF_ERR_INVALID: the checks of cnf_loss_terms and cnf_loss_terms_grad
+static inline int term_spec_check(const CnfLossSpec* spec, int D) {
+  if (!spec || spec->kind < CNF_TERM_KINETIC || spec->kind > CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
+  if (spec->kind <= CNF_TERM_FLOW_MATCHING && !(spec->dt > 0.f)) return CNF_ERR_INVALID;
+  if ((spec->kind == CNF_TERM_KINETIC_SCORE || spec->kind == CNF_TERM_FLOW_MATCHING) && !(spec->dx > 0.f))
+    return CNF_ERR_INVALID;
+  if (spec->kind == CNF_TERM_FLOW_MATCHING && !drift_ok(spec->subtype, D)) return CNF_ERR_INVALID;
+  if (spec->kind == CNF_TERM_POTENTIAL && !potential_ok(spec->subtype)) return CNF_ERR_INVALID;
+  if (spec->kind == CNF_TERM_REVERSE_KL && (!(spec->T > 0.f) || !(spec->beta > 0.f))) return CNF_ERR_INVALID;
+  return CNF_OK;
 }
 
 // Orders a compute call after the last cnf_model_set_params when that ran on a different stream.

@@ -428,14 +428,6 @@ __device__ __forceinline__ T flow_pass(const ModelArgs& a, const typename Lanes<
   return acc;
 }
 
-template <class T>
-__device__ __forceinline__ T base_logprob(const typename Lanes<T>::real* col, int D, int TS) {
-  typedef typename Lanes<T>::real R;
-  T b = splat<T>(0.0f);
-  for (int d = 0; d < D; ++d) { const T x = lds_get<T>(col, d, TS); b = vfma(x * (R)-0.5, x, b); }
-  return b - (R)(D * HALF_LOG_2PI);
-}
-
 __device__ __forceinline__ void store_aux(float* aux, int64_t i, int64_t B, float r) {
   if (i < B) aux[i] = r;
 }
@@ -485,7 +477,7 @@ __global__ __launch_bounds__(TILE, 2) void flow_kernel(const FlowArgsT<typename 
     __syncthreads();
 
     T base = splat<T>(0.0f);
-    if (!TO_BASE && a.aux_mode == AUX_LOGPROB && a.aux) base = base_logprob<T>(U + SPL * threadIdx.x, DD, TS);
+    if (!TO_BASE && a.aux_mode == AUX_LOGPROB && a.aux) base = base_logprob<T>(lds_col<T>(U + SPL * threadIdx.x, TS), DD);
     BaseAcc<T> bacc;
     // data -> base: the splines' clamps and bin searches turn a NaN coordinate into a finite point (log_prob(NaN) came
     // out as -58.9); the reference's arithmetic propagates it.  v - v is 0 for a finite v and NaN otherwise.
@@ -499,7 +491,7 @@ __global__ __launch_bounds__(TILE, 2) void flow_kernel(const FlowArgsT<typename 
       if (a.aux_mode == AUX_LOGPROB) {
         // log_prob = base(x) + ildj (conditional.py:316-321); lp_y = lp_x - fldj (:399-401)
         if constexpr (PRECISE) r = bacc.log_prob(acc, DD);
-        else r = TO_BASE ? base_logprob<T>(U + SPL * threadIdx.x, DD, TS) + acc : base - acc;
+        else r = TO_BASE ? base_logprob<T>(lds_col<T>(U + SPL * threadIdx.x, TS), DD) + acc : base - acc;
       }
       if constexpr (TO_BASE) r += poison;
       if (TO_BASE && !PRECISE && a.fd2) store_fd(a, i, r);
@@ -575,7 +567,7 @@ __global__ __launch_bounds__(1024) void flow_dpar_kernel(const FlowArgs a) {
     const T c = load_cond<T>(a, tile_start, i);
     __syncthreads();
     T base = splat<T>(0.0f);
-    if (wave == 0 && a.aux_mode == AUX_LOGPROB && a.aux) base = base_logprob<T>(U + SPL * lane, D, TS);
+    if (wave == 0 && a.aux_mode == AUX_LOGPROB && a.aux) base = base_logprob<T>(lds_col<T>(U + SPL * lane, TS), D);
     T acc = splat<T>(0.0f);
     for (int l = 0; l < L; ++l) {
       const bool odd = l & 1;                              // flows.py:141-143 perms
@@ -893,24 +885,6 @@ __device__ __forceinline__ void copy_cols(float* dst, const float* src, int D, i
   for (int d = 0; d < D; ++d) lds_put(dst, d, TS, lds_get<T>(src, d, TS));
 }
 
-template <bool FAST, class T>
-__device__ __forceinline__ T potential_of(const float* y, int D, int TS, int subtype, float a) {
-  using M = Math<FAST>;
-  if (subtype == CNF_POT_DOUBLE_WELL) {      // (|r-a1| |r+a1| / 2)^2, applications.py:184-188
-    T sm = splat<T>(0.0f), sp = splat<T>(0.0f);
-    for (int d = 0; d < D; ++d) {
-      const T r = lds_get<T>(y, d, TS);
-      sm = vfma(r - a, r - a, sm);
-      sp = vfma(r + a, r + a, sp);
-    }
-    return sm * sp * 0.25f;
-  }
-  T s2 = splat<T>(0.0f);
-  for (int d = 0; d < D; ++d) { const T r = lds_get<T>(y, d, TS); s2 = vfma(r, r, s2); }
-  if (subtype == CNF_POT_OBSTACLE) return M::exp(s2 * -0.5f) * 50.0f;   // applications.py:190-191
-  return s2 * 0.5f;                                                      // quadratic, :181-182
-}
-
 __device__ __forceinline__ float mask_tail(float v, int64_t i, int64_t B) { return i < B ? v : 0.0f; }
 __device__ __forceinline__ float mask_tail(v2f v, int64_t i, int64_t B) {
   return (i < B ? v.x : 0.0f) + (i + 1 < B ? v.y : 0.0f);
@@ -973,22 +947,12 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
       }
     }
     if (kind == CNF_TERM_KINETIC) {
-      for (int d = 0; d < D; ++d) { const T v = lds_get<T>(V + col, d, TS); acc = vfma(v, v, acc); }
+      acc = sq_norm<T>(lds_col<T>(V + col, TS), D);
     } else if (kind == CNF_TERM_POTENTIAL) {
-      acc = potential_of<FAST, T>(U + col, D, TS, a.spec.subtype, a.spec.a);
+      acc = potential<FAST, T>(lds_col<T>(U + col, TS), D, a.spec.subtype, a.spec.a).v;
     } else if (kind == CNF_TERM_REVERSE_KL) {
-      const T lp = base_logprob<T>(Nn + col, D, TS) - fldj;
-      T s2 = splat<T>(0.0f);
-      for (int d = 0; d < D; ++d) { const T r = lds_get<T>(U + col, d, TS); s2 = vfma(r, r, s2); }
-      // log(N(y;0,vs I) ws + N(y;0,vt I) wt) as a log-sum-exp (applications.py:136-163)
-      const float Tt = a.spec.T, vs = 2.0f / a.spec.beta * (Tt + 1.0f), vt = 2.0f / a.spec.beta;
-      const float ws = (Tt - t) / Tt, wt = t / Tt;
-      const float ls = -0.5f * D * logf(6.283185307179586f * vs), lt = -0.5f * D * logf(6.283185307179586f * vt);
-      const T as = vfma(s2, splat<T>(-0.5f / vs), splat<T>(ls));
-      const T at = vfma(s2, splat<T>(-0.5f / vt), splat<T>(lt));
-      const T mx = vmax(as, at);
-      const T mix = M::exp(as - mx) * ws + M::exp(at - mx) * wt;
-      acc = lp - (mx + M::log(mix));
+      const T lp = base_logprob<T>(lds_col<T>(Nn + col, TS), D) - fldj;
+      acc = lp - rkl_mixture<FAST, T>(lds_col<T>(U + col, TS), D, t, a.spec.T, a.spec.beta).logmix;
     }
     // data->base passes: NEG_LOGPROB (one, on the points themselves) or the
     // central differences of log_prob at r3 +- dx/2 e_d (applications.py:264-273)
@@ -1001,13 +965,13 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
       copy_cols<T>(U + col, (neg ? Nn : R) + col, D, TS);
       if (!neg) lds_put(U + col, d, TS, lds_get<T>(R + col, d, TS) + (sgn == 0 ? 0.5f * dx : -0.5f * dx));
       const T ildj = flow_pass<H, K, true, FAST, T>(a.m, tab, U, O, splat<T>(t));
-      const T lp = base_logprob<T>(U + col, D, TS) + ildj;
+      const T lp = base_logprob<T>(lds_col<T>(U + col, TS), D) + ildj;
       if (neg) acc = -lp;
       else if (sgn == 0) lp0 = lp;
       else {
-        T v = vfma((lp0 - lp) * (1.0f / dx), splat<T>(a.spec.coef), lds_get<T>(V + col, d, TS));
-        if (kind == CNF_TERM_FLOW_MATCHING) v -= drift_of<T>(R + col, d, D, TS, a.spec.subtype, a.spec.a);
-        acc = vfma(v, v, acc);
+        const T dr = drift_field<T>(lds_col<T>(R + col, TS), d, kind == CNF_TERM_FLOW_MATCHING ? a.spec.subtype : -1, a.spec.a);
+        const T u = score_residual(lds_get<T>(V + col, d, TS), (lp0 - lp) * (1.0f / dx), a.spec.coef, dr);
+        acc = vfma(u, u, acc);
       }
     }
     // tile reduction: lanes -> wave (shuffles) -> the wave's running sum of the slice
@@ -1051,7 +1015,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
   const int L = a.m.L;
   float* tab = lds_raw;
   float* tbl = lds_raw + HDR;                               // n_sets x L tables
-  float* R = tbl + a.n_sets * L * PWL_LTBL;                 // 2 x TS scratch columns (potential_of / drift_of read LDS columns)
+  float* R = tbl + a.n_sets * L * PWL_LTBL;                 // 2 x TS scratch columns: r3 for drift_field (registers spill)
   for (int i = tid; i < hdr_floats(K); i += NT) tab[i] = table_of<float>(a.m)[i];
   const SplineConsts sc = sc_scalars(sc_of<float>(a.m));
   const int kind = a.spec.kind;
@@ -1101,11 +1065,13 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
       if (!v1) { x[2] = 0.f; x[3] = 0.f; }
     }
     const T n0 = {x[0], x[2]}, n1 = {x[1], x[3]};
+    auto n = [&](int q) { return q == 0 ? n0 : n1; };
 
     T acc = splat<T>(0.0f);
     const int n_fwd = kind == CNF_TERM_NEG_LOGPROB ? 0 : (kind == CNF_TERM_KINETIC ? 2 : (kin ? 3 : 1));
     T fldj = splat<T>(0.0f);
     T y0 = n0, y1 = n1, va = splat<T>(0.0f), vb = splat<T>(0.0f);     // (va, vb): r1, then the velocity
+    auto y = [&](int q) { return q == 0 ? y0 : y1; };
     for (int p = 0; p < n_fwd; ++p) {                                  // set p: conditions t - dt/2, t + dt/2, t (kin) or t
       y0 = n0; y1 = n1;
       fldj = flow2_tables<K, false, FAST, false, true>(tab, tbl + p * L * PWL_LTBL, gslice + p * set_stride, L, sc, y0, y1);
@@ -1118,20 +1084,9 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
     if (kind == CNF_TERM_KINETIC) {
       acc = vfma(va, va, vb * vb);
     } else if (kind == CNF_TERM_POTENTIAL) {
-      lds_put(R + col, 0, TS, y0); lds_put(R + col, 1, TS, y1);
-      acc = potential_of<FAST, T>(R + col, 2, TS, a.spec.subtype, a.spec.a);
+      acc = potential<FAST, T>(y, 2, a.spec.subtype, a.spec.a).v;
     } else if (kind == CNF_TERM_REVERSE_KL) {
-      const T lp = vfma(n0 * -0.5f, n0, n1 * n1 * -0.5f) - (float)(2 * HALF_LOG_2PI) - fldj;
-      const T s2 = vfma(y0, y0, y1 * y1);
-      // log(N(y;0,vs I) ws + N(y;0,vt I) wt) as a log-sum-exp (applications.py:136-163)
-      const float Tt = a.spec.T, vs = 2.0f / a.spec.beta * (Tt + 1.0f), vt = 2.0f / a.spec.beta;
-      const float ws = (Tt - t) / Tt, wt = t / Tt;
-      const float ls = -logf(6.283185307179586f * vs), lt = -logf(6.283185307179586f * vt);    // -0.5 D log(2 pi v), D = 2
-      const T as = vfma(s2, splat<T>(-0.5f / vs), splat<T>(ls));
-      const T at = vfma(s2, splat<T>(-0.5f / vt), splat<T>(lt));
-      const T mx = vmax(as, at);
-      const T mix = M::exp(as - mx) * ws + M::exp(at - mx) * wt;
-      acc = lp - (mx + M::log(mix));
+      acc = base_logprob<T>(n, 2) - fldj - rkl_mixture<FAST, T>(y, 2, t, a.spec.T, a.spec.beta).logmix;
     }
     // data->base passes: NEG_LOGPROB (one, on the points themselves) or the central differences of
     // log_prob at r3 +- dx/2 e_d (applications.py:264-273); r3 = (y0, y1) of the pass at condition t
@@ -1147,13 +1102,13 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
         if (d == 0) u0 = u0 + h; else u1 = u1 + h;
       }
       const T ildj = flow2_tables<K, true, FAST, false, true>(tab, tbl + tset * L * PWL_LTBL, gslice + tset * set_stride, L, sc, u0, u1);
-      const T lp = vfma(u0 * -0.5f, u0, u1 * u1 * -0.5f) - (float)(2 * HALF_LOG_2PI) + ildj;
+      const T lp = base_logprob<T>([&](int q) { return q == 0 ? u0 : u1; }, 2) + ildj;
       if (neg) acc = -lp;
       else if (sgn == 0) lp0 = lp;
       else {
-        T v = vfma((lp0 - lp) * (1.0f / dx), splat<T>(a.spec.coef), d == 0 ? va : vb);
-        if (kind == CNF_TERM_FLOW_MATCHING) v -= drift_of<T>(R + col, d, 2, TS, a.spec.subtype, a.spec.a);
-        acc = vfma(v, v, acc);
+        const T dr = drift_field<T>(lds_col<T>(R + col, TS), d, kind == CNF_TERM_FLOW_MATCHING ? a.spec.subtype : -1, a.spec.a);
+        const T u = score_residual(d == 0 ? va : vb, (lp0 - lp) * (1.0f / dx), a.spec.coef, dr);
+        acc = vfma(u, u, acc);
       }
     }
     // tile reduction: lanes -> wave (shuffles) -> the wave's running sum of the slice
@@ -2093,21 +2048,9 @@ static int loss_terms_impl(CnfModel* m, const CnfLossSpec* spec, const float* pt
                            double* sums, void* stream_) {
   if (!m || !spec || !t || !sums || n_slices < 0 || B < 0 || slice_stride < 0 || first_sample < 0) return CNF_ERR_INVALID;
   if (!m->params_set) return CNF_ERR_INVALID;
-  if (spec->kind < CNF_TERM_KINETIC || spec->kind > CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
+  if (term_spec_check(spec, m->cfg.dim) != CNF_OK) return CNF_ERR_INVALID;
   if (m->cfg.periodized) return CNF_ERR_UNSUPPORTED;      // flow functions only (include/cnf_ot_amd.h: CnfConfig)
   const int D = m->cfg.dim;
-  if (spec->kind <= CNF_TERM_FLOW_MATCHING && !(spec->dt > 0.f)) return CNF_ERR_INVALID;
-  if ((spec->kind == CNF_TERM_KINETIC_SCORE || spec->kind == CNF_TERM_FLOW_MATCHING) && !(spec->dx > 0.f))
-    return CNF_ERR_INVALID;
-  if (spec->kind == CNF_TERM_FLOW_MATCHING) {
-    // the reference raises for these (applications.py:359,365); SMILE is 2-D by construction
-    if ((spec->subtype == CNF_DRIFT_SMILE || spec->subtype == CNF_DRIFT_NONGRADIENT) && D != 2) return CNF_ERR_INVALID;
-    if (spec->subtype == CNF_DRIFT_LORENZ && D != 3) return CNF_ERR_INVALID;
-    if (spec->subtype < CNF_DRIFT_OU || spec->subtype > CNF_DRIFT_LORENZ) return CNF_ERR_INVALID;
-  }
-  if (spec->kind == CNF_TERM_POTENTIAL && (spec->subtype < CNF_POT_QUADRATIC || spec->subtype > CNF_POT_OBSTACLE))
-    return CNF_ERR_INVALID;
-  if (spec->kind == CNF_TERM_REVERSE_KL && (!(spec->T > 0.f) || !(spec->beta > 0.f))) return CNF_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
   if (n_slices == 0) return CNF_OK;
   if (hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_slices, stream) != hipSuccess) return CNF_ERR_HIP;

@@ -261,39 +261,6 @@ __device__ __forceinline__ float* pass_bwd(const ModelArgs& a, float* lds, const
   return Aout;
 }
 
-__device__ __forceinline__ float base_lp(const float* col, int D) {
-  float b = 0.0f;
-  for (int d = 0; d < D; ++d) { const float x = col[d * GROW]; b = fmaf(-0.5f * x, x, b); }
-  return b - (float)(D * HALF_LOG_2PI);
-}
-
-// R3b[e] -= sum_d ubar_d * d drift_d / d r_e   (flow_matching_loss_fn's target field)
-__device__ __forceinline__ void drift_vjp(const float* r3, const float* ub, float* r3b, int D, int subtype, float a) {
-  switch (subtype) {
-    case CNF_DRIFT_SMILE: {
-      const float x = r3[0], y = r3[GROW], q = x * x + y * y - 4.0f, u0 = ub[0], u1 = ub[GROW];
-      r3b[0] -= u0 * (-a * (q + 2.0f * x * x)) + u1 * (-a * 2.0f * x * y);
-      r3b[GROW] -= u0 * (-a * 2.0f * x * y) + u1 * (-a * (q + 2.0f * y * y + 2.0f));
-      break;
-    }
-    case CNF_DRIFT_NONGRADIENT: {
-      const float u0 = ub[0], u1 = ub[GROW];
-      r3b[0] -= u0 * (-a) + u1 * 0.5f;
-      r3b[GROW] -= u0 * (-0.5f) + u1 * (-a);
-      break;
-    }
-    case CNF_DRIFT_LORENZ: {
-      const float x = r3[0], y = r3[GROW], z = r3[2 * GROW], u0 = ub[0], u1 = ub[GROW], u2 = ub[2 * GROW];
-      r3b[0] -= u0 * -10.0f + u1 * (28.0f - 9.0f * z) + u2 * 9.0f * y;
-      r3b[GROW] -= u0 * 10.0f - u1 + u2 * 9.0f * x;
-      r3b[2 * GROW] -= u1 * (-9.0f * x) + u2 * (-8.0f / 3.0f);
-      break;
-    }
-    default:
-      for (int d = 0; d < D; ++d) r3b[d * GROW] += a * ub[d * GROW];
-  }
-}
-
 // Roles of the steps of a tile's pass program.  Every step is: build the pass
 // input, run the forward with stash, act on its result, optionally seed and run
 // the backward, act on the input adjoint.
@@ -367,6 +334,7 @@ __global__ __launch_bounds__(GTS_MAX, 2) void grad_kernel(const GradArgs a) {
     float* r3 = R3 + tid;
     float* r3b = R3b + tid;
     float* ub = Ub + tid;
+    const auto out = lds_col<float>(sL, GROW);      // the pass's output point
     float lossv = 0.0f, lp_plus = 0.0f, ubar = 0.0f;
 
     for (int st = 0; st < n_steps; ++st) {
@@ -397,45 +365,22 @@ __global__ __launch_bounds__(GTS_MAX, 2) void grad_kernel(const GradArgs a) {
       float ld_bar = 0.0f;
       switch (role) {
         case R_NEG: {
-          lossv = -(base_lp(sL, D) + ldsum);
+          lossv = -(base_logprob<float>(out, D) + ldsum);
           for (int e = 0; e < D; ++e) aa[e * GROW] = sc * sL[e * GROW];      // d(-lp)/dx_e = x_e
           ld_bar = -sc; do_bwd = true;
           break;
         }
         case R_POT: {
-          const float pa = J.spec.a;
-          if (J.spec.subtype == CNF_POT_DOUBLE_WELL) {
-            float sm = 0.0f, sp = 0.0f;
-            for (int e = 0; e < D; ++e) { const float r = sL[e * GROW]; sm = fmaf(r - pa, r - pa, sm); sp = fmaf(r + pa, r + pa, sp); }
-            lossv = sm * sp * 0.25f;
-            for (int e = 0; e < D; ++e) { const float r = sL[e * GROW]; aa[e * GROW] = sc * 0.5f * ((r - pa) * sp + (r + pa) * sm); }
-          } else {
-            float s2 = 0.0f;
-            for (int e = 0; e < D; ++e) { const float r = sL[e * GROW]; s2 = fmaf(r, r, s2); }
-            if (J.spec.subtype == CNF_POT_OBSTACLE) {
-              lossv = 50.0f * expf(-0.5f * s2);
-              for (int e = 0; e < D; ++e) aa[e * GROW] = -sc * lossv * sL[e * GROW];
-            } else {
-              lossv = 0.5f * s2;
-              for (int e = 0; e < D; ++e) aa[e * GROW] = sc * sL[e * GROW];
-            }
-          }
+          const Potential<float> p = potential<false, float>(out, D, J.spec.subtype, J.spec.a);
+          lossv = p.v;
+          for (int e = 0; e < D; ++e) aa[e * GROW] = sc * p.grad(sL[e * GROW]);
           do_bwd = true;
           break;
         }
         case R_RKL: {
-          const float lp = base_lp(n_, D) - ldsum;
-          float s2 = 0.0f;
-          for (int e = 0; e < D; ++e) { const float r = sL[e * GROW]; s2 = fmaf(r, r, s2); }
-          const float Tt = J.spec.T, vs = 2.0f / J.spec.beta * (Tt + 1.0f), vt = 2.0f / J.spec.beta;
-          const float ws = (Tt - t) / Tt, wt = t / Tt;
-          const float ls = -0.5f * D * logf(6.283185307179586f * vs), lt = -0.5f * D * logf(6.283185307179586f * vt);
-          const float as = -0.5f * s2 / vs + ls, at = -0.5f * s2 / vt + lt;
-          const float mx = fmaxf(as, at);
-          const float es = expf(as - mx) * ws, et = expf(at - mx) * wt;
-          lossv = lp - (mx + logf(es + et));
-          const float g = (es / vs + et / vt) / (es + et);      // -d logmix / d y_e = g * y_e
-          for (int e = 0; e < D; ++e) aa[e * GROW] = sc * g * sL[e * GROW];
+          const RklMix<float> mix = rkl_mixture<false, float>(out, D, t, J.spec.T, J.spec.beta);
+          lossv = base_logprob<float>(lds_col<float>(n_, GROW), D) - ldsum - mix.logmix;
+          for (int e = 0; e < D; ++e) aa[e * GROW] = sc * mix.g * sL[e * GROW];
           ld_bar = -sc; do_bwd = true;
           break;
         }
@@ -460,14 +405,14 @@ __global__ __launch_bounds__(GTS_MAX, 2) void grad_kernel(const GradArgs a) {
           for (int e = 0; e < D; ++e) { r3[e * GROW] = sL[e * GROW]; r3b[e * GROW] = 0.0f; }
           break;
         case R_LPP:
-          lp_plus = base_lp(sL, D) + ldsum;
+          lp_plus = base_logprob<float>(out, D) + ldsum;
           break;
         case R_LPM: {
-          const float lp_minus = base_lp(sL, D) + ldsum;
-          float u = fmaf((lp_plus - lp_minus) / dx, coef, v_[dd * GROW]);
-          if (kind == CNF_TERM_FLOW_MATCHING) u -= drift_of<float>(r3, dd, D, GROW, J.spec.subtype, J.spec.a);
+          const float lp_minus = base_logprob<float>(out, D) + ldsum;
+          const float dr = drift_field<float>(lds_col<float>(r3, GROW), dd, kind == CNF_TERM_FLOW_MATCHING ? J.spec.subtype : -1, J.spec.a);
+          const float u = score_residual(v_[dd * GROW], (lp_plus - lp_minus) / dx, coef, dr);
           lossv = fmaf(u, u, lossv);
-          ubar = 2.0f * sc * u;
+          ubar = score_residual_bar(u, sc);
           ub[dd * GROW] = ubar;
           ld_bar = -ubar * coef / dx;                // d u / d lp_minus
           for (int e = 0; e < D; ++e) aa[e * GROW] = -ld_bar * sL[e * GROW];     // d base / d x_e = -x_e
@@ -480,7 +425,9 @@ __global__ __launch_bounds__(GTS_MAX, 2) void grad_kernel(const GradArgs a) {
           do_bwd = true;
           break;
         case R_R3B:
-          if (kind == CNF_TERM_FLOW_MATCHING) drift_vjp(r3, ub, r3b, D, J.spec.subtype, J.spec.a);
+          if (kind == CNF_TERM_FLOW_MATCHING)
+            drift_adjoint(lds_col<float>(r3, GROW), lds_col<float>(ub, GROW), D, J.spec.subtype, J.spec.a,
+                          [&](int e, float b) { r3b[e * GROW] += b; });
           for (int e = 0; e < D; ++e) aa[e * GROW] = r3b[e * GROW];
           do_bwd = true;
           break;
@@ -621,17 +568,17 @@ __global__ __launch_bounds__(GTS_MAX, 2) void vjp_kernel(const VjpArgs a) {
         const bool valid = tid < tp && i < a.B;
         const int64_t ib = valid ? i / a.fd2 : 0;
         const int k = (int)(i - ib * a.fd2), dd = k >> 1;
-        const float lp = base_lp(sL, D) + ldsum;
+        const float lp = base_logprob<float>(lds_col<float>(sL, GROW), D) + ldsum;
         const float other = __shfl_xor(lp, 1, 64);             // (groups start at even lanes: the partner is lane ^ 1)
         const float score = ((k & 1) ? other - lp : lp - other) * a.fd_inv_dx;
         const int64_t o = ib * D + dd;
         const float r3d = valid ? a.pts[o] : 0.0f;
         const float vel = valid ? (a.r2[o] - a.r1[o]) * a.inv_dt : 0.0f;
-        const float drift = a.drift == CNF_DRIFT_OU ? -a.drift_a * r3d : 0.0f;
-        const float u = valid ? fmaf(score, a.coef, vel) - drift : 0.0f;
-        const float ub = 2.0f * a.loss_coef * u;
+        const bool ou = a.drift == CNF_DRIFT_OU;                // (a lane per dimension: the diagonal field or none)
+        const float u = valid ? score_residual(vel, score, a.coef, ou ? ou_drift(r3d, a.drift_a) : 0.0f) : 0.0f;
+        const float ub = score_residual_bar(u, a.loss_coef);
         ld_bar = ((k & 1) ? -a.coef : a.coef) * ub * a.fd_inv_dx;
-        ub_drift = a.drift == CNF_DRIFT_OU ? a.drift_a * ub : 0.0f;
+        ub_drift = ou ? ou_drift_adjoint(ub, a.drift_a) : 0.0f;
         const bool owner = valid && !(k & 1);                  // one lane of the pair writes / counts
         if (owner) { a.rbar1[o] = -ub * a.inv_dt; a.rbar2[o] = ub * a.inv_dt; }
         // per-slice sums of u^2: lanes are ordered by point, so a wave's slices are those of its first and last valid lane
@@ -1024,7 +971,7 @@ __global__ __launch_bounds__(VJP_PWL_THREADS) void vjp_pwl_kernel(const VjpPwlAr
     }
     if constexpr (SEED) {
       // -log_prob = |x|^2 / 2 + log 2 pi - ildj at the recovered base point x; d(seed_coef * sum) / d(x, ildj)
-      const v2f nlp = vfma(u0, u0, u1 * u1) * 0.5f + (float)(2 * HALF_LOG_2PI) - lacc;
+      const v2f nlp = -base_logprob<v2f>([&](int q) { return q == 0 ? u0 : u1; }, 2) - lacc;
       float part = (v0 ? nlp.x : 0.0f) + (v1 ? nlp.y : 0.0f);
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
@@ -1358,44 +1305,28 @@ __global__ __launch_bounds__(256) void score_residual_kernel(const ResidArgs a) 
     const float* r2 = a.r + (a.n + i) * D;
     const float* r3 = a.r + (2 * a.n + i) * D;
     const float* sc = a.score + i * D;
-    float x = r3[0], y = D > 1 ? r3[1] : 0.0f, z = D > 2 ? r3[2] : 0.0f;
+    float* r3b = a.rbar + (2 * a.n + i) * D;
+    const bool ou = a.subtype == CNF_DRIFT_OU;
+    // the coupled 2-D / 3-D fields' coordinates and u_bar, in registers (read before any store: rbar may alias r)
+    const float x = r3[0], y = D > 1 ? r3[1] : 0.0f, z = D > 2 ? r3[2] : 0.0f;
+    const auto r = [&](int e) { return e == 0 ? x : (e == 1 ? y : z); };
     float ub0 = 0.f, ub1 = 0.f, ub2 = 0.f;
     for (int d = 0; d < D; ++d) {
-      float drift = 0.0f;
-      switch (a.subtype) {
-        case CNF_DRIFT_OU: drift = -a.a * r3[d]; break;
-        case CNF_DRIFT_SMILE: { const float q = x * x + y * y - 4.0f; drift = (d == 0 ? -q * x : -q * y - (y - 1.0f) * 2.0f) * a.a; break; }
-        case CNF_DRIFT_NONGRADIENT: drift = d == 0 ? x * -a.a - y * 0.5f : y * -a.a + x * 0.5f; break;
-        case CNF_DRIFT_LORENZ: drift = d == 0 ? (y - x) * 10.0f : (d == 1 ? x * 9.0f * (28.0f / 9.0f - z) - y : x * 9.0f * y - z * (8.0f / 3.0f)); break;
-        default: break;
-      }
-      const float u = fmaf(sc[d], a.coef, (r2[d] - r1[d]) * a.inv_dt) - drift;
+      const float drift = ou ? ou_drift(r3[d], a.a) : drift_field<float>(r, d, a.subtype, a.a);
+      const float u = score_residual((r2[d] - r1[d]) * a.inv_dt, sc[d], a.coef, drift);
       acc = fmaf(u, u, acc);
       if (a.rbar) {
-        const float ub = 2.0f * a.loss_coef * u;
+        const float ub = score_residual_bar(u, a.loss_coef);
         a.rbar[i * D + d] = -ub * a.inv_dt;
         a.rbar[(a.n + i) * D + d] = ub * a.inv_dt;
         a.sbar[i * D + d] = a.coef * ub;
         if (d == 0) ub0 = ub; else if (d == 1) ub1 = ub; else if (d == 2) ub2 = ub;
-        // r3_bar = -J_drift^T u_bar; the diagonal OU field is complete here, the coupled 2-D / 3-D fields below
-        a.rbar[(2 * a.n + i) * D + d] = a.subtype == CNF_DRIFT_OU ? a.a * ub : 0.0f;
+        r3b[d] = ou ? ou_drift_adjoint(ub, a.a) : 0.0f;      // complete for OU and no drift; the coupled fields below
       }
     }
-    if (a.rbar) {
-      float* r3b = a.rbar + (2 * a.n + i) * D;
-      if (a.subtype == CNF_DRIFT_SMILE) {
-        const float q = x * x + y * y - 4.0f;
-        r3b[0] = -(ub0 * (-a.a * (q + 2.0f * x * x)) + ub1 * (-a.a * 2.0f * x * y));
-        r3b[1] = -(ub0 * (-a.a * 2.0f * x * y) + ub1 * (-a.a * (q + 2.0f * y * y + 2.0f)));
-      } else if (a.subtype == CNF_DRIFT_NONGRADIENT) {
-        r3b[0] = -(ub0 * (-a.a) + ub1 * 0.5f);
-        r3b[1] = -(ub0 * (-0.5f) + ub1 * (-a.a));
-      } else if (a.subtype == CNF_DRIFT_LORENZ) {
-        r3b[0] = -(ub0 * -10.0f + ub1 * (28.0f - 9.0f * z) + ub2 * 9.0f * y);
-        r3b[1] = -(ub0 * 10.0f - ub1 + ub2 * 9.0f * x);
-        r3b[2] = -(ub1 * (-9.0f * x) + ub2 * (-8.0f / 3.0f));
-      }
-    }
+    if (a.rbar && a.subtype > CNF_DRIFT_OU)
+      drift_adjoint(r, [&](int e) { return e == 0 ? ub0 : (e == 1 ? ub1 : ub2); }, D, a.subtype, a.a,
+                    [&](int e, float b) { r3b[e] = b; });
   }
   // a wave whose samples share a slice: shuffle reduce, one double atomic; otherwise one atomic per sample
   const int64_t slice = valid ? i / a.count : -1;
@@ -1446,6 +1377,7 @@ __global__ __launch_bounds__(1024) void term_residual_kernel(const TermResidArgs
   };
   auto term = [&](int64_t i) -> float {      // the term's value at point i; writes the adjoints
     float v = 0.0f;
+    const auto pt = [&](int d) { return a.r[i * D + d]; };
     if (DFIX == 2) {
       const v2f* r2p = reinterpret_cast<const v2f*>(a.r);
       v2f* rb2 = reinterpret_cast<v2f*>(a.rbar);
@@ -1457,18 +1389,14 @@ __global__ __launch_bounds__(1024) void term_residual_kernel(const TermResidArgs
         if (a.rbar) { rb2[i] = dr * -g; rb2[a.n + i] = dr * g; if (a.amax) seen(dr * g); }
       } else if (a.kind == CNF_TERM_POTENTIAL) {
         const v2f x = r2p[i];
-        const float s2 = fmaf(x.x, x.x, x.y * x.y);
-        const v2f xm = x - a.p0, xp = x + a.p0;
-        const float sm = fmaf(xm.x, xm.x, xm.y * xm.y), sp = fmaf(xp.x, xp.x, xp.y * xp.y);
-        v2f gr;
-        if (a.subtype == CNF_POT_DOUBLE_WELL) { v = 0.25f * sm * sp; gr = (xm * sp + xp * sm) * 0.5f; }      // applications.py:184-188
-        else if (a.subtype == CNF_POT_OBSTACLE) { v = 50.0f * expf(-0.5f * s2); gr = x * -v; }                // :190-191
-        else { v = 0.5f * s2; gr = x; }                                                                        // :181-182
-        if (a.rbar) { rb2[i] = gr * a.loss_coef; if (a.amax) seen(gr * a.loss_coef); }
+        const Potential<float> p = potential<false>(x, a.subtype, a.p0);
+        const v2f gr = p.grad(x) * a.loss_coef;      // (formed beside the value: one branch on the subtype)
+        v = p.v;
+        if (a.rbar) { rb2[i] = gr; if (a.amax) seen(gr); }
       } else {      // CNF_TERM_NEG_LOGPROB
         const v2f x = r2p[i];
         if (a.rbar) rb2[i] = x * a.loss_coef;
-        v = -(a.aux[i] - 0.5f * fmaf(x.x, x.x, x.y * x.y) - (float)(2 * HALF_LOG_2PI));
+        v = -base_logprob<float>([&](int e) { return e == 0 ? x.x : x.y; }, 2) - a.aux[i];
         if (a.auxbar) a.auxbar[i] = -a.loss_coef;
       }
     } else {
@@ -1481,32 +1409,17 @@ __global__ __launch_bounds__(1024) void term_residual_kernel(const TermResidArgs
           if (a.rbar) { a.rbar[i * D + d] = -g * dr; a.rbar[(a.n + i) * D + d] = g * dr; }
         }
       } else if (a.kind == CNF_TERM_POTENTIAL) {
-        float s2 = 0.0f, sm = 0.0f, sp = 0.0f;
-        for (int d = 0; d < D; ++d) {
-          const float x = a.r[i * D + d];
-          s2 = fmaf(x, x, s2); sm = fmaf(x - a.p0, x - a.p0, sm); sp = fmaf(x + a.p0, x + a.p0, sp);
-        }
-        if (a.subtype == CNF_POT_DOUBLE_WELL) v = 0.25f * sm * sp;
-        else if (a.subtype == CNF_POT_OBSTACLE) v = 50.0f * expf(-0.5f * s2);
-        else v = 0.5f * s2;
-        if (a.rbar) {
-          for (int d = 0; d < D; ++d) {
-            const float x = a.r[i * D + d];
-            float gr;
-            if (a.subtype == CNF_POT_DOUBLE_WELL) gr = 0.5f * ((x - a.p0) * sp + (x + a.p0) * sm);
-            else if (a.subtype == CNF_POT_OBSTACLE) gr = -v * x;
-            else gr = x;
-            a.rbar[i * D + d] = a.loss_coef * gr;
-          }
-        }
+        const Potential<float> p = potential<false, float>(pt, D, a.subtype, a.p0);
+        v = p.v;
+        if (a.rbar)
+          for (int d = 0; d < D; ++d) a.rbar[i * D + d] = a.loss_coef * p.grad(pt(d));
       } else {
-        float s2 = 0.0f;
-        for (int d = 0; d < D; ++d) {
-          const float x = a.r[i * D + d];
-          s2 = fmaf(x, x, s2);
-          if (a.rbar) a.rbar[i * D + d] = a.loss_coef * x;
-        }
-        v = -(a.aux[i] - 0.5f * s2 - (float)(D * HALF_LOG_2PI));
+        // (one read per coordinate: the accessor also writes its adjoint)
+        v = -base_logprob<float>([&](int d) {
+              const float x = pt(d);
+              if (a.rbar) a.rbar[i * D + d] = a.loss_coef * x;
+              return x;
+            }, D) - a.aux[i];
         if (a.auxbar) a.auxbar[i] = -a.loss_coef;
       }
     }
@@ -1587,18 +1500,10 @@ __global__ __launch_bounds__(256) void rkl_residual_kernel(const RklArgs a) {
   float acc = 0.0f;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
     const int D = a.D;
-    float s2 = 0.0f;
-    for (int d = 0; d < D; ++d) { const float r = a.y[i * D + d]; s2 = fmaf(r, r, s2); }
-    const float vs = 2.0f / a.beta * (a.T + 1.0f), vt = 2.0f / a.beta;
-    const float ws = (a.T - a.t) / a.T, wt = a.t / a.T;
-    const float ls = -0.5f * D * logf(6.283185307179586f * vs), lt = -0.5f * D * logf(6.283185307179586f * vt);
-    const float as = -0.5f * s2 / vs + ls, at = -0.5f * s2 / vt + lt;
-    const float mx = fmaxf(as, at);
-    const float es = expf(as - mx) * ws, et = expf(at - mx) * wt;
-    acc += a.lp[i] - (mx + logf(es + et));
+    const RklMix<float> mix = rkl_mixture<false, float>([&](int d) { return a.y[i * D + d]; }, D, a.t, a.T, a.beta);
+    acc += a.lp[i] - mix.logmix;
     if (a.ybar) {
-      const float g = (es / vs + et / vt) / (es + et);      // -d logmix / d y_e = g * y_e
-      for (int d = 0; d < D; ++d) a.ybar[i * D + d] = a.loss_coef * g * a.y[i * D + d];
+      for (int d = 0; d < D; ++d) a.ybar[i * D + d] = a.loss_coef * mix.g * a.y[i * D + d];
       a.lpbar[i] = a.loss_coef;
     }
   }
@@ -1644,18 +1549,6 @@ extern "C" int cnf_grad_supported(const CnfConfig* c) {
          c->num_layers >= 1 && grad_lds_bytes(c->dim, c->num_layers, 64) <= 160 * 1024;
 }
 
-static int check_term(const CnfModel* m, const CnfLossSpec* spec) {
-  if (!spec || spec->kind < CNF_TERM_KINETIC || spec->kind > CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
-  const int D = m->cfg.dim;
-  if (spec->kind <= CNF_TERM_FLOW_MATCHING && !(spec->dt > 0.f)) return CNF_ERR_INVALID;
-  if ((spec->kind == CNF_TERM_KINETIC_SCORE || spec->kind == CNF_TERM_FLOW_MATCHING) && !(spec->dx > 0.f)) return CNF_ERR_INVALID;
-  if (spec->kind == CNF_TERM_FLOW_MATCHING) {
-    if ((spec->subtype == CNF_DRIFT_SMILE || spec->subtype == CNF_DRIFT_NONGRADIENT) && D != 2) return CNF_ERR_INVALID;
-    if (spec->subtype == CNF_DRIFT_LORENZ && D != 3) return CNF_ERR_INVALID;
-  }
-  return CNF_OK;
-}
-
 extern "C" int cnf_loss_terms_grad_multi(CnfModel* m, int32_t n_terms, const CnfLossSpec* specs, const float* const* pts,
                                          const int32_t* pts_shared, const float* const* t, const int64_t* n_slices,
                                          const int64_t* B, const float* scale, double* const* sums, float* grad,
@@ -1674,10 +1567,10 @@ extern "C" int cnf_loss_terms_grad_multi(CnfModel* m, int32_t n_terms, const Cnf
   GradArgs a;
   a.m = model_args(m); a.slabs = m->grad_slabs; a.n_params = m->n_params; a.div_magic = m->div_magic;
   a.n_jobs = 0; a.n_tiles = 0;
+  for (int i = 0; i < n_terms; ++i)      // (every term is checked before anything is enqueued)
+    if (term_spec_check(specs + i, D) != CNF_OK || !pts[i] || !t[i] || !sums[i] || n_slices[i] < 0 || B[i] < 0)
+      return CNF_ERR_INVALID;
   for (int i = 0; i < n_terms; ++i) {
-    const int r = check_term(m, specs + i);
-    if (r != CNF_OK) return r;
-    if (!pts[i] || !t[i] || !sums[i] || n_slices[i] < 0 || B[i] < 0) return CNF_ERR_INVALID;
     if (n_slices[i] == 0) continue;
     if (hipMemsetAsync(sums[i], 0, sizeof(double) * (size_t)n_slices[i], stream) != hipSuccess) return CNF_ERR_HIP;
     if (B[i] == 0) continue;
@@ -1932,7 +1825,7 @@ extern "C" int cnf_kinetic_potential_vjp(CnfModel* m, const float* z, int64_t co
                                          float c_kin, int32_t subtype, float pot_a, float c_pot, double* kin,
                                          double* pot, float* grad, const float* params, float* work, void* stream_) {
   if (!m || !z || !c || !kin || (grad && !params) || !work || count < 1 || S < 1 || !(dt > 0.f)) return CNF_ERR_INVALID;
-  if ((subtype >= 0) != (pot != nullptr)) return CNF_ERR_INVALID;
+  if ((subtype >= 0) != (pot != nullptr) || (subtype >= 0 && !potential_ok(subtype))) return CNF_ERR_INVALID;
   if (!m->params_set || (grad && !m->grad_slabs)) return CNF_ERR_INVALID;
   {      // (pass_vjp_pwl's conditions, asked before anything is launched; grad == NULL: the terms' values alone)
     const CnfConfig& g = m->cfg;
@@ -2072,9 +1965,7 @@ extern "C" int cnf_score_residual(const float* r, const float* score, int64_t n,
                                   float* sbar, void* stream_) {
   if (!r || !score || !sums || n < 0 || count < 1 || D < 1 || !(dt > 0.f) || (rbar == nullptr) != (sbar == nullptr))
     return CNF_ERR_INVALID;
-  if (drift > CNF_DRIFT_LORENZ) return CNF_ERR_INVALID;
-  if ((drift == CNF_DRIFT_SMILE || drift == CNF_DRIFT_NONGRADIENT) && D != 2) return CNF_ERR_INVALID;
-  if (drift == CNF_DRIFT_LORENZ && D != 3) return CNF_ERR_INVALID;
+  if (drift != -1 && !drift_ok(drift, D)) return CNF_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t n_slices = (n + count - 1) / count;
   if (n_slices == 0) return CNF_OK;
@@ -2092,6 +1983,7 @@ extern "C" int cnf_term_residual(int32_t kind, const float* r, const float* aux,
   if (!r || !sums || n < 0 || count < 1 || D < 1) return CNF_ERR_INVALID;
   if (kind != CNF_TERM_KINETIC && kind != CNF_TERM_POTENTIAL && kind != CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
   if (kind == CNF_TERM_KINETIC && !(p0 > 0.f)) return CNF_ERR_INVALID;
+  if (kind == CNF_TERM_POTENTIAL && !potential_ok(subtype)) return CNF_ERR_INVALID;
   if (kind == CNF_TERM_NEG_LOGPROB && !aux) return CNF_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t n_slices = (n + count - 1) / count;

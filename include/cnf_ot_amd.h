@@ -265,7 +265,12 @@ typedef struct CnfLossSpec {
 /* pts: [n_slices * B, D] when pts_shared == 0 (each slice its own draw, the
  * key-split of utils.py:328), [B, D] when pts_shared != 0 (every slice reuses
  * the same draw: the reused rng of applications.py:392-400).  t: [n_slices].
- * sums: [n_slices] doubles, overwritten. */
+ * sums: [n_slices] doubles, overwritten.  CNF_ERR_INVALID (nothing enqueued) for a spec
+ * the reference does not define: a kind outside CnfTermKind, dt <= 0 (the kinetic
+ * and score terms), dx <= 0 (the score terms), a potential subtype outside
+ * CnfPotential, a drift subtype outside CnfDrift or one for another dimension
+ * (SMILE, NONGRADIENT: dim 2; LORENZ: dim 3), a reverse-KL term with T <= 0 or
+ * beta <= 0. */
 int cnf_loss_terms(CnfModel *m, const CnfLossSpec *spec, const float *pts,
                    int pts_shared, const float *t, int64_t n_slices, int64_t B,
                    double *sums, void *stream);
@@ -291,7 +296,7 @@ int cnf_loss_terms_seeded(CnfModel *m, const CnfLossSpec *spec, uint64_t seed,
  * cnf_grad_enable allocates the per-wave gradient slabs (the only allocation;
  * call once, outside any graph capture; max_blocks <= 0: a default).
  *
- * cnf_loss_terms_grad = cnf_loss_terms (same arguments, same `sums`) PLUS
+ * cnf_loss_terms_grad = cnf_loss_terms (same arguments and spec checks, same `sums`) PLUS
  *   grad[p] += scale * d(sum over all slices and samples of the term)/d params[p]
  * `grad` (device, cnf_param_count() floats) is ACCUMULATED into, so the caller
  * zeroes it once and adds every term of a composite loss with its coefficient
@@ -367,7 +372,7 @@ int cnf_neg_logprob_vjp(CnfModel *m, const float *pts, const float *c,
  * launch in which all slices read the same z (no repeated copy of it), the term epilogues, which also leave the largest
  * adjoint for the backward (no scan), and one backward launch -- what cnf_sample + cnf_term_residual + cnf_pass_vjp do
  * in six launches over 2 (3) S repeated copies of z.  work: 4 x 2 (3) S x count floats, 16-byte aligned (the pushed
- * points and their adjoints).  pot == NULL iff subtype < 0.  grad == NULL: the terms' values alone (the loss without
+ * points and their adjoints).  pot == NULL iff subtype < 0; subtype > 2: CNF_ERR_INVALID.  grad == NULL: the terms' values alone (the loss without
  * jax.value_and_grad; work: 2 x 2 (3) S x count floats).  CNF_ERR_UNSUPPORTED (nothing written) where the table
  * backward does not apply or 2 (3) S > 128: compose the term from those calls. */
 int cnf_kinetic_potential_vjp(CnfModel *m, const float *z, int64_t count,
@@ -419,7 +424,8 @@ int cnf_score_fd_vjp(CnfModel *m, const float *r, const float *c, int64_t count,
  * base -> data launch), score [n, D] from cnf_logprob_fd; per slice of `count`
  * samples  sums[s] = sum_{i,d} ((r2 - r1)/dt + coef score - drift_d(r3))^2
  * (kinetic_with_score_loss_fn / flow_matching_loss_fn, applications.py:245-374;
- * drift = CnfDrift, or -1 for none).  With rbar / sbar non-NULL it also writes
+ * drift = CnfDrift, or -1 for none; anything else, or a drift for another
+ * dimension, is CNF_ERR_INVALID).  With rbar / sbar non-NULL it also writes
  * the adjoints of r and score for d(loss) = loss_coef * d(sum of sums): the
  * seeds of cnf_logprob_fd_vjp and cnf_pass_vjp.
  *
@@ -428,7 +434,8 @@ int cnf_score_fd_vjp(CnfModel *m, const float *r, const float *c, int64_t count,
  * (applications.py:129-163), adjoints ybar / lpbar likewise. */
 /* cnf_term_residual: value and adjoints of the kinetic / potential / density-fit terms composed from separate flow
  * launches (kinetic_loss_fn applications.py:220-242: r = [r1 | r2], 2 n points, p0 = dt; potential_loss_fn :176-205:
- * r = n points, subtype = CnfPotential, p0 = a; kl_loss_fn :11-86: r = the recovered base points, aux = ildj).
+ * r = n points, subtype = CnfPotential (else CNF_ERR_INVALID), p0 = a; kl_loss_fn :11-86: r = the recovered base
+ * points, aux = ildj).
  * sums [ceil(n / count)] per slice; rbar (and auxbar for the density fit) receive loss_coef * d(sum) / d(.) when
  * non-NULL. */
 int cnf_term_residual(int32_t kind, const float *r, const float *aux, int64_t n,

@@ -942,3 +942,55 @@ def test_input_adjoints_on_the_linear_tails(dev, to_base):
     print(f"\n[tails to_base={to_base} mode={mode}] tail samples {int(tail.sum())}: worst rel {rel[tail].max():.2e}; "
           f"all: median {np.median(rel):.1e}, beyond 1% {int((rel > 1e-2).sum())}")
     assert rel[tail].max() <= 2e-2 and (rel > 1e-2).sum() <= 5
+
+
+def test_term_specs_outside_the_reference_are_rejected(dev):
+  """The C ABI checks a term spec the same way in every entry point that takes one (cnf_loss_terms and
+  cnf_loss_terms_grad alike): a potential subtype outside 0..2, a drift subtype outside 0..3 (-1..3 where -1 means no
+  drift), a reverse-KL term with T <= 0 or beta <= 0 return CNF_ERR_INVALID, on real device buffers."""
+  from cnf_ot_amd import FlowConfig, FlowEngine, Params, _capi
+  from cnf_ot_amd.flows import _stream_ptr
+  cfg = FlowConfig(dim=2)
+  params = Params.random(cfg, 0.2, seed=5, device=dev)
+  eng = FlowEngine(cfg, dev).load(params)
+  lib, h, st = eng.lib, eng._h, _stream_ptr(dev)
+  assert lib.cnf_grad_enable(h, 0) == _capi.CNF_OK
+  B, inv = 64, _capi.CNF_ERR_INVALID
+  pts = torch.randn(B, 2, device=dev)
+  t = torch.full((1,), 0.5, device=dev)
+  sums = torch.zeros(4, dtype=torch.float64, device=dev)
+  grad = torch.zeros(cfg.param_count(), device=dev)
+  flat = params.flat.contiguous()
+  S = _capi.CnfLossSpec
+  bad = [S(kind=_capi.TERM_POTENTIAL, subtype=3, a=1.0),
+         S(kind=_capi.TERM_FLOW_MATCHING, subtype=4, dt=0.01, dx=0.01, coef=1.0, a=1.0),
+         S(kind=_capi.TERM_REVERSE_KL, T=0.0, beta=1.0),
+         S(kind=_capi.TERM_REVERSE_KL, T=1.0, beta=0.0)]
+  for spec in bad:
+    assert lib.cnf_loss_terms(h, _capi.ctypes.byref(spec), pts.data_ptr(), 0, t.data_ptr(), 1, B, sums.data_ptr(),
+                              st) == inv, (spec.kind, spec.subtype)
+    assert lib.cnf_loss_terms_grad(h, _capi.ctypes.byref(spec), pts.data_ptr(), 0, t.data_ptr(), 1, B, 1.0,
+                                   sums.data_ptr(), grad.data_ptr(), flat.data_ptr(), st) == inv, (spec.kind, spec.subtype)
+  # several terms: every spec is checked before the first term's sums are touched
+  ct = _capi.ctypes
+  two = (S * 2)(S(kind=_capi.TERM_KINETIC, dt=0.01), bad[0])
+  sums2 = torch.full((2,), 7.0, dtype=torch.float64, device=dev)
+  P2 = ct.c_void_p * 2
+  assert lib.cnf_loss_terms_grad_multi(h, 2, two, P2(pts.data_ptr(), pts.data_ptr()), (ct.c_int32 * 2)(0, 0),
+                                       P2(t.data_ptr(), t.data_ptr()), (ct.c_int64 * 2)(1, 1), (ct.c_int64 * 2)(B, B),
+                                       (ct.c_float * 2)(1.0, 1.0), P2(sums2.data_ptr(), sums2[1:].data_ptr()),
+                                       grad.data_ptr(), flat.data_ptr(), st) == inv
+  out = torch.zeros(B, 2, device=dev)
+  assert lib.cnf_term_residual(_capi.TERM_POTENTIAL, pts.data_ptr(), None, B, B, 2, 3, 1.0, 1.0, sums.data_ptr(),
+                               out.data_ptr(), None, st) == inv
+  c = torch.tensor([0.45, 0.55, 0.5], device=dev)
+  work = torch.zeros(16 * B, device=dev)
+  assert lib.cnf_kinetic_potential_vjp(h, pts.data_ptr(), B, c.data_ptr(), 1, 0.1, 1.0, 3, 1.0, 1.0, sums.data_ptr(),
+                                       sums[1:].data_ptr(), None, None, work.data_ptr(), st) == inv
+  r = torch.randn(3 * B, 2, device=dev)
+  score, rbar, sbar = torch.zeros(B, 2, device=dev), torch.zeros(3 * B, 2, device=dev), torch.zeros(B, 2, device=dev)
+  assert lib.cnf_score_residual(r.data_ptr(), score.data_ptr(), B, B, 2, 0.01, 1.0, -2, 1.0, 1.0, sums.data_ptr(),
+                                rbar.data_ptr(), sbar.data_ptr(), st) == inv
+  torch.cuda.synchronize()
+  assert not sums.any() and not grad.any() and not out.any() and not work.any() and not rbar.any()
+  assert (sums2 == 7.0).all()
