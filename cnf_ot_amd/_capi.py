@@ -38,6 +38,7 @@ class CnfLossSpec(ctypes.Structure):
 
 
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
+TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
 DRIFTS = {"ou": 0, "gradient": 1, "smile": 1, "nongradient": 2, "lorenz": 3}
 

@@ -20,6 +20,7 @@ per-slice batches; the obstacle potential is summed, not averaged, over slices
 (applications.py:397-400); RWPO/FP kinetic scaled by T / t_batch_size;
 flow_matching overrides dt = dx = 0.01 (:286,301); fp beta = 4 (:432).
 """
+import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -607,6 +608,88 @@ def flow_matching_loss_fn(model, dim, a, sigma, subtype, dt, dx, params, cond, r
   ctx = _Ctx(model, params, rng, shard, grad)
   c = 0.5 / batch_size
   return ctx.reduce([_flow_matching_sum(ctx, dim, a, sigma, subtype, [float(cond)], batch_size, c)])[0] * c
+
+
+# ---- post-training evaluation (cnf_ot/mfc/solvers.py:129-308) -------------------
+# The density errors are one fused launch each (CNF_TERM_DENSITY_L2 / _DATA: per-slice sums of
+# (exp(log_prob) - p_mix)^2, no [B, D] samples in HBM); the caller takes the root of the mean.
+
+def ou_variance(t, a, var0, sigma=0.5):
+  """Per-dimension variance at time t under the flow-matching dynamics v = -a r - sigma grad log rho, started from
+  variance var0: exp(-2 a t) (var0 - sigma / a) + sigma / a.  At sigma = 1/2 this is the reference's 1/(2a) form
+  (solvers.py:246-252), which hard-codes that value -- and so does the density-error kernel's mixture."""
+  return math.exp(-2.0 * a * t) * (var0 - sigma / a) + sigma / a
+
+
+def density_l2_error_fn(model, dim, T, a, params, cond, rng, batch_size, var0=4.0, shard=None):
+  """rmse_mc_loss_fn (solvers.py:254-279): sqrt(mean (exp(log_prob) - p_mix)^2) over batch_size samples drawn at
+  `cond`, p_mix(y) = (1 - cond) N(y; 0, var0 I) + cond N(y; 0, vT I), vT = ou_variance(T, a, var0).  One
+  cnf_loss_terms_seeded launch (the noise is drawn in the kernel); this rank's block of the samples, one sum
+  all-reduce."""
+  shard = shard if shard is not None else current_shard()
+  be = model.terms_backend(params)
+  start, count = shard_range(batch_size, shard)
+  spec = _spec(_capi.TERM_DENSITY_L2, coef=var0, a=a, T=T)
+  total = all_reduce_sums(be.loss_terms_seeded(spec, rng, [float(cond)], count, first_sample=start), shard)
+  return torch.sqrt(total[0] / batch_size)
+
+
+def density_grid(grid_size, lo, hi, rows, device):
+  """Rows `rows` (a range of y indices) of jnp.meshgrid(linspace(lo, hi, n), linspace(lo, hi, n)) flattened to
+  [len(rows) * n, 2] points (x fastest), as rmse_grid_loss_fn builds them (solvers.py:288-293)."""
+  xs = torch.linspace(lo, hi, grid_size, dtype=torch.float64, device=device)
+  X, Y = torch.meshgrid(xs, xs[rows.start:rows.stop], indexing="xy")
+  return torch.stack([X.reshape(-1), Y.reshape(-1)], 1).to(torch.float32).contiguous()
+
+
+def density_l2_grid_error_fn(model, T, a, params, cond, grid_size=500, lo=-5.0, hi=5.0, var0=4.0, shard=None):
+  """rmse_grid_loss_fn (solvers.py:284-305): the density error of density_l2_error_fn on the grid_size^2 points of
+  [lo, hi]^2.  Dim 2 only, as the reference only calls it there.  The grid is built once on the device, then ONE
+  cnf_loss_terms launch (CNF_TERM_DENSITY_L2_DATA); a rank takes its block of grid rows."""
+  if model.cfg.dim != 2:
+    raise ValueError(f"density_l2_grid_error_fn: the grid error is defined at dim 2 only, not {model.cfg.dim}")
+  shard = shard if shard is not None else current_shard()
+  be = model.terms_backend(params)
+  start, rows = shard_range(grid_size, shard)
+  pts = density_grid(grid_size, lo, hi, range(start, start + rows), be.device)
+  spec = _spec(_capi.TERM_DENSITY_L2_DATA, coef=var0, a=a, T=T)
+  total = all_reduce_sums(be.loss_terms(spec, pts, [float(cond)], pts.shape[0], True), shard)
+  return torch.sqrt(total[0] / (grid_size * grid_size))
+
+
+def cost_rwpo_terms(x, y, beta, a):
+  """The double-well cost_rwpo of solvers.py:190-220 from its draws, scaled: x [nx, 2], y [nx, ny, 2] (float64)."""
+  nx, ny = y.shape[0], y.shape[1]
+  r = y.reshape(-1, 2)
+  v = (torch.linalg.norm(r - a, dim=1) * torch.linalg.norm(r + a, dim=1) / 2) ** 2
+  return (-2.0 / beta * torch.log(torch.exp(v.reshape(nx, ny) * (-beta / 2)).mean(1))).mean()
+
+
+def rwpo_true_value(dim, T, beta, a, subtype, rng=None):
+  """The reference value of the rwpo energy (solvers.py:164-235).  quadratic: the closed form dim (1 + log(T + 1)) /
+  beta (:170-172, quadratic potential and Gaussian initial condition).  double_well: cost_rwpo(rng, 100, 1000)
+  (:190-220, 232), dim 2 only as in the reference: x ~ N(0, 2/beta (T+1) I) [100], y = x + N(0, 2/beta T I)
+  [100 x 1000], both from the cnf_fill_normal stream of `rng` (x: samples 0-99, y: the next 100 000), in float64 on
+  the device.  obstacle: None (the reference has no value: it raises NameError at :234-235)."""
+  if subtype == "quadratic":
+    return dim * (1.0 + math.log(T + 1.0)) / beta
+  if subtype == "obstacle":
+    return None
+  if subtype != "double_well":
+    raise ValueError(f"unknown potential {subtype!r}")
+  if dim != 2:
+    raise ValueError(f"rwpo_true_value: cost_rwpo is defined at dim 2 only, not {dim}")
+  seed, off = seed_to_u64(0 if rng is None else rng)
+  nx, ny = 100, 1000
+  dev = torch.device("cuda", torch.cuda.current_device())
+  z = torch.empty(nx * (1 + ny) * 2, dtype=torch.float32, device=dev)
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_fill_normal(seed, off * 2, z.numel(), z.data_ptr(), _stream_ptr(dev)),
+                "cnf_fill_normal")
+  z = z.double()
+  x = z[:nx * 2].reshape(nx, 2) * math.sqrt(2.0 / beta * (T + 1))
+  y = z[nx * 2:].reshape(nx, ny, 2) * math.sqrt(2.0 / beta * T) + x.reshape(nx, 1, 2)
+  return float(cost_rwpo_terms(x, y, beta, a))
 
 
 # ---- composite losses ---------------------------------------------------------

@@ -170,15 +170,23 @@ static inline bool drift_ok(int subtype, int D) {
   if (subtype == CNF_DRIFT_LORENZ) return D == 3;
   return subtype == CNF_DRIFT_OU;
 }
-// CNF_OK or CNF_ERR_INVALID: the checks of cnf_loss_terms and cnf_loss_terms_grad
+// CNF_OK or CNF_ERR_INVALID: the checks of cnf_loss_terms (term_grad_spec_check adds those of the gradient entries)
 static inline int term_spec_check(const CnfLossSpec* spec, int D) {
-  if (!spec || spec->kind < CNF_TERM_KINETIC || spec->kind > CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
+  if (!spec || spec->kind < CNF_TERM_KINETIC || spec->kind > CNF_TERM_DENSITY_L2_DATA) return CNF_ERR_INVALID;
   if (spec->kind <= CNF_TERM_FLOW_MATCHING && !(spec->dt > 0.f)) return CNF_ERR_INVALID;
   if ((spec->kind == CNF_TERM_KINETIC_SCORE || spec->kind == CNF_TERM_FLOW_MATCHING) && !(spec->dx > 0.f))
     return CNF_ERR_INVALID;
   if (spec->kind == CNF_TERM_FLOW_MATCHING && !drift_ok(spec->subtype, D)) return CNF_ERR_INVALID;
   if (spec->kind == CNF_TERM_POTENTIAL && !potential_ok(spec->subtype)) return CNF_ERR_INVALID;
   if (spec->kind == CNF_TERM_REVERSE_KL && (!(spec->T > 0.f) || !(spec->beta > 0.f))) return CNF_ERR_INVALID;
+  if ((spec->kind == CNF_TERM_DENSITY_L2 || spec->kind == CNF_TERM_DENSITY_L2_DATA) &&
+      (!(spec->coef > 0.f) || !(spec->a > 0.f) || !(spec->T > 0.f)))
+    return CNF_ERR_INVALID;
+  return CNF_OK;
+}
+// the checks of cnf_loss_terms_grad(_multi): the density-error terms are evaluation terms and have no backward
+static inline int term_grad_spec_check(const CnfLossSpec* spec, int D) {
+  if (term_spec_check(spec, D) != CNF_OK || spec->kind > CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;
   return CNF_OK;
 }
 

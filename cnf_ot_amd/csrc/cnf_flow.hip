@@ -867,7 +867,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
 struct LossArgs {
   ModelArgs m;
   CnfLossSpec spec;
-  const float* pts;     // base noise (or data points for NEG_LOGPROB)
+  const float* pts;     // base noise (or data points for NEG_LOGPROB, DENSITY_L2_DATA)
   const float* t;       // [n_slices]
   double* sums;         // [n_slices]
   int64_t B;            // samples per slice
@@ -878,6 +878,7 @@ struct LossArgs {
   // fill_normal_kernel): sample i of slice s is stream sample first_sample + s * pts_slice_stride + i
   uint64_t seed;
   int64_t first_sample;
+  DensityMix mix;       // the density-error terms' mixture (density_mix_consts)
 };
 
 template <class T>
@@ -931,7 +932,8 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
     T acc = splat<T>(0.0f);
     const float dt = a.spec.dt;
     const bool kin = kind <= CNF_TERM_FLOW_MATCHING;
-    const int n_fwd = kind == CNF_TERM_NEG_LOGPROB ? 0 : (kind == CNF_TERM_KINETIC ? 2 : (kin ? 3 : 1));
+    const bool data = kind == CNF_TERM_NEG_LOGPROB || kind == CNF_TERM_DENSITY_L2_DATA;    // points are data
+    const int n_fwd = data ? 0 : (kind == CNF_TERM_KINETIC ? 2 : (kin ? 3 : 1));
     T fldj = splat<T>(0.0f);
     for (int p = 0; p < n_fwd; ++p) {
       const float c = !kin ? t : (p == 0 ? t - 0.5f * dt : (p == 1 ? t + 0.5f * dt : t));
@@ -953,10 +955,13 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
     } else if (kind == CNF_TERM_REVERSE_KL) {
       const T lp = base_logprob<T>(lds_col<T>(Nn + col, TS), D) - fldj;
       acc = lp - rkl_mixture<FAST, T>(lds_col<T>(U + col, TS), D, t, a.spec.T, a.spec.beta).logmix;
+    } else if (kind == CNF_TERM_DENSITY_L2) {
+      const T lp = base_logprob<T>(lds_col<T>(Nn + col, TS), D) - fldj;
+      acc = density_l2_residual<FAST, T>(lp, density_mixture<FAST, T>(lds_col<T>(U + col, TS), D, t, a.mix));
     }
-    // data->base passes: NEG_LOGPROB (one, on the points themselves) or the
+    // data->base passes: NEG_LOGPROB / DENSITY_L2_DATA (one, on the points themselves) or the
     // central differences of log_prob at r3 +- dx/2 e_d (applications.py:264-273)
-    const bool neg = kind == CNF_TERM_NEG_LOGPROB;
+    const bool neg = data;
     const int n_tb = neg ? 1 : ((kind == CNF_TERM_KINETIC_SCORE || kind == CNF_TERM_FLOW_MATCHING) ? 2 * D : 0);
     const float dx = a.spec.dx;
     T lp0 = splat<T>(0.0f);
@@ -964,9 +969,13 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
       const int d = e >> 1, sgn = e & 1;
       copy_cols<T>(U + col, (neg ? Nn : R) + col, D, TS);
       if (!neg) lds_put(U + col, d, TS, lds_get<T>(R + col, d, TS) + (sgn == 0 ? 0.5f * dx : -0.5f * dx));
+      // (the mixture at the data point waits in the unused velocity column: nothing more is live across the pass)
+      if (kind == CNF_TERM_DENSITY_L2_DATA)
+        lds_put(V + col, 0, TS, density_mixture<FAST, T>(lds_col<T>(Nn + col, TS), D, t, a.mix));
       const T ildj = flow_pass<H, K, true, FAST, T>(a.m, tab, U, O, splat<T>(t));
       const T lp = base_logprob<T>(lds_col<T>(U + col, TS), D) + ildj;
-      if (neg) acc = -lp;
+      if (kind == CNF_TERM_DENSITY_L2_DATA) acc = density_l2_residual<FAST, T>(lp, lds_get<T>(V + col, 0, TS));
+      else if (neg) acc = -lp;
       else if (sgn == 0) lp0 = lp;
       else {
         const T dr = drift_field<T>(lds_col<T>(R + col, TS), d, kind == CNF_TERM_FLOW_MATCHING ? a.spec.subtype : -1, a.spec.a);
@@ -1002,6 +1011,7 @@ struct LossPwlArgs {
   uint64_t seed;
   int64_t first_sample;
   int32_t n_sets, tiles_per_slice;
+  DensityMix mix;             // the density-error terms' mixture (density_mix_consts)
 };
 
 template <int K, bool FAST>
@@ -1068,7 +1078,8 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
     auto n = [&](int q) { return q == 0 ? n0 : n1; };
 
     T acc = splat<T>(0.0f);
-    const int n_fwd = kind == CNF_TERM_NEG_LOGPROB ? 0 : (kind == CNF_TERM_KINETIC ? 2 : (kin ? 3 : 1));
+    const bool data = kind == CNF_TERM_NEG_LOGPROB || kind == CNF_TERM_DENSITY_L2_DATA;    // points are data
+    const int n_fwd = data ? 0 : (kind == CNF_TERM_KINETIC ? 2 : (kin ? 3 : 1));
     T fldj = splat<T>(0.0f);
     T y0 = n0, y1 = n1, va = splat<T>(0.0f), vb = splat<T>(0.0f);     // (va, vb): r1, then the velocity
     auto y = [&](int q) { return q == 0 ? y0 : y1; };
@@ -1087,10 +1098,13 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
       acc = potential<FAST, T>(y, 2, a.spec.subtype, a.spec.a).v;
     } else if (kind == CNF_TERM_REVERSE_KL) {
       acc = base_logprob<T>(n, 2) - fldj - rkl_mixture<FAST, T>(y, 2, t, a.spec.T, a.spec.beta).logmix;
+    } else if (kind == CNF_TERM_DENSITY_L2) {
+      acc = density_l2_residual<FAST, T>(base_logprob<T>(n, 2) - fldj,
+                                         density_mixture<FAST, T>(y, 2, t, a.mix));
     }
-    // data->base passes: NEG_LOGPROB (one, on the points themselves) or the central differences of
+    // data->base passes: NEG_LOGPROB / DENSITY_L2_DATA (one, on the points themselves) or the central differences of
     // log_prob at r3 +- dx/2 e_d (applications.py:264-273); r3 = (y0, y1) of the pass at condition t
-    const bool neg = kind == CNF_TERM_NEG_LOGPROB;
+    const bool neg = data;
     const int n_tb = neg ? 1 : ((kind == CNF_TERM_KINETIC_SCORE || kind == CNF_TERM_FLOW_MATCHING) ? 4 : 0);
     if (kind == CNF_TERM_FLOW_MATCHING) { lds_put(R + col, 0, TS, y0); lds_put(R + col, 1, TS, y1); }
     T lp0 = splat<T>(0.0f);
@@ -1101,9 +1115,12 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
         const float h = sgn == 0 ? 0.5f * dx : -0.5f * dx;
         if (d == 0) u0 = u0 + h; else u1 = u1 + h;
       }
+      // (the mixture at the data point waits in the scratch columns: nothing more is live across the pass)
+      if (kind == CNF_TERM_DENSITY_L2_DATA) lds_put(R + col, 0, TS, density_mixture<FAST, T>(n, 2, t, a.mix));
       const T ildj = flow2_tables<K, true, FAST, false, true>(tab, tbl + tset * L * PWL_LTBL, gslice + tset * set_stride, L, sc, u0, u1);
       const T lp = base_logprob<T>([&](int q) { return q == 0 ? u0 : u1; }, 2) + ildj;
-      if (neg) acc = -lp;
+      if (kind == CNF_TERM_DENSITY_L2_DATA) acc = density_l2_residual<FAST, T>(lp, lds_get<T>(R + col, 0, TS));
+      else if (neg) acc = -lp;
       else if (sgn == 0) lp0 = lp;
       else {
         const T dr = drift_field<T>(lds_col<T>(R + col, TS), d, kind == CNF_TERM_FLOW_MATCHING ? a.spec.subtype : -1, a.spec.a);
@@ -2036,6 +2053,7 @@ static int loss_terms_pwl(CnfModel* m, const CnfLossSpec* spec, const float* pts
     a.B = B; a.n_slices = ns; a.pts_slice_stride = slice_stride;
     a.seed = seed; a.first_sample = first_sample + s0 * slice_stride;
     a.n_sets = n_sets; a.tiles_per_slice = (int32_t)tps;
+    a.mix = cnf::density_mix_consts(*spec, 2);
     const int64_t tiles = ns * tps;
     const int64_t grid = tiles < m->num_cus ? tiles : m->num_cus;
     hipLaunchKernelGGL((cnf::loss_pwl_kernel<5, true>), dim3((unsigned)grid), dim3(threads), lds, stream, a);
@@ -2066,6 +2084,7 @@ static int loss_terms_impl(CnfModel* m, const CnfLossSpec* spec, const float* pt
   a.m = model_args(m); a.spec = *spec; a.pts = pts; a.t = t; a.sums = sums;
   a.B = B; a.n_slices = n_slices; a.pts_slice_stride = slice_stride;
   a.div_magic = m->div_magic; a.seed = seed; a.first_sample = first_sample;
+  a.mix = density_mix_consts(*spec, D);
   // five D x TS buffers: keep a workgroup under ~64 KB of LDS
   int spl = (m->fast_math && n_slices * B >= (int64_t)m->num_cus * 4 * 64 * 2) ? 2 : 1;
   if (m->force_spl == 1 || m->force_spl == 2) spl = m->fast_math ? m->force_spl : 1;
@@ -2097,7 +2116,8 @@ extern "C" int cnf_loss_terms(CnfModel* m, const CnfLossSpec* spec, const float*
 extern "C" int cnf_loss_terms_seeded(CnfModel* m, const CnfLossSpec* spec, uint64_t seed, int64_t first_sample,
                                      int64_t slice_stride, const float* t, int64_t n_slices, int64_t B,
                                      double* sums, void* stream) {
-  if (spec && spec->kind == CNF_TERM_NEG_LOGPROB) return CNF_ERR_INVALID;   // that term takes data points
+  if (spec && (spec->kind == CNF_TERM_NEG_LOGPROB || spec->kind == CNF_TERM_DENSITY_L2_DATA))
+    return CNF_ERR_INVALID;                                                  // those terms take data points
   return loss_terms_impl(m, spec, nullptr, slice_stride, seed, first_sample, t, n_slices, B, sums, stream);
 }
 

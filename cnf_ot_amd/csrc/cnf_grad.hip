@@ -1568,7 +1568,7 @@ extern "C" int cnf_loss_terms_grad_multi(CnfModel* m, int32_t n_terms, const Cnf
   a.m = model_args(m); a.slabs = m->grad_slabs; a.n_params = m->n_params; a.div_magic = m->div_magic;
   a.n_jobs = 0; a.n_tiles = 0;
   for (int i = 0; i < n_terms; ++i)      // (every term is checked before anything is enqueued)
-    if (term_spec_check(specs + i, D) != CNF_OK || !pts[i] || !t[i] || !sums[i] || n_slices[i] < 0 || B[i] < 0)
+    if (term_grad_spec_check(specs + i, D) != CNF_OK || !pts[i] || !t[i] || !sums[i] || n_slices[i] < 0 || B[i] < 0)
       return CNF_ERR_INVALID;
   for (int i = 0; i < n_terms; ++i) {
     if (n_slices[i] == 0) continue;

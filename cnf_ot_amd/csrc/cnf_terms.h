@@ -103,6 +103,35 @@ __device__ __forceinline__ RklMix<T> rkl_mixture(X y, int D, float t, float Tt, 
   return RklMix<T>{mx + M::log(es + et), (es / vs + et / vt) / (es + et)};
 }
 
+// The density-error target of rmse_mc_loss_fn / rmse_grid_loss_fn (solvers.py:239-305) at condition t:
+// p_mix(y; t) = (1 - t) N(y; 0, v0 I) + t N(y; 0, vT I), vT = exp(-2 a T) (v0 - 1/(2a)) + 1/(2a).  Linear space, not a
+// log-sum-exp: the weights 1 - t and t are taken literally and may be <= 0 outside [0, 1].  The constants of the two
+// Gaussians are made on the host and reach the kernels as arguments: computed in a kernel, the loop-invariant
+// logarithms and exponential were hoisted into vector registers held across the flow passes of every term.
+struct DensityMix { float e0, l0, eT, lT; };    // exponent factors -1/(2 v) and log-normalisations -D/2 log(2 pi v)
+
+static inline DensityMix density_mix_consts(const CnfLossSpec& s, int D) {
+  const double v0 = s.coef, h = 0.5 / s.a, vT = exp(-2.0 * s.a * s.T) * (v0 - h) + h;
+  return DensityMix{(float)(-0.5 / v0), (float)(-0.5 * D * log(2.0 * M_PI * v0)), (float)(-0.5 / vT),
+                    (float)(-0.5 * D * log(2.0 * M_PI * vT))};
+}
+
+template <bool FAST, class T, class X>
+__device__ __forceinline__ T density_mixture(X y, int D, float t, const DensityMix& c) {
+  using M = Math<FAST>;
+  const T s2 = sq_norm<T>(y, D);
+  const T p0 = M::exp(vfma(s2, splat<T>(c.e0), splat<T>(c.l0)));
+  const T pT = M::exp(vfma(s2, splat<T>(c.eT), splat<T>(c.lT)));
+  return p0 * (1.0f - t) + pT * t;
+}
+
+// The density-error residual (exp(lp) - p_mix)^2 of one sample, lp the flow's log-density at the point
+template <bool FAST, class T>
+__device__ __forceinline__ T density_l2_residual(T lp, T pmix) {
+  const T d = Math<FAST>::exp(lp) - pmix;
+  return d * d;
+}
+
 // The OU drift -a r (applications.py:310) is diagonal: coordinate e's drift and adjoint need nothing but coordinate e
 template <class T> __device__ __forceinline__ T ou_drift(T r, float a) { return r * -a; }
 __device__ __forceinline__ float ou_drift_adjoint(float ub, float a) { return a * ub; }

@@ -1,17 +1,23 @@
-"""Mirror of the training step of cnf_ot/mfc/solvers.py (the caller of the hot
-path): config keys of config/mfc.yaml, model construction (:41-56), the loss
-binding (:58-88), and `update` = value_and_grad + Adam (:90-97), on the HIP
-kernels.  Plotting / printing / post-training evaluation of the reference
-(:129-493) are out of scope; the two evaluators are
-in cnf_ot_amd.utils.
+"""Mirror of cnf_ot/mfc/solvers.py (the caller of the hot path): config keys of
+config/mfc.yaml, model construction (:41-56), the loss binding (:58-88),
+`update` = value_and_grad + Adam (:90-97), the training loop (:99-127), and the
+post-training evaluation (:129-308: `evaluate`, printed by `main`), on the HIP
+kernels.  Plots (:119-127, 309-493) are out of scope, and so is the double-well
+density-vs-interpolator comparison (:178-188, 222-231), whose data files
+(data/fcn4a*_interp.pkl) are not shipped with the reference.
+
+  python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz]
 """
+import argparse
+import sys
 from dataclasses import dataclass, field
 from functools import partial
-from typing import Any, Callable, Dict, Tuple
+from typing import Any, Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
-from . import _capi, applications
+from . import _capi, applications, utils
 from .flows import DeviceRng, RQSFlow, FlowModel, _OnDevice, _stream_ptr, mark_updated
 from .params import Params
 
@@ -215,3 +221,127 @@ def train(config, epochs: int = None, log=None, capture: bool = False):
     if log is not None and step % config["train"]["eval_frequency"] == 0:
       log(step, float(loss))
   return model, params, hist
+
+
+# ---- post-training evaluation (solvers.py:129-308) ------------------------------
+
+def evaluate(config, model: FlowModel, params: Params, rng) -> Dict[str, Any]:
+  """What solvers.py:129-308 computes after training, without plots, keyed by name.  Every value is a Python float
+  (var_T: a list of floats, one per dimension), or None where the reference has no value.
+    all:  param_count (:128-129)
+    ot:   kinetic_energy_more (65 536 samples x 10 000 slices), kinetic_energy_less (4 096 x 1 000)   (:132-149)
+    rwpo: e_kin = T calc_score_kinetic_energy, e_pot = potential_loss_fn(params, T, rng, 65536), total, true_val
+          (applications.rwpo_true_value), rel_err_pct = (total - true_val) / true_val * 100          (:150-237)
+    fp:   l2_mc: the density L2 error of 1 M samples at cond 1 against the reference's mixture (source variance 4,
+          as it prints it, :238-282); l2_grid: the same on the 500 x 500 grid of [-5, 5]^2 (dim 2 only, :284-307);
+          l2_mc_ic: l2_mc against the mixture of the training's own initial condition N(0, (T+1)/2 I) (fp_loss_fn's
+          reverse KL at beta = 4, applications.py:432: the reference's variance 4 does not match it, so its printed
+          error cannot reach 0); var_T: the per-dimension sample variance of 1 M samples at t = T, and
+          var_T_closed_form = ou_variance(T, a, (T+1)/2, sigma).
+  The double-well density-vs-interpolator comparison (:178-188, 222-231) needs data/fcn4a*_interp.pkl, which the
+  reference does not ship; it is left out (the reference opens that file before cost_rwpo, so without it its whole
+  double-well evaluation fails), and true_val still comes from cost_rwpo."""
+  g = config["general"]
+  _type, dim = g["type"], g["dim"]
+  out: Dict[str, Any] = {"param_count": int(params.flat.numel())}
+  if _type == "ot":
+    out["kinetic_energy_more"] = float(utils.calc_kinetic_energy(model.apply.sample, params, rng, batch_size=65536,
+                                                                 t_size=10000, dim=dim))
+    out["kinetic_energy_less"] = float(utils.calc_kinetic_energy(model.apply.sample, params, rng, batch_size=4096,
+                                                                 t_size=1000, dim=dim))
+  elif _type == "rwpo":
+    r = config["rwpo"]
+    T, beta, a, sub = r["T"], r["beta"], r["a"], r["pot_type"]
+    e_kin = T * float(utils.calc_score_kinetic_energy(model.apply.sample, model.apply.log_prob, params, T, beta, dim,
+                                                      rng))
+    e_pot = float(applications.potential_loss_fn(model, dim, a, sub, params, T, rng, 65536))
+    true_val = applications.rwpo_true_value(dim, T, beta, a, sub, rng) if (sub != "double_well" or dim == 2) else None
+    total = e_kin + e_pot
+    out.update(e_kin=e_kin, e_pot=e_pot, total=total, true_val=true_val,
+               rel_err_pct=None if true_val is None else (total - true_val) / true_val * 100)
+  elif _type == "fp":
+    f = config["fp"]
+    T, a, sigma = f["T"], f["a"], f["sigma"]
+    n = 1000000
+    var_ic = (T + 1.0) / 2.0
+    out["l2_mc"] = float(applications.density_l2_error_fn(model, dim, T, a, params, 1.0, rng, n, var0=4.0))
+    out["l2_grid"] = float(applications.density_l2_grid_error_fn(model, T, a, params, 1.0, 500)) if dim == 2 else None
+    out["l2_mc_ic"] = float(applications.density_l2_error_fn(model, dim, T, a, params, 1.0, rng, n, var0=var_ic))
+    y = model.apply.sample(params, cond=float(T), seed=rng, sample_shape=(n,))
+    out["var_T"] = [float(v) for v in y.double().var(dim=0).cpu()]
+    out["var_T_closed_form"] = applications.ou_variance(T, a, var_ic, sigma)
+  else:
+    raise Exception(f"Unknown problem type: {_type}...")        # solvers.py:87-88
+  return out
+
+
+_SOLVING = {"rwpo": "Solving regularized Wasserstein proximal in {dim}D with lambda{lam}...",
+            "fp": "Solving Fokker-Planck equation in {dim}D with lambda{lam}...",
+            "ot": "Solving optimal transport in {dim}D with lambda{lam}..."}
+
+
+def _eval_rng(seed, step):
+  """eval_rng, rng = jax.random.split(rng) (solvers.py:110,131): a key of its own, apart from the training steps'."""
+  return ((int(seed) ^ 0x5DEECE66DA3B9F1B) + 0x9E3779B97F4A7C15 * (step + 1)) & 0xFFFFFFFFFFFFFFFF
+
+
+def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None) -> Dict[str, Any]:
+  """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
+  `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116)."""
+  g, tr = config["general"], config["train"]
+  _type, dim, seed = g["type"], g["dim"], g["seed"]
+  if _type not in _SOLVING:
+    raise Exception(f"Unknown problem type: {_type}...")
+  print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
+
+  def log(step, loss):
+    desc = f"step {step}: loss={loss:.4e}"
+    if _type == "ot":
+      # train() hands its callback (step, loss) only; the model and the parameters it is training are its locals
+      # (the parameters are updated in place, so they are the current ones)
+      f = sys._getframe(1).f_locals
+      KL = float(applications.density_fit_kl_loss_fn(f["model"], dim, 1, f["params"], _eval_rng(seed, step),
+                                                      tr["batch_size"]))
+      desc += f"KL={KL:.4f}"
+    print(desc, flush=True)
+
+  model, params, hist = train(config, epochs=epochs, log=log, capture=capture)
+  if hist:
+    print(f"loss={float(hist[-1]):.4e}")
+  if save:
+    np.savez(save, params=params.flat.detach().cpu().numpy())
+  res = evaluate(config, model, params, _eval_rng(seed, -1))
+  print("Network parameters: {}".format(res["param_count"]))
+  if _type == "ot":
+    print("kinetic energy with more samples: {:.3e}".format(res["kinetic_energy_more"]))
+    print("kinetic energy with less samples: {:.3e}".format(res["kinetic_energy_less"]))
+  elif _type == "rwpo":
+    print(f"kinetic energy: {res['e_kin']:.3e}")
+    print(f"potential energy: {res['e_pot']:.3e}")
+    if res["true_val"] is None:
+      print(f"total energy: {res['total']:.3e}|relative err: n/a (no reference value for this potential)")
+    else:
+      print("total energy: {:.3e}|relative err: {:.3e}".format(res["total"], res["rel_err_pct"]))
+  else:
+    print("L2 error via Monte-Carlo: {:.3e}".format(res["l2_mc"]))
+    if res["l2_grid"] is not None:
+      print("L2 error on grid: {:.3e}".format(res["l2_grid"]))
+    print("L2 error via Monte-Carlo against the initial condition N(0, (T+1)/2 I): {:.3e}".format(res["l2_mc_ic"]))
+    print("variance at T: {} | closed form: {:.4f}".format(" ".join(f"{v:.4f}" for v in res["var_T"]),
+                                                          res["var_T_closed_form"]))
+  return res
+
+
+def _parse(argv):
+  p = argparse.ArgumentParser(prog="python -m cnf_ot_amd.solvers",
+                              description="Train a cnf_ot configuration on the HIP engine and print its evaluation.")
+  p.add_argument("--config", default=None, help="config file (mfc.yaml layout); default: the checked-in defaults")
+  p.add_argument("--epochs", type=int, default=None, help="training steps (default: train.epochs)")
+  p.add_argument("--capture", action="store_true", help="replay each training step as one captured HIP graph")
+  p.add_argument("--save", default=None, help="write the trained flat parameters to this .npz file")
+  return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+  args = _parse(sys.argv[1:])
+  main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save)

@@ -245,7 +245,20 @@ enum CnfTermKind {
   CNF_TERM_REVERSE_KL = 4,
   /* kl_loss_fn, applications.py:11-86 (after the host mixed the samples):
    * sum_i -log_prob(value_i; t); pts are DATA points, not base noise */
-  CNF_TERM_NEG_LOGPROB = 5
+  CNF_TERM_NEG_LOGPROB = 5,
+  /* rmse_mc_loss_fn, solvers.py:239-279 (the fp evaluation; the caller takes
+   * sqrt(sum / n)): one base -> data pass at t, as REVERSE_KL, giving y_i and
+   * lp_i; sum_i (exp(lp_i) - p_mix(y_i; t))^2 with the mixture in linear space
+   *   p_mix(y; t) = (1 - t) N(y; 0, v0 I) + t N(y; 0, vT I),
+   *   vT = exp(-2 a T) (v0 - 1/(2a)) + 1/(2a),  v0 = coef
+   * (the reference hard-codes v0 = 4; its weights are 1 - cond and cond, t is
+   * not divided by T, and may lie outside [0, 1]).  An evaluation term: no
+   * gradient entry accepts it. */
+  CNF_TERM_DENSITY_L2 = 6,
+  /* rmse_grid_loss_fn, solvers.py:284-305: the same residual at DATA points
+   * (pts as for NEG_LOGPROB; one data -> base pass gives log_prob at the point
+   * itself): sum_i (exp(log_prob(pts_i; t)) - p_mix(pts_i; t))^2.  No gradient. */
+  CNF_TERM_DENSITY_L2_DATA = 7
 };
 enum CnfPotential { CNF_POT_QUADRATIC = 0, CNF_POT_DOUBLE_WELL = 1, CNF_POT_OBSTACLE = 2 };
 /* drift of flow_matching_loss_fn: OU = -a r (applications.py:310, README);
@@ -257,9 +270,10 @@ typedef struct CnfLossSpec {
   int32_t kind;      /* CnfTermKind                                         */
   int32_t subtype;   /* CnfPotential or CnfDrift                            */
   float dt, dx;      /* finite-difference steps (general.dt / general.dx)   */
-  float coef;        /* 1/beta (KINETIC_SCORE) or sigma (FLOW_MATCHING)     */
+  float coef;        /* 1/beta (KINETIC_SCORE), sigma (FLOW_MATCHING) or the
+                        source variance v0 (DENSITY_L2, DENSITY_L2_DATA)    */
   float a;           /* potential / drift parameter (rwpo.a, fp.a)          */
-  float T, beta;     /* REVERSE_KL                                          */
+  float T, beta;     /* REVERSE_KL; T also the horizon of the DENSITY_L2s   */
 } CnfLossSpec;
 
 /* pts: [n_slices * B, D] when pts_shared == 0 (each slice its own draw, the
@@ -270,7 +284,8 @@ typedef struct CnfLossSpec {
  * and score terms), dx <= 0 (the score terms), a potential subtype outside
  * CnfPotential, a drift subtype outside CnfDrift or one for another dimension
  * (SMILE, NONGRADIENT: dim 2; LORENZ: dim 3), a reverse-KL term with T <= 0 or
- * beta <= 0. */
+ * beta <= 0, a density-error term (DENSITY_L2, DENSITY_L2_DATA) with coef <= 0,
+ * a <= 0 or T <= 0. */
 int cnf_loss_terms(CnfModel *m, const CnfLossSpec *spec, const float *pts,
                    int pts_shared, const float *t, int64_t n_slices, int64_t B,
                    double *sums, void *stream);
@@ -280,7 +295,8 @@ int cnf_loss_terms(CnfModel *m, const CnfLossSpec *spec, const float *pts,
  * + i) of the cnf_fill_normal stream of `seed`.  slice_stride = 0: every slice
  * reuses the same draw (applications.py:392-400); slice_stride = batch size:
  * each slice its own draw (the key split of utils.py:328).  Not for
- * CNF_TERM_NEG_LOGPROB (whose points are data). */
+ * CNF_TERM_NEG_LOGPROB or CNF_TERM_DENSITY_L2_DATA (whose points are data):
+ * CNF_ERR_INVALID. */
 int cnf_loss_terms_seeded(CnfModel *m, const CnfLossSpec *spec, uint64_t seed,
                           int64_t first_sample, int64_t slice_stride,
                           const float *t, int64_t n_slices, int64_t B,
@@ -296,7 +312,9 @@ int cnf_loss_terms_seeded(CnfModel *m, const CnfLossSpec *spec, uint64_t seed,
  * cnf_grad_enable allocates the per-wave gradient slabs (the only allocation;
  * call once, outside any graph capture; max_blocks <= 0: a default).
  *
- * cnf_loss_terms_grad = cnf_loss_terms (same arguments and spec checks, same `sums`) PLUS
+ * cnf_loss_terms_grad = cnf_loss_terms (same arguments and spec checks, same `sums`; the evaluation terms
+ * CNF_TERM_DENSITY_L2 and CNF_TERM_DENSITY_L2_DATA have no backward: CNF_ERR_INVALID, nothing enqueued, here and in
+ * cnf_loss_terms_grad_multi and cnf_term_residual) PLUS
  *   grad[p] += scale * d(sum over all slices and samples of the term)/d params[p]
  * `grad` (device, cnf_param_count() floats) is ACCUMULATED into, so the caller
  * zeroes it once and adds every term of a composite loss with its coefficient
