@@ -100,6 +100,10 @@ SYMBOLS = {
   "cnf_adam_step_dev": (ctypes.c_int, [_P, _P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_float, _P, _P]),
   "cnf_weighted_sum": (ctypes.c_int, [_P, _P, _I64, _P, _P]),
+  "cnf_hopf_cole_workspace": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, _I64, _I64,
+                                              ctypes.POINTER(_I64)]),
+  "cnf_hopf_cole_2d": (ctypes.c_int, [ctypes.c_int32, ctypes.c_float] + [ctypes.c_double] * 6
+                       + [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

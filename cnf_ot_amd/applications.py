@@ -692,6 +692,79 @@ def rwpo_true_value(dim, T, beta, a, subtype, rng=None):
   return float(cost_rwpo_terms(x, y, beta, a))
 
 
+# The exact rwpo solution at dim 2 (the reference's offline generator, cnf_ot/mfc/2d_WPO_ref_solution.py:60-187): one
+# cnf_hopf_cole_2d call, float64 separable log-sum-exp passes on the device (include/cnf_ot_amd.h).
+HOPF_COLE_FIELDS = ("score_T", "w0", "wT")
+
+
+def rwpo_initial_variance(T, beta):
+  """The per-dimension variance 2 (T + 1) / beta of the initial condition the rwpo training fits: the source of its
+  reverse-KL term at cond 0 (reverse_kl_loss_fn, applications.py:137-143)."""
+  return 2.0 * (T + 1.0) / beta
+
+
+def rwpo_reference_solution(T, beta, a, subtype, x1, x2=None, var0=None, dz=0.01, window=6.0, y_range=4.0,
+                            fields=HOPF_COLE_FIELDS):
+  """The regularized Wasserstein proximal solution at time T on the tensor grid x1 [n1] x x2 [n2] (x2 = x1 if None),
+  by the generator's Hopf-Cole quadrature with eps = 1/beta, g = the potential `subtype` (a as float32, as the loss
+  spec carries it), rho0 = N(0, var0 I) (default: rwpo_initial_variance(T, beta); the generator hard-codes N(0, I)),
+  a y grid of step dz over [-y_range, y_range]^2 and the z window |z_i - y_i| <= window.  Returns a dict of float64
+  device tensors: log_rho_T [n2, n1] (x1 fastest, meshgrid(x1, x2, indexing="xy")), the requested `fields` among
+  score_T, w0, wT [n2, n1, 2], and the 0-dim true_val (the optimal energy) and ic_mass (sum rho0 dz^2)."""
+  fields = tuple(fields)
+  bad = [f for f in fields if f not in HOPF_COLE_FIELDS]
+  if bad:
+    raise ValueError(f"rwpo_reference_solution: unknown fields {bad} (known: {HOPF_COLE_FIELDS})")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  x1 = torch.as_tensor(x1, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+  x2 = x1 if x2 is None else torch.as_tensor(x2, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+  n1, n2 = x1.numel(), x2.numel()
+  if n1 == 0 or n2 == 0:
+    raise ValueError("rwpo_reference_solution: the output grid is empty")
+  return _hopf_cole(dev, T, beta, a, subtype, var0, dz, window, y_range, x1, x2, fields)
+
+
+def rwpo_true_value_quadrature(dim, T, beta, a, subtype, var0=None, dz=0.01, window=6.0, y_range=4.0):
+  """The optimal rwpo energy -2 eps sum_y rho0(y) (log h(y) - log(4 pi eps T)) dy^2 from the same quadrature as
+  rwpo_reference_solution (deterministic; for the quadratic potential it approaches rwpo_true_value's closed form
+  as the ranges grow).  Dim 2 only."""
+  if dim != 2:
+    raise ValueError(f"rwpo_true_value_quadrature: the quadrature is defined at dim 2 only, not {dim}")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  return float(_hopf_cole(dev, T, beta, a, subtype, var0, dz, window, y_range, None, None, ())["true_val"])
+
+
+def _hopf_cole(dev, T, beta, a, subtype, var0, dz, window, y_range, x1, x2, fields):
+  if subtype not in _capi.POTENTIALS:
+    raise ValueError(f"unknown potential {subtype!r}")
+  var0 = rwpo_initial_variance(T, beta) if var0 is None else var0
+  lib = _capi.lib()
+  n1, n2 = (0, 0) if x1 is None else (x1.numel(), x2.numel())
+  nbytes = _capi.ctypes.c_int64(0)
+  _capi.check(lib.cnf_hopf_cole_workspace(float(dz), float(window), float(y_range), n1, n2, _capi.ctypes.byref(nbytes)),
+              "cnf_hopf_cole_workspace")
+  f64 = dict(dtype=torch.float64, device=dev)
+  ws = torch.empty(-(-nbytes.value // 8), **f64)
+  scalars = torch.empty(2, **f64)
+  out = {}
+  if n1:
+    out["log_rho_T"] = torch.empty(n2, n1, **f64)
+    for f in fields:
+      out[f] = torch.empty(n2, n1, 2, **f64)
+
+  def ptr(name):
+    return out[name].data_ptr() if name in out else None
+
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_hopf_cole_2d(_capi.POTENTIALS[subtype], float(a), float(T), float(beta), float(var0), float(dz),
+                                     float(window), float(y_range), None if x1 is None else x1.data_ptr(), n1,
+                                     None if x2 is None else x2.data_ptr(), n2, ptr("log_rho_T"), ptr("score_T"),
+                                     ptr("w0"), ptr("wT"), scalars.data_ptr(), scalars.data_ptr() + 8, ws.data_ptr(),
+                                     ws.numel() * 8, _stream_ptr(dev)), "cnf_hopf_cole_2d")
+  out["true_val"], out["ic_mass"] = scalars[0], scalars[1]
+  return out
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

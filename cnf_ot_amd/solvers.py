@@ -2,9 +2,10 @@
 config/mfc.yaml, model construction (:41-56), the loss binding (:58-88),
 `update` = value_and_grad + Adam (:90-97), the training loop (:99-127), and the
 post-training evaluation (:129-308: `evaluate`, printed by `main`), on the HIP
-kernels.  Plots (:119-127, 309-493) are out of scope, and so is the double-well
-density-vs-interpolator comparison (:178-188, 222-231), whose data files
-(data/fcn4a*_interp.pkl) are not shipped with the reference.
+kernels.  Plots (:119-127, 309-493) are out of scope.  The double-well
+density-vs-interpolator comparison (:178-188, 222-231) reads data files
+(data/fcn4a*_interp.pkl) that the reference does not ship; here it compares with
+the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz]
 """
@@ -238,9 +239,11 @@ def evaluate(config, model: FlowModel, params: Params, rng) -> Dict[str, Any]:
           reverse KL at beta = 4, applications.py:432: the reference's variance 4 does not match it, so its printed
           error cannot reach 0); var_T: the per-dimension sample variance of 1 M samples at t = T, and
           var_T_closed_form = ou_variance(T, a, (T+1)/2, sigma).
-  The double-well density-vs-interpolator comparison (:178-188, 222-231) needs data/fcn4a*_interp.pkl, which the
-  reference does not ship; it is left out (the reference opens that file before cost_rwpo, so without it its whole
-  double-well evaluation fails), and true_val still comes from cost_rwpo."""
+          At dim 2 (None elsewhere), for every potential, from the exact solution (rwpo_quadrature_terms):
+          true_val_quadrature, rel_err_pct_quadrature, density_sq_err, ic_mass.
+  The reference's double-well density-vs-interpolator comparison (:178-188, 222-231) reads data/fcn4a*_interp.pkl,
+  which it does not ship; density_sq_err computes the interpolated solution's source exactly instead, and true_val
+  still comes from cost_rwpo."""
   g = config["general"]
   _type, dim = g["type"], g["dim"]
   out: Dict[str, Any] = {"param_count": int(params.flat.numel())}
@@ -259,6 +262,8 @@ def evaluate(config, model: FlowModel, params: Params, rng) -> Dict[str, Any]:
     total = e_kin + e_pot
     out.update(e_kin=e_kin, e_pot=e_pot, total=total, true_val=true_val,
                rel_err_pct=None if true_val is None else (total - true_val) / true_val * 100)
+    out.update(rwpo_quadrature_terms(model, params, T, beta, a, sub, total) if dim == 2 else
+               dict.fromkeys(RWPO_QUADRATURE_KEYS))
   elif _type == "fp":
     f = config["fp"]
     T, a, sigma = f["T"], f["a"], f["sigma"]
@@ -273,6 +278,34 @@ def evaluate(config, model: FlowModel, params: Params, rng) -> Dict[str, Any]:
   else:
     raise Exception(f"Unknown problem type: {_type}...")        # solvers.py:87-88
   return out
+
+
+RWPO_QUADRATURE_KEYS = ("true_val_quadrature", "rel_err_pct_quadrature", "density_sq_err", "ic_mass")
+DENSITY_GRID = (-2.0, 2.0, 100)       # the reference's XY grid of the double-well density check (solvers.py:182-188)
+
+
+def density_eval_points(device):
+  """The reference's XY: meshgrid(linspace(-2, 2, 100), same) flattened, x fastest, as the float32 points the flow
+  sees.  Returns (the 1-D coordinates in float64, the [10 000, 2] float32 points)."""
+  lo, hi, n = DENSITY_GRID
+  xs = torch.linspace(lo, hi, n, dtype=torch.float64, device=device).to(torch.float32)
+  X, Y = torch.meshgrid(xs, xs, indexing="xy")
+  return xs.double(), torch.stack([X.reshape(-1), Y.reshape(-1)], 1).contiguous()
+
+
+def rwpo_quadrature_terms(model: FlowModel, params: Params, T, beta, a, subtype, total) -> Dict[str, Any]:
+  """evaluate's rwpo keys from the exact dim-2 solution (applications.rwpo_reference_solution, the reference's
+  generator at its own resolution): true_val_quadrature, rel_err_pct_quadrature = (total - it) / it * 100,
+  ic_mass, and density_sq_err = sum over the reference's 100 x 100 grid of [-2, 2]^2 of
+  (exp(log_prob(XY, cond=T)) - rho_T(XY))^2 -- the statistic solvers.py:222-225 prints, rho_T evaluated exactly at
+  the grid points instead of through the generator's bilinear interpolator."""
+  xs, pts = density_eval_points(params.flat.device)
+  sol = applications.rwpo_reference_solution(T, beta, a, subtype, xs, fields=())
+  lp = model.apply.log_prob(params, pts, cond=float(T))
+  err = float(((torch.exp(lp.double()) - torch.exp(sol["log_rho_T"].reshape(-1))) ** 2).sum())
+  tv = float(sol["true_val"])
+  return {"true_val_quadrature": tv, "rel_err_pct_quadrature": (total - tv) / tv * 100, "density_sq_err": err,
+          "ic_mass": float(sol["ic_mass"])}
 
 
 _SOLVING = {"rwpo": "Solving regularized Wasserstein proximal in {dim}D with lambda{lam}...",
@@ -322,6 +355,10 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
       print(f"total energy: {res['total']:.3e}|relative err: n/a (no reference value for this potential)")
     else:
       print("total energy: {:.3e}|relative err: {:.3e}".format(res["total"], res["rel_err_pct"]))
+    if res["true_val_quadrature"] is not None:
+      print(f"density squared error against the exact solution: {res['density_sq_err']:.3e}")
+      print("total energy: {:.3e}|relative err against the quadrature value {:.6f}: {:.3e}".format(
+        res["total"], res["true_val_quadrature"], res["rel_err_pct_quadrature"]))
   else:
     print("L2 error via Monte-Carlo: {:.3e}".format(res["l2_mc"]))
     if res["l2_grid"] is not None:

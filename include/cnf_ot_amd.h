@@ -499,6 +499,35 @@ int cnf_adam_step_dev(float *params, const float *grad, float *mu, float *nu,
 int cnf_weighted_sum(const double *v, const double *w, int64_t n, double *out,
                      void *stream);
 
+/* ---- the exact 2-D rwpo solution for evaluation (cnf_ot/mfc/2d_WPO_ref_solution.py:60-187, solvers.py:170-232) ----
+ * The regularized Wasserstein proximal problem's solution by the Hopf-Cole kernel formula, as the reference's offline
+ * generator sums it on a uniform grid, with eps = 1 / beta and g = the potential of potential_loss_fn (CnfPotential,
+ * `a` as the loss spec carries it):
+ *   h(y)      = sum_z exp(-(g(z) + |y - z|^2 / (2T)) / (2 eps)) dz^2     over |z_i - y_i| <= window
+ *   rho_T(x)  = sum_y exp(-(g(x) + |x - y|^2 / (2T)) / (2 eps)) rho0(y) / h(y) dz^2
+ *   score_T   = -grad g(x) / (2 eps) - (x - m(x)) / (2 eps T),  m = the rho0 / h weighted mean of y
+ *   w0        = -(x - m0(x)) / T + eps x,  m0 weighted by exp(-g(y) / (2 eps))
+ *   wT        = -grad g - eps score_T
+ *   true_value = -2 eps sum_y rho0(y) (log h(y) - log(4 pi eps T)) dz^2    (the optimal rwpo energy)
+ *   ic_mass    = sum_y rho0(y) dz^2                                        (how much of rho0 the y grid holds)
+ * rho0 = N(0, var0 I).  Grids are index-based: y = k dz for |k| <= n_y = round(y_range / dz), z = k dz for
+ * |k| <= n_y + n_w, n_w = round(window / dz), a z term counted iff its index offset is <= n_w per coordinate.
+ * Outputs (device, float64) on the tensor grid x1 [n1] x x2 [n2], x1 fastest: log_rho [n2, n1] (the log: nothing
+ * underflows); score, w0, wT [n2, n1, 2], each optional (NULL: not computed); true_value, ic_mass: one double each,
+ * optional.  n1 = n2 = 0 (x1, x2, log_rho NULL): the true value and the mass only.  Every sum is a float64
+ * log-sum-exp in a fixed order: no atomics, repeated calls are bit-identical.
+ * cnf_hopf_cole_workspace: the device workspace cnf_hopf_cole_2d needs, in bytes (~8 ((2 n_y + 2 n_w + 1)^2 + ...)).
+ * CNF_ERR_INVALID: T, beta, var0, dz, window or y_range <= 0 or not finite; an unknown potential; n_y, n_w, n1 or
+ * n2 above 2^19; only one of n1, n2 zero; a required pointer NULL; the workspace too small. */
+int cnf_hopf_cole_workspace(double dz, double window, double y_range,
+                            int64_t n1, int64_t n2, int64_t *bytes);
+int cnf_hopf_cole_2d(int32_t subtype, float a, double T, double beta,
+                     double var0, double dz, double window, double y_range,
+                     const double *x1, int64_t n1, const double *x2,
+                     int64_t n2, double *log_rho, double *score, double *w0,
+                     double *wT, double *true_value, double *ic_mass,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
