@@ -56,6 +56,8 @@ SYMBOLS = {
   "cnf_model_reserve": (ctypes.c_int, [_P, _P, _I64]),
   "cnf_model_reserved": (_I64, [_P, _P]),
   "cnf_model_table_bytes": (_I64, [_P]),
+  "cnf_model_has_tables": (ctypes.c_int, [_P]),
+  "cnf_model_term_on_tables": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int]),
   "cnf_model_last_path": (ctypes.c_int, [_P]),
   "cnf_model_set_precise": (ctypes.c_int, [_P, ctypes.c_int]),
   "cnf_forward_logdet": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _P]),

@@ -28,7 +28,7 @@ import torch
 
 from . import _capi
 from .distributed import Shard, all_reduce_sums, current_shard, shard_range
-from .flows import DeviceRng, _OnDevice, _stream_ptr, seed_to_u64
+from .flows import DeviceRng, FlowEngine, _OnDevice, _stream_ptr, seed_to_u64
 
 # Cholesky factor L (lower: A = L L^T, applied as z @ L like oracle/losses.py) of the Gaussian source's covariance A = [[5, 1], [1, .5]]
 # (applications.py:28-32), computed once: torch.linalg.cholesky of a 2 x 2 CPU tensor costs ~20 ms PER CALL on a
@@ -94,16 +94,20 @@ class _Ctx:
 
   def __init__(self, model, params, rng, shard: Optional[Shard], grad: Optional[torch.Tensor] = None):
     self.be = model.terms_backend(params)
+    # the HIP engine, or a stand-in that has `normal`, `loss_terms` and `loss_terms_grad` alone (the CPU tests'): the
+    # one place that asks; every route below that needs more than those three reads this flag
+    self.hip = isinstance(self.be, FlowEngine)
     self.rng = rng
     self.shard = shard if shard is not None else current_shard()
     self.grad = grad
+    if self.hip and grad is not None:
+      self.be.grad_ready(grad)      # (cnf_grad_enable: what `_on_tables` asks about exists from here on)
     self._noise = {}
     self._passes = []       # base -> data backward passes waiting for ONE launch (defer_pass_vjp)
     self._jobs = []         # fused loss terms waiting for ONE launch (cnf_loss_terms_grad_multi)
     self._grad64 = None     # the reduced gradient of the last `reduce`, in float64
     # the terms' per-slice sums land side by side in one buffer: `reduce` needs no concatenation kernel
-    self._sumbuf = torch.empty(256, dtype=torch.float64, device=self.be.device) if hasattr(self.be, "device") and \
-        getattr(self.be.device, "type", "cpu") == "cuda" else None
+    self._sumbuf = torch.empty(256, dtype=torch.float64, device=self.be.device) if self.hip else None
     self._sumpos = 0
 
   def new_sums(self, n: int):
@@ -134,7 +138,7 @@ class _Ctx:
       if s is not None:
         kw["sums"] = s
     if self.grad is not None:
-      if "sums" in kw and hasattr(self.be, "loss_terms_grad_multi"):
+      if "sums" in kw and self.hip:
         # value_and_grad: the term is QUEUED -- the terms of a loss go out as one launch whose grid their tiles share
         # (flush_terms, at the latest in `reduce`); nobody reads a term's sums before the collective
         self._jobs.append((spec, pts, t, B_local, shared, coef, kw["sums"]))
@@ -313,27 +317,16 @@ def _source_samples(ctx, z, start, count, n_global, source):
 # ---- dim 2, value_and_grad of large batches: the terms composed from table-path launches ---------------------------
 # The fused gradient kernel evaluates the conditioner MLP per sample and multiplies per-sample weight gradients on
 # the matrix cores (4 G flow passes/s); cnf_pass_vjp on the conditioner tables needs neither (per-piece sufficient
-# statistics: DESIGN.md 5.4, 9 G passes/s).  So when a rank's share of a term is large enough for the tables
-# (cnf_grad.hip: slices >= 8 192 points, >= 262 144 points per pass) the term is ONE forward launch on the tables,
-# a few elementwise kernels for its value and adjoints, and ONE table backward launch.
-TABLE_BACKWARD_MIN_SLICE = 8192
-TABLE_BACKWARD_MIN_POINTS = 262144
+# statistics: DESIGN.md 5.4, 9 G passes/s).  So when the library's table kernels will take a rank's share of a term
+# (cnf_model_term_on_tables: the network, the set_pwl mode and the size thresholds, stated once in cnf_common.h) the
+# term is ONE forward launch on the tables, a few elementwise kernels for its value and adjoints, and ONE table
+# backward launch.  The same composition serves the loss WITHOUT its gradient (table forward + term epilogue: 70 G
+# flow passes/s where the fused loss kernel, three table sets in LDS, does 39 -- config 5's share 0.54 -> 0.3 ms).
 
-
-def _use_table_backward(ctx, dim, count, n_slices, passes=1):
-  be = ctx.be
-  return (ctx.grad is not None and dim == 2 and hasattr(be, "pass_vjp") and getattr(be, "_tables_ok", False)
-          and getattr(be, "_pwl_mode", 0) != 0 and count >= TABLE_BACKWARD_MIN_SLICE
-          and count * n_slices * passes >= TABLE_BACKWARD_MIN_POINTS)
-
-
-def _use_table_values(ctx, dim, count, n_slices, passes=1):
-  """The same composition for the loss WITHOUT its gradient (table forward + term epilogue: 70 G flow passes/s where the
-  fused loss kernel, three table sets in LDS, does 39 -- config 5's share 0.54 -> 0.3 ms)."""
-  be = ctx.be
-  return (ctx.grad is None and dim == 2 and hasattr(be, "kinetic_potential_vjp") and getattr(be, "_tables_ok", False)
-          and getattr(be, "_pwl_mode", 0) != 0 and count >= TABLE_BACKWARD_MIN_SLICE
-          and count * n_slices * passes >= TABLE_BACKWARD_MIN_POINTS)
+def _on_tables(ctx, count, n_slices, passes=1):
+  """Whether the term -- `passes` flow passes over n_slices slices of `count` points -- is composed from table launches:
+  the library's answer, for the value alone or (ctx.grad) for value and gradient."""
+  return ctx.hip and ctx.be.term_on_tables(count, count * n_slices * passes, ctx.grad is not None)
 
 
 def _neg_logprob_tables(ctx, samples, cond, coef):
@@ -344,9 +337,10 @@ def _neg_logprob_tables(ctx, samples, cond, coef):
   total = be.neg_logprob_vjp(samples, c, coef, ctx.grad) if ctx.grad is not None else None
   if total is not None:
     return total
+  # (the value alone; or the call declined for what `_on_tables` does not cover: no table reservation or slab room)
   # plain fp32 positions, like the fused loss kernel: a mean over the batch does not need the float64 position path
   # that makes single log_prob values good to 1e-5 (1.75 x the time of this launch)
-  was = getattr(be, "_precise", True)
+  was = be._precise
   be.set_precise(False)
   try:
     x, ildj = be.inverse_logdet(samples, c)
@@ -367,9 +361,10 @@ def _kinetic_tables(ctx, z, conds, count, dt, coef):
   S = _n_conds(th)
   half = np.float32(0.5 * dt)
   c2 = be.slice_conds(_cat_conds([th - half, th + half]))
-  done = be.kinetic_potential_vjp(z, c2, S, dt, coef, ctx.grad) if hasattr(be, "kinetic_potential_vjp") else None
+  done = be.kinetic_potential_vjp(z, c2, S, dt, coef, ctx.grad)
   if done is not None:      # (one call: no repeated copy of z, one table build, no adjoint scan)
     return done[0]
+  # (declined for what `_on_tables` does not cover: more than 128 slice sets, an odd slice length, no reservation or slab room)
   z2 = z.repeat(2 * S, 1)
   r, _ = be.forward_logdet(z2, c2, want_logdet=False)
   sums, rbar, _ = be.term_residual(_capi.TERM_KINETIC, r, None, count, p0=dt, loss_coef=coef, want_adjoints=ctx.grad is not None)
@@ -402,10 +397,10 @@ def _kinetic_potential_tables(ctx, z, conds, count, dt, c_kin, subtype, a, c_pot
   n = S * count
   half = np.float32(0.5 * dt)
   c3 = be.slice_conds(_cat_conds([th - half, th + half, th]))
-  done = (be.kinetic_potential_vjp(z, c3, S, dt, c_kin, ctx.grad, subtype=_capi.POTENTIALS[subtype], a=a, c_pot=c_pot)
-          if hasattr(be, "kinetic_potential_vjp") else None)
+  done = be.kinetic_potential_vjp(z, c3, S, dt, c_kin, ctx.grad, subtype=_capi.POTENTIALS[subtype], a=a, c_pot=c_pot)
   if done is not None:
     return done
+  # (declined for what `_on_tables` does not cover: more than 128 slice sets, an odd slice length, no reservation or slab room)
   z3 = z.repeat(3 * S, 1)
   r, _ = be.forward_logdet(z3, c3, want_logdet=False)
   if ctx.grad is None:
@@ -433,14 +428,15 @@ def _kl_sum(ctx, T, cond, batch_size, source, coef):
     samples = z
   else:
     samples = s1 * ((T - cond) / T) + z * (cond / T)      # target N(0,I) drawn from the same key
-  if _use_table_backward(ctx, z.shape[1], count, 1) or _use_table_values(ctx, z.shape[1], count, 1):
+  if _on_tables(ctx, count, 1):
     return _neg_logprob_tables(ctx, samples.contiguous(), cond, coef)
   return ctx.terms(_spec(_capi.TERM_NEG_LOGPROB), samples.contiguous(), [cond], count, coef)
 
 
 def _reverse_kl_sum(ctx, T, beta, cond, batch_size, coef):
   z, _, count = ctx.noise(batch_size)
-  if (_use_unfused(ctx, z.shape[1]) and count <= UNFUSED_RKL_MAX_BATCH) or _use_table_backward(ctx, z.shape[1], count, 1):
+  # (the gradient form alone: without a gradient the term stays on the fused kernel)
+  if (_use_unfused(ctx, z.shape[1]) and count <= UNFUSED_RKL_MAX_BATCH) or (ctx.grad is not None and _on_tables(ctx, count, 1)):
     return _reverse_kl_unfused(ctx, T, beta, cond, batch_size, coef)
   return ctx.terms(_spec(_capi.TERM_REVERSE_KL, T=T, beta=beta), z, [cond], count, coef)
 
@@ -449,15 +445,14 @@ def _potential_sum(ctx, a, subtype, conds, batch_size, coef):
   if subtype not in _capi.POTENTIALS:
     raise ValueError(f"unknown potential {subtype!r}")
   z, _, count = ctx.noise(batch_size)
-  if _use_table_backward(ctx, z.shape[1], count, _n_conds(conds)) or _use_table_values(ctx, z.shape[1], count, _n_conds(conds)):
+  if _on_tables(ctx, count, _n_conds(conds)):
     return _potential_tables(ctx, z, conds, count, subtype, a, coef)
   return ctx.terms(_spec(_capi.TERM_POTENTIAL, subtype=_capi.POTENTIALS[subtype], a=a), z, conds, count, coef)
 
 
 def _kinetic_sum(ctx, dt, conds, batch_size, coef):
   z, _, count = ctx.noise(batch_size)
-  if (_use_table_backward(ctx, z.shape[1], count, _n_conds(conds), passes=2)
-      or _use_table_values(ctx, z.shape[1], count, _n_conds(conds), passes=2)):
+  if _on_tables(ctx, count, _n_conds(conds), passes=2):
     return _kinetic_tables(ctx, z, conds, count, dt, coef)
   return ctx.terms(_spec(_capi.TERM_KINETIC, dt=dt), z, conds, count, coef)
 
@@ -494,7 +489,7 @@ def _score_terms_unfused(ctx, conds, batch_size, dt, dx, coef_score, loss_coef, 
   z3 = z.repeat(3 * S, 1)                                     # the same draw for every slice and condition
   want = ctx.grad is not None
   r, _ = be.forward_logdet(z3, c3, want_logdet=False)
-  if want and drift in (-1, _capi.DRIFTS["ou"]) and hasattr(be, "score_fd_vjp"):
+  if want and drift in (-1, _capi.DRIFTS["ou"]):
     # value AND backward of the score term in one launch: the kernel that differentiates the 2 D evaluation points
     # forms the score from its own forward passes (no separate forward launch over them)
     sums, rbar = be.score_fd_vjp(r, tt, count, dt, dx, coef_score, drift, a, loss_coef, ctx.grad)
@@ -520,7 +515,7 @@ def _reverse_kl_unfused(ctx, T, beta, cond, batch_size, coef):
   want = ctx.grad is not None
   total, ybar, lpbar = be.rkl_residual(y, lp, cond, T, beta, coef, want)
   if want:      # lp = base(noise) - fldj: the adjoint of the pass's log-det output is -lpbar
-    if _use_table_backward(ctx, z.shape[1], count, 1):      # (dim 2, large batch: the table form, on its own)
+    if ctx.grad is not None and _on_tables(ctx, count, 1):      # (dim 2, large batch: the table form, on its own)
       be.pass_vjp(z, c, ybar, -lpbar, False, grad=ctx.grad, want_xbar=False)
     else:
       ctx.defer_pass_vjp(z, [cond], count, ybar, -lpbar)
@@ -528,7 +523,7 @@ def _reverse_kl_unfused(ctx, T, beta, cond, batch_size, coef):
 
 
 def _use_unfused(ctx, dim):
-  return dim >= UNFUSED_SCORE_MIN_DIM and hasattr(ctx.be, "pass_vjp")
+  return dim >= UNFUSED_SCORE_MIN_DIM and ctx.hip
 
 
 def _kinetic_score_sum(ctx, beta, dt, dx, conds, batch_size, coef):
@@ -780,8 +775,7 @@ def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, b
   def later():
     if subtype == "obstacle":      # summed, not averaged, over slices (applications.py:397-400)
       z, _, count = ctx.noise(sub)
-      if (_use_table_backward(ctx, z.shape[1], count, _n_conds(t_batch), passes=2)      # one forward + one backward launch for both
-          or _use_table_values(ctx, z.shape[1], count, _n_conds(t_batch), passes=2)):
+      if _on_tables(ctx, count, _n_conds(t_batch), passes=2):      # one forward + one backward launch for both
         return list(_kinetic_potential_tables(ctx, z, t_batch, count, dt, c_kin, "obstacle", 0.0, 1.0 / sub))
       return [_kinetic_sum(ctx, dt, t_batch, sub, c_kin), _potential_sum(ctx, 0.0, "obstacle", t_batch, sub, 1.0 / sub)]
     return [_kinetic_sum(ctx, dt, t_batch, sub, c_kin)]

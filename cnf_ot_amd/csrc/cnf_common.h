@@ -92,6 +92,35 @@ enum CnfPath {
   CNF_PATH_DETECT = 8,      // per-sample condition: uniformity check + table kernels + MLP kernel, gated on the device
 };
 
+// ---- The dim-2 conditioner-table route, stated once (host code; no HIP call anywhere below) -------------------------
+// The network the tables exist for (cnf_pwl.h: hidden width PWL_H = 16, 5 bins, two MLP layers; the sin / cos
+// features of a periodized model are not piecewise linear in u) ...
+static inline bool pwl_network(const CnfConfig& g) {
+  return g.dim == 2 && g.hidden_size == 16 && g.num_bins == 5 && g.mlp_num_layers == 2 && !g.periodized;
+}
+// ... and the one its backward (vjp_pwl_kernel) exists for: what cnf_grad_enable allocates pwl_stats for
+static inline bool pwl_backward_network(const CnfConfig& g) { return pwl_network(g) && g.num_layers <= 4; }
+// This model has a table path under its current knobs ...
+static inline bool pwl_config_ok(const CnfModel* m) { return m->use_pwl && m->fast_math && pwl_network(m->cfg); }
+// ... and a table backward (after cnf_grad_enable; without pwl_stats the MLP backward remains)
+static inline bool pwl_backward_ok(const CnfModel* m) {
+  return pwl_config_ok(m) && pwl_backward_network(m->cfg) && m->pwl_stats != nullptr;
+}
+// A pass on the tables is worth it while a slice amortises its tables and their per-piece finishing (measured
+// crossover: see DESIGN.md)
+// (measured, scripts/exp_vjp_crossover.py, round 3's kernel: 131 072 points 0.049 vs 0.044 ms for the MLP backward,
+// 262 144 points 0.056 vs 0.066 -- 32 slices of 8 192: 0.062 vs 0.066 --, 524 288 points 0.072 vs 0.110; slices of
+// 4 096 points lose until there are ~100 of them.  Round 2's kernel crossed over at twice that.)
+constexpr int64_t PWL_MIN_SLICE = 8192, PWL_MIN_POINTS = 262144;
+// Whether a term composed from table launches -- slices of slice_len points, n_points over all slices of all its
+// passes -- is taken by the table kernels under the model's use_pwl mode (0: never; 1: from the thresholds up; 2: at
+// every size); with_grad: by the table backward too.  What cnf_pass_vjp, cnf_neg_logprob_vjp and
+// cnf_kinetic_potential_vjp ask before their own conditions (alignment, odd slice lengths, slab room, slice count).
+static inline bool pwl_term_on_tables(const CnfModel* m, int64_t slice_len, int64_t n_points, bool with_grad) {
+  if (with_grad ? !pwl_backward_ok(m) : !pwl_config_ok(m)) return false;
+  return m->use_pwl != 1 || (slice_len >= PWL_MIN_SLICE && n_points >= PWL_MIN_POINTS);
+}
+
 #ifdef CNF_MINIMAL_CONFIGS   /* faster builds while iterating on the kernels */
 #define CNF_KERNEL_CONFIGS(X) X(16, 5)
 #else

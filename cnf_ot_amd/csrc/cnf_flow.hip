@@ -1660,10 +1660,12 @@ extern "C" int64_t cnf_model_reserved(CnfModel* m, void* stream) {
 
 static const int64_t PWL_MAX_SLICES = 2048;      // slices per build + flow kernel pair
 
-static bool pwl_config_ok(const CnfModel* m) {
-  const CnfConfig& g = m->cfg;
-  return m->use_pwl && m->fast_math && g.dim == 2 && g.hidden_size == cnf::PWL_H && g.num_bins == 5 &&
-         g.mlp_num_layers == 2 && !g.periodized;      // (sin / cos features are not piecewise linear in u)
+static_assert(cnf::PWL_H == 16, "pwl_network (cnf_common.h) states the tables' network");
+
+extern "C" int cnf_model_has_tables(const CnfModel* m) { return m && pwl_network(m->cfg) ? 1 : 0; }
+
+extern "C" int cnf_model_term_on_tables(const CnfModel* m, int64_t slice_len, int64_t n_points, int with_grad) {
+  return m && pwl_term_on_tables(m, slice_len, n_points, with_grad != 0) ? 1 : 0;
 }
 
 // The piecewise-linear path (cnf_pwl.h): dim 2, H = 16, K = 5, two MLP layers, a condition that is

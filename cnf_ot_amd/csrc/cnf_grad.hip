@@ -1549,6 +1549,38 @@ extern "C" int cnf_grad_supported(const CnfConfig* c) {
          c->num_layers >= 1 && grad_lds_bytes(c->dim, c->num_layers, 64) <= 160 * 1024;
 }
 
+// Launches a backward kernel over n_tiles tiles of ts threads: as many workgroups as are resident at once and, where
+// its waves write gradient slabs (one each), no more than cnf_grad_enable made room for.  Returns the slabs written
+// (grid x waves), or -1 when the kernel cannot have `lds` bytes (nothing launched).
+template <class K, class A>
+static int64_t launch_backward(const CnfModel* m, K kernel, const A& a, int64_t n_tiles, int ts, size_t lds, bool slabs,
+                               hipStream_t stream) {
+  if (!ensure_lds(kernel, lds)) return -1;
+  const int64_t max_grid = slabs ? m->grad_max_blocks * 4 / (ts / 64) : (int64_t)1 << 30;
+  int64_t cap = (int64_t)resident_blocks_per_cu(kernel, ts, lds) * m->num_cus;
+  if (cap > max_grid) cap = max_grid;
+  const int64_t grid = balanced_grid(n_tiles, cap);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(ts), lds, stream, a);
+  return grid * (ts / 64);
+}
+
+// grad += the sum of the first n_slabs slabs (amax != null: the table backward's, whose adjoint maximum it clears)
+static int grad_finish(const CnfModel* m, int64_t n_slabs, const float* params, float* grad, uint32_t* amax,
+                       hipStream_t stream) {
+  const int fb = (int)((m->n_params + 31) / 32);
+  hipLaunchKernelGGL(grad_finish_kernel, dim3(fb), dim3(1024), 0, stream, m->grad_slabs, n_slabs, m->n_params, params,
+                     grad, (double)m->sc.span_eff, (double)m->sc.sp_offset, amax);
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
+// The vjp_kernel instantiation of a model (dim 2 with fast math has its own; without weight gradients nothing is staged)
+typedef void (*VjpKernel)(const VjpArgs);
+static VjpKernel vjp_kernel_of(const CnfModel* m, bool wgrad) {
+  if (!wgrad) return m->fast_math ? vjp_kernel<true, false> : vjp_kernel<false, false>;
+  if (!m->fast_math) return vjp_kernel<false, true>;
+  return m->cfg.dim == 2 ? vjp_kernel<true, true, 2> : vjp_kernel<true, true>;
+}
+
 extern "C" int cnf_loss_terms_grad_multi(CnfModel* m, int32_t n_terms, const CnfLossSpec* specs, const float* const* pts,
                                          const int32_t* pts_shared, const float* const* t, const int64_t* n_slices,
                                          const int64_t* B, const float* scale, double* const* sums, float* grad,
@@ -1584,27 +1616,10 @@ extern "C" int cnf_loss_terms_grad_multi(CnfModel* m, int32_t n_terms, const Cnf
   for (int i = a.n_jobs; i < GRAD_MAX_JOBS; ++i) { a.job[i] = a.job[0]; a.job[i].first_tile = a.n_tiles; }
   if (!m->grad_slabs) return CNF_ERR_INVALID;      // cnf_grad_enable first
   if (wait_for_params(m, stream) != CNF_OK) return CNF_ERR_HIP;
-  const int64_t max_grid = m->grad_max_blocks * 4 / (ts / 64);           // (slabs: one per wave)
-  int64_t n_slabs = 0;
-  auto launch = [&](auto kernel) -> bool {
-    if (!ensure_lds(kernel, lds)) return false;
-    int64_t cap = (int64_t)resident_blocks_per_cu(kernel, ts, lds) * m->num_cus;
-    if (cap > max_grid) cap = max_grid;
-    const int64_t grid = balanced_grid(a.n_tiles, cap);
-    n_slabs = grid * (ts / 64);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(ts), lds, stream, a);
-    return true;
-  };
-  if (m->fast_math) {
-    if (D == 2 ? !launch(grad_kernel<true, 2>) : !launch(grad_kernel<true>)) return CNF_ERR_HIP;
-  } else {
-    if (!launch(grad_kernel<false>)) return CNF_ERR_HIP;
-  }
-  if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  const int fb = (int)((m->n_params + 31) / 32);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(fb), dim3(1024), 0, stream, m->grad_slabs, n_slabs, m->n_params, params,
-                     grad, (double)m->sc.span_eff, (double)m->sc.sp_offset, (uint32_t*)nullptr);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+  void (*const kernel)(const GradArgs) = generic ? (m->fast_math ? grad_kernel<true> : grad_kernel<false>) : grad_kernel<true, 2>;
+  const int64_t n_slabs = launch_backward(m, kernel, a, a.n_tiles, ts, lds, true, stream);
+  if (n_slabs < 0 || hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
+  return grad_finish(m, n_slabs, params, grad, nullptr, stream);
 }
 
 extern "C" int cnf_loss_terms_grad(CnfModel* m, const CnfLossSpec* spec, const float* pts, int pts_shared,
@@ -1625,7 +1640,7 @@ extern "C" int cnf_grad_enable(CnfModel* m, int64_t max_blocks) {
   m->grad_max_blocks = max_blocks;
   // the table backward of dim-2 passes (vjp_pwl_kernel): per-piece statistics of PWL_STAT_SLICES slices, kept zero
   // between calls (pwl_stats_finish_kernel clears what it reads)
-  if (!m->pwl_stats && m->cfg.dim == 2 && m->cfg.num_layers <= 4 && m->cfg.mlp_num_layers == 2) {
+  if (!m->pwl_stats && pwl_backward_network(m->cfg)) {
     // [64 bytes: the call's largest adjoint][statistics][coarse statistics]
     const size_t bytes = 64 + 2 * sizeof(stat_t) * (size_t)PWL_STAT_SLICES * m->cfg.num_layers * PWL_NPIECE * PWL_STAT;
     if (hipMalloc((void**)&m->pwl_stats, bytes) == hipSuccess) {
@@ -1673,18 +1688,11 @@ static int pass_vjp_pwl(CnfModel* m, int to_base, const float* pts, const float*
                         const float* ybar, const float* ldbar, float* xbar, float* grad, const float* params,
                         int64_t B, hipStream_t stream, float seed_coef = 0.0f, double* seed_sums = nullptr,
                         const float* built = nullptr) {
-  const CnfConfig& g = m->cfg;
-  if (!m->use_pwl || !m->fast_math || !m->pwl_stats || g.dim != 2 || g.hidden_size != PWL_H || g.num_bins != GK ||
-      g.mlp_num_layers != 2 || g.num_layers > 4 || g.periodized)
-    return CNF_ERR_UNSUPPORTED;
-  const int L = g.num_layers;
+  static_assert(PWL_H == 16 && GK == 5, "pwl_network (cnf_common.h) states the tables' network");
+  const int L = m->cfg.num_layers;
   const int64_t slice_len = c_block < B ? c_block : B;
   const int64_t n_slices = (B + slice_len - 1) / slice_len;
-  // worth it while a slice amortises its tables and their per-piece finishing (measured crossover: see DESIGN.md)
-  // (measured, scripts/exp_vjp_crossover.py, round 3's kernel: 131 072 points 0.049 vs 0.044 ms for the MLP backward,
-  // 262 144 points 0.056 vs 0.066 -- 32 slices of 8 192: 0.062 vs 0.066 --, 524 288 points 0.072 vs 0.110; slices of
-  // 4 096 points lose until there are ~100 of them.  Round 2's kernel crossed over at twice that.)
-  if (m->use_pwl == 1 && (slice_len < 8192 || B < 262144)) return CNF_ERR_UNSUPPORTED;
+  if (!pwl_term_on_tables(m, slice_len, B, true)) return CNF_ERR_UNSUPPORTED;
   // (a lane's two samples are one 16-byte access of the points and adjoints, one 8-byte access of ldbar)
   if ((reinterpret_cast<uintptr_t>(pts) & 15) || (reinterpret_cast<uintptr_t>(ybar) & 15) ||
       (reinterpret_cast<uintptr_t>(xbar) & 15) || (reinterpret_cast<uintptr_t>(ldbar) & 7) || (n_slices > 1 && (slice_len & 1)))
@@ -1699,10 +1707,13 @@ static int pass_vjp_pwl(CnfModel* m, int to_base, const float* pts, const float*
   const size_t lds = lds_bytes(acc_r);
   if (lds > 160 * 1024) return CNF_ERR_UNSUPPORTED;
   const bool seeded = seed_sums != nullptr;
-  if (seeded ? (L == 2 ? !ensure_lds(vjp_pwl_kernel<true, 2, true>, lds) : !ensure_lds(vjp_pwl_kernel<true, 0, true>, lds))
-      : L == 2 ? (to_base ? !ensure_lds(vjp_pwl_kernel<true, 2>, lds) : !ensure_lds(vjp_pwl_kernel<false, 2>, lds))
-               : (to_base ? !ensure_lds(vjp_pwl_kernel<true>, lds) : !ensure_lds(vjp_pwl_kernel<false>, lds)))
-    return CNF_ERR_UNSUPPORTED;
+  typedef void (*VjpPwlKernel)(const VjpPwlArgs);
+  // L = 2 (every configuration of the reference) has its own instantiations with the layer loop unrolled
+  const VjpPwlKernel kernel =
+      seeded ? (L == 2 ? (VjpPwlKernel)vjp_pwl_kernel<true, 2, true> : (VjpPwlKernel)vjp_pwl_kernel<true, 0, true>)
+      : to_base ? (L == 2 ? (VjpPwlKernel)vjp_pwl_kernel<true, 2> : (VjpPwlKernel)vjp_pwl_kernel<true>)
+                : (L == 2 ? (VjpPwlKernel)vjp_pwl_kernel<false, 2> : (VjpPwlKernel)vjp_pwl_kernel<false>);
+  if (!ensure_lds(kernel, lds)) return CNF_ERR_UNSUPPORTED;
   // The seeds are seed_coef x (a base point | 1): the scale is set for adjoints up to 32 |seed_coef| -- base points
   // lie within the splines' range of +-10 unless the data does not -- with the 2^22 of head room every term has
   uint32_t amax_bits = 0;
@@ -1740,25 +1751,13 @@ static int pass_vjp_pwl(CnfModel* m, int to_base, const float* pts, const float*
     const int64_t grid = tiles < m->num_cus ? tiles : m->num_cus;
     const int split = ns * L <= 32 ? 8 : 1;
     if (grid + ns * L * split > m->grad_max_blocks * 4) return s0 == 0 ? CNF_ERR_UNSUPPORTED : CNF_ERR_HIP;      // (slabs: cnf_grad_enable)
-    if (seeded) {
-      if (L == 2) hipLaunchKernelGGL((vjp_pwl_kernel<true, 2, true>), dim3((unsigned)grid), dim3(threads), lds, stream, a);
-      else hipLaunchKernelGGL((vjp_pwl_kernel<true, 0, true>), dim3((unsigned)grid), dim3(threads), lds, stream, a);
-    } else if (L == 2) {
-      if (to_base) hipLaunchKernelGGL((vjp_pwl_kernel<true, 2>), dim3((unsigned)grid), dim3(threads), lds, stream, a);
-      else hipLaunchKernelGGL((vjp_pwl_kernel<false, 2>), dim3((unsigned)grid), dim3(threads), lds, stream, a);
-    } else {
-      if (to_base) hipLaunchKernelGGL(vjp_pwl_kernel<true>, dim3((unsigned)grid), dim3(threads), lds, stream, a);
-      else hipLaunchKernelGGL(vjp_pwl_kernel<false>, dim3((unsigned)grid), dim3(threads), lds, stream, a);
-    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
     StatsFinishArgs f;
     f.weights = m->prep + hdr_floats(GK); f.per_layer = m->per_layer; f.cvals = c + s0; f.tables = tables;
     f.stats = stats; f.coarse = coarse; f.amax = amax; f.amax_bits = amax_bits; f.slabs = m->grad_slabs; f.n_params = m->n_params; f.L = L;
     f.first_slab = (int32_t)grid; f.split = split;
     hipLaunchKernelGGL(pwl_stats_finish_kernel, dim3((unsigned)(ns * L * split)), dim3(256), 0, stream, f);
-    const int fb = (int)((m->n_params + 31) / 32);
-    hipLaunchKernelGGL(grad_finish_kernel, dim3(fb), dim3(1024), 0, stream, m->grad_slabs, grid + ns * L * split, m->n_params,
-                       params, grad, (double)m->sc.span_eff, (double)m->sc.sp_offset, amax);
-    if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
+    if (grad_finish(m, grid + ns * L * split, params, grad, amax, stream) != CNF_OK) return CNF_ERR_HIP;
   }
   return CNF_OK;
 }
@@ -1787,32 +1786,11 @@ static int pass_vjp_impl(CnfModel* m, int to_base, const float* pts, const float
   const int D = m->cfg.dim, L = m->cfg.num_layers;
   const int ts = pick_tile([&](int t) { return vjp_lds_bytes(D, L, t, grad != nullptr); });
   const size_t lds = vjp_lds_bytes(D, L, ts, grad != nullptr);
-  const int64_t n_tiles = (B + ts - 1) / ts;
-  const int64_t max_grid = grad ? m->grad_max_blocks * 4 / (ts / 64) : (int64_t)1 << 30;
-  int64_t n_slabs = 0;
-  auto launch = [&](auto kernel) -> bool {
-    if (!ensure_lds(kernel, lds)) return false;
-    int64_t cap = (int64_t)resident_blocks_per_cu(kernel, ts, lds) * m->num_cus;
-    if (cap > max_grid) cap = max_grid;
-    const int64_t grid = balanced_grid(n_tiles, cap);
-    n_slabs = grid * (ts / 64);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(ts), lds, stream, a);
-    return true;
-  };
-  if (!grad) {
-    if (m->fast_math ? !launch(vjp_kernel<true, false>) : !launch(vjp_kernel<false, false>)) return CNF_ERR_UNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-  }
-  if (m->fast_math) {
-    if (D == 2 ? !launch(vjp_kernel<true, true, 2>) : !launch(vjp_kernel<true, true>)) return CNF_ERR_UNSUPPORTED;
-  } else {
-    if (!launch(vjp_kernel<false, true>)) return CNF_ERR_UNSUPPORTED;
-  }
+  const int64_t n_slabs = launch_backward(m, vjp_kernel_of(m, grad != nullptr), a, (B + ts - 1) / ts, ts, lds,
+                                          grad != nullptr, stream);
+  if (n_slabs < 0) return CNF_ERR_UNSUPPORTED;
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  const int fb = (int)((m->n_params + 31) / 32);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(fb), dim3(1024), 0, stream, m->grad_slabs, n_slabs, m->n_params, params,
-                     grad, (double)m->sc.span_eff, (double)m->sc.sp_offset, (uint32_t*)nullptr);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+  return grad ? grad_finish(m, n_slabs, params, grad, nullptr, stream) : CNF_OK;
 }
 
 extern "C" int cnf_input_vjp(CnfModel* m, int to_base, const float* pts, const float* c, int64_t c_block,
@@ -1827,16 +1805,11 @@ extern "C" int cnf_kinetic_potential_vjp(CnfModel* m, const float* z, int64_t co
   if (!m || !z || !c || !kin || (grad && !params) || !work || count < 1 || S < 1 || !(dt > 0.f)) return CNF_ERR_INVALID;
   if ((subtype >= 0) != (pot != nullptr) || (subtype >= 0 && !potential_ok(subtype))) return CNF_ERR_INVALID;
   if (!m->params_set || (grad && !m->grad_slabs)) return CNF_ERR_INVALID;
-  {      // (pass_vjp_pwl's conditions, asked before anything is launched; grad == NULL: the terms' values alone)
-    const CnfConfig& g = m->cfg;
-    if (!m->use_pwl || g.dim != 2 || g.hidden_size != PWL_H || g.num_bins != GK || g.mlp_num_layers != 2 || g.periodized)
-      return CNF_ERR_UNSUPPORTED;
-    if (grad && (!cnf_grad_supported(&g) || !m->fast_math || !m->pwl_stats || g.num_layers > 4)) return CNF_ERR_UNSUPPORTED;
-  }
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t sets = pot ? 3 : 2, ns = sets * S, B = ns * count, n = (int64_t)S * count;
+  // (what pass_vjp_pwl will ask, before anything is launched; grad == NULL: the terms' values alone)
+  if (!pwl_term_on_tables(m, count, B, grad != nullptr) || (grad && !cnf_grad_supported(&m->cfg))) return CNF_ERR_UNSUPPORTED;
   if (ns > PWL_STAT_SLICES || (count & 1) || (reinterpret_cast<uintptr_t>(work) & 15)) return CNF_ERR_UNSUPPORTED;
-  if (m->use_pwl == 1 && (count < 8192 || B < 262144)) return CNF_ERR_UNSUPPORTED;      // (pass_vjp_pwl's thresholds)
   if (wait_for_params(m, stream) != CNF_OK) return CNF_ERR_HIP;
   float* r = work;
   float* rbar = grad ? work + 2 * B : nullptr;
@@ -1900,28 +1873,10 @@ static int fd_vjp_launch(CnfModel* m, VjpArgs& a, const float* pts, const float*
   const size_t lds = vjp_lds_bytes(D, L, ts, true);
   if (lds > 160 * 1024) return CNF_ERR_UNSUPPORTED;
   const int64_t tp = (ts / (2 * D)) * (2 * D);
-  const int64_t n_tiles = (a.B + tp - 1) / tp;
-  const int64_t max_grid = m->grad_max_blocks * 4 / (ts / 64);
-  int64_t n_slabs = 0;
-  auto launch = [&](auto kernel) -> bool {
-    if (!ensure_lds(kernel, lds)) return false;
-    int64_t cap = (int64_t)resident_blocks_per_cu(kernel, ts, lds) * m->num_cus;
-    if (cap > max_grid) cap = max_grid;
-    const int64_t grid = balanced_grid(n_tiles, cap);
-    n_slabs = grid * (ts / 64);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(ts), lds, stream, a);
-    return true;
-  };
-  if (m->fast_math) {
-    if (D == 2 ? !launch(vjp_kernel<true, true, 2>) : !launch(vjp_kernel<true, true>)) return CNF_ERR_UNSUPPORTED;
-  } else {
-    if (!launch(vjp_kernel<false, true>)) return CNF_ERR_UNSUPPORTED;
-  }
+  const int64_t n_slabs = launch_backward(m, vjp_kernel_of(m, true), a, (a.B + tp - 1) / tp, ts, lds, true, stream);
+  if (n_slabs < 0) return CNF_ERR_UNSUPPORTED;
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  const int fb = (int)((m->n_params + 31) / 32);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(fb), dim3(1024), 0, stream, m->grad_slabs, n_slabs, m->n_params, params,
-                     grad, (double)m->sc.span_eff, (double)m->sc.sp_offset, (uint32_t*)nullptr);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+  return grad_finish(m, n_slabs, params, grad, nullptr, stream);
 }
 
 extern "C" int cnf_logprob_fd_vjp(CnfModel* m, const float* pts, const float* c, int64_t c_block, float dx,

@@ -146,8 +146,8 @@ class FlowEngine:
     self._reserved = {}               # stream -> table sets reserved (cnf_model_reserve)
     self._pwl_mode = 1
     self._precise = True
-    self._tables_ok = (cfg.dim == 2 and cfg.hidden_size == 16 and cfg.num_bins == 5 and cfg.mlp_num_layers == 2
-                       and not cfg.periodized)
+    self._tables_ok = bool(self.lib.cnf_model_has_tables(self._h))      # a reservation is of use
+    self._grad_enabled = False
 
   def __del__(self):
     h = getattr(self, "_h", None)
@@ -199,6 +199,24 @@ class FlowEngine:
       _capi.check(self.lib.cnf_model_reserve(self._h, stream, want), "cnf_model_reserve")
     self._reserved[stream] = want
     return want
+
+  def term_on_tables(self, slice_len: int, n_points: int, with_grad: bool) -> bool:
+    """cnf_model_term_on_tables: whether a loss term composed from table launches -- slices of `slice_len` points,
+    `n_points` over all slices of all its passes -- is taken by the table kernels as the model stands (`set_pwl`
+    mode, network, thresholds); with_grad: by the table backward too -- ask after `grad_ready`, which allocates its
+    statistics.  No HIP call: legal inside a stream capture."""
+    return bool(self.lib.cnf_model_term_on_tables(self._h, int(slice_len), int(n_points), 1 if with_grad else 0))
+
+  def grad_ready(self, grad: torch.Tensor) -> None:
+    """What every gradient call starts with: parameters loaded, cnf_grad_enable done, `grad` a flat float32
+    [n_params] tensor.  cnf_grad_enable allocates (once per engine), so the first call comes before a stream capture."""
+    if self._flat is None:
+      raise RuntimeError("load(params) before asking for gradients")
+    if not self._grad_enabled:
+      with _OnDevice(self.device):
+        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
+      self._grad_enabled = True
+    self._check_out(grad, (self.cfg.param_count(),), "grad")
 
   def last_path(self) -> str:
     """Which kernels the most recent compute call ran (cnf_model_last_path)."""
@@ -430,19 +448,13 @@ class FlowEngine:
   def loss_terms_grad(self, spec, pts, t, B: int, shared: bool, scale: float, grad: torch.Tensor, sums=None) -> torch.Tensor:
     """cnf_loss_terms_grad: like `loss_terms`, and accumulates
     scale * d(sum of the term)/d(params) into `grad` (flat float32 [n_params])."""
-    if self._flat is None:
-      raise RuntimeError("load(params) before asking for gradients")
-    if not getattr(self, "_grad_enabled", False):
-      with _OnDevice(self.device):
-        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-      self._grad_enabled = True
+    self.grad_ready(grad)
     pts = self._points(pts, "loss_terms_grad")
     t = self.slice_conds(t)
     n_slices = t.numel()
     need = B if shared else n_slices * B
     if pts.shape[0] != need:
       raise ValueError(f"loss_terms_grad: pts has {pts.shape[0]} rows, expected {need}")
-    self._check_out(grad, (self.cfg.param_count(),), "grad")
     if sums is None:
       sums = torch.empty(n_slices, dtype=torch.float64, device=self.device)
     if n_slices > 0:
@@ -456,13 +468,7 @@ class FlowEngine:
   def loss_terms_grad_multi(self, jobs, grad: torch.Tensor) -> None:
     """cnf_loss_terms_grad_multi: several terms of one loss in ONE launch.  jobs: (spec, pts, t, B, shared, scale, sums)
     tuples, at most 4 per launch (longer lists go out in groups); `sums` tensors are filled, `grad` accumulated."""
-    if self._flat is None:
-      raise RuntimeError("load(params) before asking for gradients")
-    if not getattr(self, "_grad_enabled", False):
-      with _OnDevice(self.device):
-        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-      self._grad_enabled = True
-    self._check_out(grad, (self.cfg.param_count(),), "grad")
+    self.grad_ready(grad)
     for g0 in range(0, len(jobs), 4):
       grp = jobs[g0:g0 + 4]
       n = len(grp)
@@ -520,13 +526,7 @@ class FlowEngine:
     ybar = None if ybar is None else self._check_out(self._points(ybar, "ybar"), pts.shape, "ybar")
     ldbar = None if ldbar is None else ldbar.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
     if grad is not None:
-      if self._flat is None:
-        raise RuntimeError("load(params) before asking for gradients")
-      if not getattr(self, "_grad_enabled", False):
-        with _OnDevice(self.device):
-          _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-        self._grad_enabled = True
-      self._check_out(grad, (self.cfg.param_count(),), "grad")
+      self.grad_ready(grad)
       if self._pwl_mode and B > 0:          # the table form of the backward builds tables for chunks of 128 slices
         self.reserve(min(-(-B // c_block), 128))
     xbar = torch.empty_like(pts) if want_xbar else None
@@ -548,13 +548,7 @@ class FlowEngine:
     pts = self._points(pts, "neg_logprob_vjp")
     B = pts.shape[0]
     c, c_block = self.cond(cond, B)
-    if self._flat is None:
-      raise RuntimeError("load(params) before asking for gradients")
-    if not getattr(self, "_grad_enabled", False):
-      with _OnDevice(self.device):
-        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-      self._grad_enabled = True
-    self._check_out(grad, (self.cfg.param_count(),), "grad")
+    self.grad_ready(grad)
     n_slices = max(-(-B // c_block), 1)
     if sums is None:
       sums = torch.empty(n_slices, dtype=torch.float64, device=self.device)
@@ -584,13 +578,7 @@ class FlowEngine:
     if not self._pwl_mode or count == 0 or self.cfg.dim != 2:
       return None
     if grad is not None:
-      if self._flat is None:
-        raise RuntimeError("load(params) before asking for gradients")
-      if not getattr(self, "_grad_enabled", False):
-        with _OnDevice(self.device):
-          _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-        self._grad_enabled = True
-      self._check_out(grad, (self.cfg.param_count(),), "grad")
+      self.grad_ready(grad)
     if sets * S > 128:
       return None
     self.reserve(sets * S)
@@ -629,17 +617,11 @@ class FlowEngine:
     """cnf_logprob_fd_vjp: backward of `logprob_fd` for the output adjoint gbar
     [B, D]: returns pts_bar (or None) and accumulates the parameter gradient
     into `grad`."""
-    if self._flat is None:
-      raise RuntimeError("load(params) before asking for gradients")
-    if not getattr(self, "_grad_enabled", False):
-      with _OnDevice(self.device):
-        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-      self._grad_enabled = True
+    self.grad_ready(grad)
     pts = self._points(pts, "logprob_fd_vjp")
     B = pts.shape[0]
     c, c_block = self.cond(cond, B)
     gbar = self._check_out(self._points(gbar, "gbar"), pts.shape, "gbar")
-    self._check_out(grad, (self.cfg.param_count(),), "grad")
     pts_bar = torch.empty_like(pts) if want_pts_bar else None
     if B > 0:
       with _OnDevice(self.device):
@@ -653,12 +635,7 @@ class FlowEngine:
                    grad: torch.Tensor):
     """cnf_score_fd_vjp: per-slice sums (float64 [n / count]) of the score-term residual from r [3n, D] AND its
     backward in one launch: returns (sums, rbar [3n, D]); the parameter gradient is accumulated into `grad`."""
-    if self._flat is None:
-      raise RuntimeError("load(params) before asking for gradients")
-    if not getattr(self, "_grad_enabled", False):
-      with _OnDevice(self.device):
-        _capi.check(self.lib.cnf_grad_enable(self._h, 0), "cnf_grad_enable")
-      self._grad_enabled = True
+    self.grad_ready(grad)
     r = self._points(r, "score_fd_vjp")
     n = r.shape[0] // 3
     if r.shape[0] != 3 * n or n % count:
@@ -666,7 +643,6 @@ class FlowEngine:
     c = self.slice_conds(cond)
     if c.numel() != n // count:
       raise ValueError("one condition per slice")
-    self._check_out(grad, (self.cfg.param_count(),), "grad")
     sums = torch.empty(n // count, dtype=torch.float64, device=self.device)
     rbar = torch.empty_like(r)
     if n > 0:

@@ -121,6 +121,19 @@ int cnf_model_reserve(CnfModel *m, void *stream, int64_t n_sets);
 int64_t cnf_model_reserved(CnfModel *m, void *stream);
 int64_t cnf_model_table_bytes(const CnfModel *m);
 
+/* The library's own answer to "will this run on the tables?", for a caller that composes a loss term from table
+ * launches (cnf_sample / cnf_inverse_logdet + cnf_term_residual + cnf_pass_vjp, or cnf_neg_logprob_vjp /
+ * cnf_kinetic_potential_vjp) instead of one fused cnf_loss_terms(_grad) launch.  cnf_model_has_tables: 1 if the
+ * model's network is the one the tables exist for (dim 2, the reference's conditioner), whatever the knobs say -- a
+ * reservation is of use.  cnf_model_term_on_tables: 1 if a term with slices of slice_len points, n_points over all
+ * slices of all its passes, is taken by the table kernels as the model stands; with_grad: by the table backward too
+ * (after cnf_grad_enable, which allocates its statistics).  Those entry points ask the same question before their
+ * own conditions (alignment, odd slice lengths, more than 128 slice sets), so a 1 is not a promise: compose the
+ * term from the other calls when one of them still returns CNF_ERR_UNSUPPORTED.  Neither makes a HIP call: both are
+ * legal inside a stream capture. */
+int cnf_model_has_tables(const CnfModel *m);
+int cnf_model_term_on_tables(const CnfModel *m, int64_t slice_len, int64_t n_points, int with_grad);
+
 /* Numerics of the data -> base direction (cnf_log_prob, cnf_inverse_logdet).
  * log_prob = sum_d -x_d^2/2 + ildj multiplies the error of the recovered base
  * point by |x| (up to 5), and an all-fp32 evaluation of the softmax-normalised

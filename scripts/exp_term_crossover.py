@@ -1,5 +1,5 @@
 """ot_loss_fn value_and_grad (dim 2) with its terms fused (cnf_loss_terms_grad) or composed on the tables, around the
-thresholds of applications.TABLE_BACKWARD_MIN_*."""
+thresholds of the table route (cnf_common.h: PWL_MIN_SLICE / PWL_MIN_POINTS, what cnf_model_term_on_tables answers)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,10 +12,9 @@ for sub in ("free", "obstacle"):
     f = lambda p, rng, lam, bs, **kw: app.ot_loss_fn(model, 2, 1.0, 0.01, tbs, sub, p, rng, lam, bs, source="gaussian", **kw)
     vg = app.value_and_grad(f)
     row = []
-    for minpts, minslice in ((1 << 40, 1 << 40), (1, 1)):
-      app.TABLE_BACKWARD_MIN_POINTS, app.TABLE_BACKWARD_MIN_SLICE = minpts, minslice
+    for mode in (0, 2):      # set_pwl(0): every term on the fused gradient kernel; 2: composed on the tables at every size
       be = model.terms_backend(params)
-      be.set_pwl(2 if minpts == 1 else 1)
+      be.set_pwl(mode)
       for _ in range(3): vg(params, 11, 50.0, B)
       torch.cuda.synchronize(); t0 = time.perf_counter()
       for _ in range(20): vg(params, 11, 50.0, B)

@@ -533,6 +533,50 @@ def test_pass_vjp_table_form_matches_mlp_backward(dev, to_base, L, S, Bs):
     assert (g2[lo:hi] - g0[lo:hi]).abs().max().item() <= 1e-4 * max(ref, 1e-3 * g0.abs().max().item()), (lo, hi)
 
 
+# (slice length, slices, passes) -> composed from table launches in the default mode?  From the predicate the loss code
+# used to evaluate itself: count >= 8 192 and count * slices * passes >= 262 144.
+TABLE_ROUTES = [(65536, 1, 1, False), (262144, 1, 1, True), (131072, 1, 1, False), (131072, 1, 2, True),
+                (8192, 32, 1, True), (8192, 16, 2, True), (8191, 64, 1, False), (4096, 96, 2, False)]
+
+
+def test_table_route_query_in_the_default_mode(dev):
+  """cnf_model_term_on_tables (FlowEngine.term_on_tables) in the default table mode: the routes the loss code took
+  when it kept its own copy of the thresholds, for the value alone and with the gradient; never at dim 3, with
+  set_pwl(0), or -- with the gradient -- for 5 flow layers (the table backward exists for up to 4).  cnf_pass_vjp takes
+  the route the query names."""
+  from cnf_ot_amd import FlowConfig, FlowEngine, Params
+
+  def engine(**kw):
+    cfg = FlowConfig(**kw)
+    params = Params.random(cfg, 0.2, seed=6, device=dev)
+    eng = FlowEngine(cfg, dev).load(params)
+    eng.grad_ready(torch.zeros_like(params.flat))
+    return cfg, eng
+
+  cfg, eng = engine(dim=2)
+  _, eng3 = engine(dim=3)
+  _, eng5 = engine(dim=2, num_layers=5)
+  for count, S, passes, want in TABLE_ROUTES:
+    n = count * S * passes
+    assert want == (count >= 8192 and n >= 262144)
+    for with_grad in (False, True):
+      assert eng.term_on_tables(count, n, with_grad) == want, (count, S, passes, with_grad)
+      assert not eng3.term_on_tables(count, n, with_grad)
+      eng.set_pwl(0)
+      assert not eng.term_on_tables(count, n, with_grad)
+      eng.set_pwl(1)
+    assert not eng5.term_on_tables(count, n, True)
+  gen = torch.Generator(device="cpu").manual_seed(3)
+  for B in (65536, 262144):      # a "no" shape first: the MLP backward leaves last_path alone
+    pts = torch.randn(B, 2, generator=gen).to(dev)
+    ybar = torch.randn(B, 2, generator=gen).to(dev)
+    g = torch.zeros(cfg.param_count(), device=dev)
+    eng.pass_vjp(pts, torch.tensor([0.4], device=dev), ybar, None, False, grad=g, want_xbar=False)
+    torch.cuda.synchronize()
+    assert (eng.last_path() == "tables") == eng.term_on_tables(B, B, True), B
+    assert torch.isfinite(g).all() and g.abs().max().item() > 0
+
+
 @pytest.mark.parametrize("bad", [float("nan"), float("inf")])
 def test_table_backward_does_not_hide_non_finite_adjoints(dev, bad):
   """The fixed-point statistics of the table backward cannot carry a NaN or an Inf (an integer sum, range tests that
@@ -583,8 +627,6 @@ def test_value_and_grad_through_the_table_backward(dev, subtype, monkeypatch):
   be.set_pwl(0)
   loss0, g0 = vg(params, 11, 50.0, B)
   used = []
-  monkeypatch.setattr(app, "TABLE_BACKWARD_MIN_SLICE", 256)
-  monkeypatch.setattr(app, "TABLE_BACKWARD_MIN_POINTS", 256)
   orig, orig_nlp, orig_kp = be.pass_vjp, be.neg_logprob_vjp, be.kinetic_potential_vjp
   monkeypatch.setattr(be, "pass_vjp", lambda *a, **k: (used.append(1), orig(*a, **k))[1])
   monkeypatch.setattr(be, "neg_logprob_vjp", lambda *a, **k: (used.append(1), orig_nlp(*a, **k))[1])
@@ -614,8 +656,6 @@ def test_loss_without_gradient_through_the_tables(dev, subtype, monkeypatch):
   be.set_pwl(0)
   loss0 = float(f(params, 11, 50.0, B))
   used = []
-  monkeypatch.setattr(app, "TABLE_BACKWARD_MIN_SLICE", 256)
-  monkeypatch.setattr(app, "TABLE_BACKWARD_MIN_POINTS", 256)
   orig_kp = be.kinetic_potential_vjp
   monkeypatch.setattr(be, "kinetic_potential_vjp", lambda *a, **k: (used.append(a[5] is None), orig_kp(*a, **k))[1])
   be.set_pwl(2)
