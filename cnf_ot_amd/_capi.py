@@ -29,6 +29,15 @@ class CnfConfig(ctypes.Structure):
   ]
 
 
+class CnfFieldGrid(ctypes.Structure):
+  _fields_ = [
+    ("lo_x", ctypes.c_double), ("lo_y", ctypes.c_double), ("step_x", ctypes.c_double), ("step_y", ctypes.c_double),
+    ("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("axis_x", ctypes.c_int32), ("axis_y", ctypes.c_int32),
+    ("sec_axis", ctypes.c_int32), ("n_sec", ctypes.c_int32),
+    ("fixed", ctypes.c_void_p), ("sec", ctypes.c_void_p),
+  ]
+
+
 class CnfLossSpec(ctypes.Structure):
   _fields_ = [
     ("kind", ctypes.c_int32), ("subtype", ctypes.c_int32),
@@ -106,6 +115,12 @@ SYMBOLS = {
                                               ctypes.POINTER(_I64)]),
   "cnf_hopf_cole_2d": (ctypes.c_int, [ctypes.c_int32, ctypes.c_float] + [ctypes.c_double] * 6
                        + [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+  "cnf_eulerian_fields": (ctypes.c_int, [_P, ctypes.POINTER(CnfFieldGrid), _P, _I64, _P, _I64, ctypes.c_float, ctypes.c_float,
+                                        _P, _P, _P, _P, _P]),
+  "cnf_eulerian_fields_f64": (ctypes.c_int, [_P, ctypes.POINTER(CnfFieldGrid), _P, _I64, _P, _I64, ctypes.c_double,
+                                            ctypes.c_double, _P, _P, _P, _P, _P]),
+  "cnf_trajectories": (ctypes.c_int, [_P, _P, _I64, ctypes.c_float, _P, _I64, ctypes.c_float, _P, _P, _P]),
+  "cnf_trajectories_f64": (ctypes.c_int, [_P, _P, _I64, ctypes.c_double, _P, _I64, ctypes.c_double, _P, _P, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),
@@ -121,7 +136,7 @@ _INTERNAL = {
   "cnf_model_read_profile": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
 }
-PATH_NAMES = {0: "none", 1: "mlp1", 2: "mlp2", 3: "mfma", 4: "tables", 5: "loss_mlp", 6: "loss_tables", 7: "f64", 8: "detect", 9: "dpar"}
+PATH_NAMES = {0: "none", 1: "mlp1", 2: "mlp2", 3: "mfma", 4: "tables", 5: "loss_mlp", 6: "loss_tables", 7: "f64", 8: "detect", 9: "dpar", 10: "fields"}
 
 _lib = None
 

@@ -994,6 +994,162 @@ __global__ __launch_bounds__(TILE, 2) void loss_kernel(const LossArgs a) {
 
 
 // ---------------------------------------------------------------------------
+// fields_kernel: the arrays under the reference's figures (cnf_ot/utils.py:598-798, solvers.py:309-493) -- density,
+// log-density, velocity and score at fixed points of data space, and the characteristics through given start points
+// with the velocity along them -- for S times in one launch.  One tile of 256 points of one time per workgroup
+// iteration, one point per lane.  Per (time, point): one data -> base pass (at the slice's own time, or at t0 for
+// trajectories) leaves the base point xi in LDS; the base -> data passes at t (trajectory) and t -+ dt/2 (velocity)
+// start from that copy; the score takes 2 D plain-fp32 data -> base passes at r +- dx/2 e_d (as cnf_logprob_fd: the
+// precise position path would only be cancelled by the difference).  The points of a regular 2-D grid are generated
+// here from (lo, step, nx): index i nx + j is (x_j, y_i), the reference's meshgrid + hstack; several sections along a
+// third axis are averaged in a fixed order inside the thread (plot_proj_density's prob / len(section)).  Each flow
+// direction is instantiated once per use (loops over the passes), as in loss_kernel.
+// LDS: [hdr][P points][U][O][X xi][V result], each D x TILE; float32: + [LO][2^(-i/32) table][float64 `first` table].
+// ---------------------------------------------------------------------------
+template <class R> struct FieldArgsT {
+  ModelArgs m;
+  const R* pts;          // [N, D] explicit points, or null: the grid below
+  const R* t;            // [S]
+  const R* fixed;        // grid: [D] values of the coordinates the grid does not span
+  const R* sec;          // grid: [n_sec] values of coordinate sec_axis, or null
+  R* rho;                // [S, N]     mean over sections of exp(log_prob), or null
+  R* logp;               // [S, N]     or null
+  R* vel;                // [S, N, D]  or null
+  R* score;              // [S, N, D]  or null
+  R* traj;               // [S, N, D]  or null
+  double lo_x, lo_y, step_x, step_y;
+  int64_t N, S;
+  int32_t nx, axis_x, axis_y, sec_axis, n_sec;
+  int32_t fixed_base;    // trajectories: the data -> base pass runs at t0, not at the slice's time
+  int32_t slice_chunk;   // slices one workgroup iteration walks (fixed_base: they share the data -> base pass)
+  R t0, dt, dx;
+  uint32_t div_magic;
+};
+
+template <class T>
+__device__ __forceinline__ void field_copy(typename Lanes<T>::real* dst, const typename Lanes<T>::real* src, int D) {
+  for (int d = 0; d < D; ++d) lds_put(dst, d, TILE, lds_get<T>(src, d, TILE));
+}
+// v - v summed over the coordinates: 0 for a finite point, NaN otherwise (see flow_kernel)
+template <class T>
+__device__ __forceinline__ T field_poison(const typename Lanes<T>::real* col, int D) {
+  T p = (T)0;
+  for (int d = 0; d < D; ++d) { const T v = lds_get<T>(col, d, TILE); p += v - v; }
+  return p;
+}
+
+template <int H, int K, bool FAST, class T>
+__global__ __launch_bounds__(TILE, 2) void fields_kernel(const FieldArgsT<T> a) {
+  static_assert(Lanes<T>::N == 1, "one point per lane");
+  typedef T R;
+  constexpr bool PR = std::is_same<T, float>::value;      // the density pass of the float32 kernel: precise positions
+  extern __shared__ __attribute__((aligned(16))) float lds_raw[];
+  R* lds = reinterpret_cast<R*>(lds_raw);
+  constexpr int HDR = hdr_floats(K);
+  constexpr int TS = TILE;
+  const int D = a.m.D;
+  R* tab = lds;
+  R* P = lds + HDR;
+  R* U = P + D * TS;
+  R* O = U + D * TS;
+  R* X = O + D * TS;
+  R* V = X + D * TS;
+  for (int i = threadIdx.x; i < HDR; i += TILE) tab[i] = table_of<R>(a.m)[i];
+  [[maybe_unused]] double* e2tab = nullptr;
+  [[maybe_unused]] double* tabd = nullptr;
+  [[maybe_unused]] R* LO = nullptr;
+  if constexpr (PR) {                                      // HDR, D * TS are multiples of 4 floats: 8-byte aligned
+    LO = V + D * TS;
+    e2tab = reinterpret_cast<double*>(LO + D * TS);
+    tabd = e2tab + EXP2_N;
+    for (int i = threadIdx.x; i < EXP2_N; i += TILE) e2tab[i] = a.m.e2tab[i];
+    for (int i = threadIdx.x; i < HDR; i += TILE) tabd[i] = a.m.tabd[i];
+  }
+  const int col = threadIdx.x;
+  const bool want_xi = a.vel || a.traj;
+  const bool want_base = want_xi || a.rho || a.logp;
+  const R half_dt = (R)0.5 * a.dt, inv_dt = (R)1 / a.dt, half_dx = (R)0.5 * a.dx, inv_dx = (R)1 / a.dx;
+
+  const int64_t tiles = (a.N + TS - 1) / TS;
+  const int64_t chunks = (a.S + a.slice_chunk - 1) / a.slice_chunk;
+  for (int64_t item = blockIdx.x; item < tiles * chunks; item += gridDim.x) {
+    const int64_t chunk = item / tiles;
+    const int64_t tile_start = (item - chunk * tiles) * TS;
+    const int64_t i = tile_start + col;
+    const int64_t s0 = chunk * a.slice_chunk, s1 = s0 + a.slice_chunk < a.S ? s0 + a.slice_chunk : a.S;
+    __syncthreads();                                       // the previous item's stores are done with U / V
+    if (a.pts) {
+      tile_load<R>(a.pts, P, D, a.div_magic, TS, tile_start, a.N);
+    } else {
+      const int64_t n = i < a.N ? i : 0;
+      const int64_t iy = n / a.nx, ix = n - iy * a.nx;
+      for (int d = 0; d < D; ++d) lds_put(P + col, d, TS, a.fixed[d]);
+      if (a.sec) lds_put(P + col, a.sec_axis, TS, a.sec[0]);
+      // numpy.linspace's own arithmetic: a product and a sum, each rounded (no fused multiply-add)
+      lds_put(P + col, a.axis_x, TS, (R)__dadd_rn(__dmul_rn((double)ix, a.step_x), a.lo_x));
+      lds_put(P + col, a.axis_y, TS, (R)__dadd_rn(__dmul_rn((double)iy, a.step_y), a.lo_y));
+    }
+    __syncthreads();
+
+    T poison = (T)0;
+    for (int64_t s = s0; s < s1; ++s) {
+      const R ts = a.t[s];
+      if (want_base && (s == s0 || !a.fixed_base)) {
+        double rho_acc = 0.0;
+        T lp = (T)0;
+        for (int k = 0; k < a.n_sec; ++k) {
+          field_copy<T>(U + col, P + col, D);
+          if (a.sec) lds_put(U + col, a.sec_axis, TS, a.sec[k]);
+          poison = field_poison<T>(U + col, D);
+          BaseAcc<T> bacc;
+          const T ildj = flow_pass<H, K, true, FAST, T, false, PR>(a.m, tab, U, O, a.fixed_base ? a.t0 : ts, e2tab, tabd,
+                                                                   LO, &bacc);
+          if constexpr (PR) lp = bacc.log_prob(ildj, D) + poison;
+          else lp = base_logprob<T>(lds_col<T>(U + col, TS), D) + ildj + poison;
+          rho_acc += exp((double)lp);
+        }
+        if (want_xi) field_copy<T>(X + col, U + col, D);
+        if (a.logp && i < a.N) a.logp[s * a.N + i] = lp;
+        if (a.rho && i < a.N) a.rho[s * a.N + i] = (R)(rho_acc / (double)a.n_sec);
+      }
+      // base -> data from xi: at t (the trajectory), then at t - dt/2 and t + dt/2 (the velocity)
+      const int n_fwd = (a.traj ? 1 : 0) + (a.vel ? 2 : 0);
+      for (int p = 0; p < n_fwd; ++p) {
+        const int q = p - (a.traj ? 1 : 0);               // -1: trajectory, 0 / 1: the velocity's two ends
+        const R c = q < 0 ? ts : (q == 0 ? ts - half_dt : ts + half_dt);
+        field_copy<T>(U + col, X + col, D);
+        (void)flow_pass<H, K, false, FAST, T>(a.m, tab, U, O, c);
+        if (q == 0) { field_copy<T>(V + col, U + col, D); continue; }
+        for (int d = 0; d < D; ++d) {
+          const T r = lds_get<T>(U + col, d, TS);
+          lds_put(V + col, d, TS, q < 0 ? r + poison : (r - lds_get<T>(V + col, d, TS)) * inv_dt + poison);
+        }
+        __syncthreads();
+        tile_store<R>((q < 0 ? a.traj : a.vel) + s * a.N * D, V, D, a.div_magic, TS, tile_start, a.N);
+        __syncthreads();
+      }
+      if (a.score) {
+        T lp0 = (T)0;
+        for (int e = 0; e < 2 * D; ++e) {
+          const int d = e >> 1, sgn = e & 1;
+          field_copy<T>(U + col, P + col, D);
+          lds_put(U + col, d, TS, lds_get<T>(P + col, d, TS) + (sgn == 0 ? half_dx : -half_dx));
+          const T ps = field_poison<T>(U + col, D);
+          const T ildj = flow_pass<H, K, true, FAST, T>(a.m, tab, U, O, ts);
+          const T lp = base_logprob<T>(lds_col<T>(U + col, TS), D) + ildj;
+          if (sgn == 0) lp0 = lp;
+          else lds_put(V + col, d, TS, (lp0 - lp) * inv_dx + ps);
+        }
+        __syncthreads();
+        tile_store<R>(a.score + s * a.N * D, V, D, a.div_magic, TS, tile_start, a.N);
+        __syncthreads();
+      }
+    }
+  }
+}
+
+
+// ---------------------------------------------------------------------------
 // loss_pwl_kernel: the fused loss terms at dim 2 on the conditioner tables.
 // Same terms and arithmetic as loss_kernel; a sample pair lives in registers,
 // the passes of a term use up to three table sets (conditions t - dt/2,
@@ -2184,4 +2340,113 @@ extern "C" int cnf_sample_logprob_f64(CnfModel* m, const double* noise, const do
                                       double* logp, int64_t B, void* stream) {
   if (!y) return CNF_ERR_INVALID;
   return run_flow_f64(m, false, noise, c, c_block, y, logp, AUX_LOGPROB, B, stream);
+}
+
+// ---- fields and trajectories (fields_kernel) ----------------------------------------------------------------------
+// The configurations the kernel serves: the dims of the fused loss kernel, hardware transcendentals for float32, not
+// periodized; everything else is CNF_ERR_UNSUPPORTED and composed from the flow calls by the caller.
+template <class R>
+static size_t fields_lds_bytes(const CnfModel* m) {
+  const int D = m->cfg.dim;
+  return std::is_same<R, double>::value
+             ? (size_t)(hdr_floats(m->cfg.num_bins) + 5 * D * TILE) * sizeof(double)
+             : (size_t)(hdr_floats(m->cfg.num_bins) + 6 * D * TILE) * sizeof(float) + precise_lds_bytes(m->cfg.num_bins);
+}
+
+// Checked before anything else a call does, the empty call included: one model gives one answer for every N and S.
+template <class R>
+static bool fields_supported(const CnfModel* m) {
+  constexpr bool F64 = std::is_same<R, double>::value;
+  if (m->cfg.periodized || m->cfg.dim > 14 || (!F64 && !m->fast_math)) return false;
+  if (fields_lds_bytes<R>(m) > 160 * 1024) return false;
+#define X(HH, KK) if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) return true;
+  CNF_KERNEL_CONFIGS(X)
+#undef X
+  return false;
+}
+
+template <class R>
+static int launch_fields(CnfModel* m, cnf::FieldArgsT<R>& a, hipStream_t stream) {
+  constexpr bool F64 = std::is_same<R, double>::value;
+  if (!fields_supported<R>(m)) return CNF_ERR_UNSUPPORTED;
+  const size_t lds = fields_lds_bytes<R>(m);
+  if (wait_for_params(m, stream) != CNF_OK) return CNF_ERR_HIP;
+  a.m = model_args(m);
+  a.div_magic = m->div_magic;
+  const int64_t tiles = (a.N + TILE - 1) / TILE;
+  // trajectories: a workgroup that walks all S times runs the data -> base pass once, one per time runs it S times
+  // but S workgroups side by side -- the latter while the tiles alone leave compute units idle
+  a.slice_chunk = (a.fixed_base && tiles >= 2 * (int64_t)m->num_cus) ? (int32_t)(a.S < (1 << 20) ? a.S : (1 << 20)) : 1;
+  const int64_t items = tiles * ((a.S + a.slice_chunk - 1) / a.slice_chunk);
+  const int64_t grid = balanced_grid(items, (int64_t)m->num_cus * 8);
+#define X(HH, KK)                                                                             \
+  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                    \
+    m->last_path = F64 ? CNF_PATH_F64 : CNF_PATH_FIELDS;                                      \
+    if constexpr (F64) CNF_LAUNCH((cnf::fields_kernel<HH, KK, false, double>), grid, lds, stream, a);  \
+    else CNF_LAUNCH((cnf::fields_kernel<HH, KK, true, float>), grid, lds, stream, a);          \
+    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                            \
+  }
+  CNF_KERNEL_CONFIGS(X)
+#undef X
+  return CNF_ERR_UNSUPPORTED;
+}
+
+template <class R>
+static int eulerian_fields_impl(CnfModel* m, const CnfFieldGrid* g, const R* pts, int64_t N, const R* t, int64_t S,
+                                R dt, R dx, R* rho, R* logp, R* vel, R* score, void* stream) {
+  if (!m || !t || N < 0 || S < 0 || (g != nullptr) == (pts != nullptr)) return CNF_ERR_INVALID;
+  if (!rho && !logp && !vel && !score) return CNF_ERR_INVALID;
+  if (!m->params_set) return CNF_ERR_INVALID;
+  if ((vel && !(dt > 0)) || (score && !(dx > 0))) return CNF_ERR_INVALID;
+  const int D = m->cfg.dim;
+  cnf::FieldArgsT<R> a = {};
+  a.n_sec = 1; a.sec_axis = -1;
+  if (g) {
+    if (g->nx < 1 || g->ny < 1 || (int64_t)g->nx * g->ny != N || !g->fixed) return CNF_ERR_INVALID;
+    if (g->axis_x < 0 || g->axis_x >= D || g->axis_y < 0 || g->axis_y >= D || g->axis_x == g->axis_y) return CNF_ERR_INVALID;
+    if (g->n_sec < 1 || (g->sec == nullptr) != (g->sec_axis < 0)) return CNF_ERR_INVALID;
+    if (g->sec && (g->sec_axis >= D || g->sec_axis == g->axis_x || g->sec_axis == g->axis_y)) return CNF_ERR_INVALID;
+    if (!g->sec && g->n_sec != 1) return CNF_ERR_INVALID;
+    if (g->n_sec > 1 && (logp || vel || score)) return CNF_ERR_INVALID;      // a mean over sections: the density alone
+    a.fixed = static_cast<const R*>(g->fixed); a.sec = static_cast<const R*>(g->sec);
+    a.lo_x = g->lo_x; a.lo_y = g->lo_y; a.step_x = g->step_x; a.step_y = g->step_y;
+    a.nx = g->nx; a.axis_x = g->axis_x; a.axis_y = g->axis_y; a.sec_axis = g->sec_axis; a.n_sec = g->n_sec;
+  }
+  if (!fields_supported<R>(m)) return CNF_ERR_UNSUPPORTED;
+  if (N == 0 || S == 0) return CNF_OK;
+  a.pts = pts; a.t = t; a.rho = rho; a.logp = logp; a.vel = vel; a.score = score; a.traj = nullptr;
+  a.N = N; a.S = S; a.fixed_base = 0; a.t0 = 0; a.dt = vel ? dt : (R)1; a.dx = score ? dx : (R)1;
+  return launch_fields<R>(m, a, (hipStream_t)stream);
+}
+
+template <class R>
+static int trajectories_impl(CnfModel* m, const R* r0, int64_t N, R t0, const R* t, int64_t S, R dt, R* traj, R* vel,
+                             void* stream) {
+  if (!m || !r0 || !t || N < 0 || S < 0 || (!traj && !vel)) return CNF_ERR_INVALID;
+  if (!m->params_set || (vel && !(dt > 0))) return CNF_ERR_INVALID;
+  if (!fields_supported<R>(m)) return CNF_ERR_UNSUPPORTED;
+  if (N == 0 || S == 0) return CNF_OK;
+  cnf::FieldArgsT<R> a = {};
+  a.pts = r0; a.t = t; a.traj = traj; a.vel = vel;
+  a.N = N; a.S = S; a.n_sec = 1; a.sec_axis = -1; a.fixed_base = 1; a.t0 = t0; a.dt = vel ? dt : (R)1; a.dx = (R)1;
+  return launch_fields<R>(m, a, (hipStream_t)stream);
+}
+
+extern "C" int cnf_eulerian_fields(CnfModel* m, const CnfFieldGrid* grid, const float* pts, int64_t N, const float* t,
+                                   int64_t S, float dt, float dx, float* rho, float* logp, float* vel, float* score,
+                                   void* stream) {
+  return eulerian_fields_impl<float>(m, grid, pts, N, t, S, dt, dx, rho, logp, vel, score, stream);
+}
+extern "C" int cnf_eulerian_fields_f64(CnfModel* m, const CnfFieldGrid* grid, const double* pts, int64_t N,
+                                       const double* t, int64_t S, double dt, double dx, double* rho, double* logp,
+                                       double* vel, double* score, void* stream) {
+  return eulerian_fields_impl<double>(m, grid, pts, N, t, S, dt, dx, rho, logp, vel, score, stream);
+}
+extern "C" int cnf_trajectories(CnfModel* m, const float* r0, int64_t N, float t0, const float* t, int64_t S, float dt,
+                                float* traj, float* vel, void* stream) {
+  return trajectories_impl<float>(m, r0, N, t0, t, S, dt, traj, vel, stream);
+}
+extern "C" int cnf_trajectories_f64(CnfModel* m, const double* r0, int64_t N, double t0, const double* t, int64_t S,
+                                    double dt, double* traj, double* vel, void* stream) {
+  return trajectories_impl<double>(m, r0, N, t0, t, S, dt, traj, vel, stream);
 }

@@ -613,6 +613,113 @@ class FlowEngine:
                                             score.data_ptr(), B, _stream_ptr(self.device)), "cnf_logprob_fd")
     return score
 
+  def _times(self, t, dtype) -> torch.Tensor:
+    if dtype == torch.float32:
+      return self.slice_conds(t)
+    if not torch.is_tensor(t):
+      t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+    return t.to(device=self.device, dtype=dtype).reshape(-1).contiguous()
+
+  def eulerian_fields(self, t, pts=None, grid=None, *, rho=False, logp=False, vel=False, score=False, dt: float = 0.01,
+                      dx: float = 0.01, dtype=None, out=None):
+    """cnf_eulerian_fields(_f64): fields at fixed points of data space at the times t [S], in one launch.  Points:
+    `pts` [N, D] (its dtype selects float32 / float64), or `grid` = dict(lo=(x, y), step=(x, y), n=(nx, ny),
+    axes=(ax, ay), fixed=[D] values, section=[n_sec] values or None, section_axis) generated in the kernel (dtype=
+    selects the kernels, default float32).  Returns a dict of the requested fields: rho [S, N] (the mean over the
+    sections), logp [S, N], vel [S, N, D], score [S, N, D]; `out`: a dict of preallocated result tensors to fill
+    instead (nothing is allocated then but the small time / fixed / section vectors).  Returns None where the fused
+    kernel does not apply (CNF_ERR_UNSUPPORTED): compose the fields from log_prob / inverse_logdet / forward_logdet /
+    logprob_fd."""
+    if (pts is None) == (grid is None):
+      raise ValueError("eulerian_fields: give either pts or grid")
+    D = self.cfg.dim
+    g = None
+    keep = []
+    if pts is not None:
+      pts = self._points(pts, "eulerian_fields", keep_f64=True)
+      dtype, N = pts.dtype, pts.shape[0]
+    else:
+      dtype = torch.float32 if dtype is None else dtype
+      if dtype not in (torch.float32, torch.float64):
+        raise ValueError("eulerian_fields: dtype must be float32 or float64")
+      (nx, ny), (ax, ay) = (int(v) for v in grid["n"]), (int(v) for v in grid["axes"])
+      if nx < 1 or ny < 1 or not (0 <= ax < D and 0 <= ay < D) or ax == ay:
+        raise ValueError(f"eulerian_fields: a grid of {nx} x {ny} points over axes {(ax, ay)} of a {D}-dim event")
+      N = nx * ny
+      fixed = grid.get("fixed")
+      fixed = torch.zeros(D, dtype=dtype, device=self.device) if fixed is None else \
+        torch.as_tensor(np.asarray(fixed, dtype=np.float64)).to(device=self.device, dtype=dtype).reshape(-1).contiguous()
+      if fixed.numel() != D:
+        raise ValueError(f"eulerian_fields: fixed must have {D} values")
+      sec, sec_axis = grid.get("section"), grid.get("section_axis")
+      if sec is not None:
+        sec = torch.as_tensor(np.asarray(sec, dtype=np.float64)).to(device=self.device, dtype=dtype).reshape(-1).contiguous()
+        if sec_axis is None or not 0 <= int(sec_axis) < D or int(sec_axis) in (ax, ay) or sec.numel() < 1:
+          raise ValueError("eulerian_fields: section needs a section_axis apart from the grid's axes")
+        if sec.numel() > 1 and (logp or vel or score):
+          raise ValueError("eulerian_fields: a mean over several sections is defined for rho alone")
+      keep += [fixed, sec]
+      g = _capi.CnfFieldGrid(float(grid["lo"][0]), float(grid["lo"][1]), float(grid["step"][0]), float(grid["step"][1]),
+                             nx, ny, ax, ay, -1 if sec is None else int(sec_axis), 1 if sec is None else sec.numel(),
+                             fixed.data_ptr(), None if sec is None else sec.data_ptr())
+    if not (rho or logp or vel or score):
+      raise ValueError("eulerian_fields: ask for at least one field")
+    if (vel and not dt > 0) or (score and not dx > 0):
+      raise ValueError("eulerian_fields: dt and dx must be positive")
+    tt = self._times(t, dtype)
+    S = tt.numel()
+    res = {}
+    for name, want, shape in (("rho", rho, (S, N)), ("logp", logp, (S, N)), ("vel", vel, (S, N, D)),
+                              ("score", score, (S, N, D))):
+      if want:
+        res[name] = self._check_out(out[name], shape, "eulerian_fields " + name, dtype) if out is not None else \
+          torch.empty(shape, dtype=dtype, device=self.device)
+    if S == 0 or N == 0:
+      return res
+    fn = self.lib.cnf_eulerian_fields_f64 if dtype == torch.float64 else self.lib.cnf_eulerian_fields
+    ptr = lambda k: res[k].data_ptr() if k in res else None
+    with _OnDevice(self.device):
+      rc = fn(self._h, _capi.ctypes.byref(g) if g is not None else None, pts.data_ptr() if pts is not None else None, N,
+              tt.data_ptr(), S, float(dt), float(dx), ptr("rho"), ptr("logp"), ptr("vel"), ptr("score"),
+              _stream_ptr(self.device))
+    if rc == _capi.CNF_ERR_UNSUPPORTED:
+      return None
+    _capi.check(rc, "cnf_eulerian_fields")
+    return res
+
+  def trajectories(self, r0, t, t0: float = 0.0, *, traj=True, vel=False, dt: float = 0.01, out=None):
+    """cnf_trajectories(_f64): the characteristics r(t) = F(F^-1(r0, t0), t) through the points r0 [N, D] at the
+    times t [S] -- traj [S, N, D] -- and, with vel, the central-difference velocity along them [S, N, D]; float64
+    r0 selects the float64 kernels.  Returns (traj, vel) (None for what was not asked), or None where the fused kernel
+    does not apply (compose from inverse_logdet + forward_logdet).  `out`: (traj, vel) preallocated."""
+    r0 = self._points(r0, "trajectories", keep_f64=True)
+    if not (traj or vel):
+      raise ValueError("trajectories: ask for traj, vel or both")
+    if vel and not dt > 0:
+      raise ValueError("trajectories: dt must be positive")
+    N, D = r0.shape
+    tt = self._times(t, r0.dtype)
+    S = tt.numel()
+    outs = []
+    for k, want in enumerate((traj, vel)):
+      if not want:
+        outs.append(None)
+      elif out is not None:
+        outs.append(self._check_out(out[k], (S, N, D), "trajectories out", r0.dtype))
+      else:
+        outs.append(torch.empty(S, N, D, dtype=r0.dtype, device=self.device))
+    if S == 0 or N == 0:
+      return tuple(outs)
+    fn = self.lib.cnf_trajectories_f64 if r0.dtype == torch.float64 else self.lib.cnf_trajectories
+    with _OnDevice(self.device):
+      rc = fn(self._h, r0.data_ptr(), N, float(t0), tt.data_ptr(), S, float(dt),
+              outs[0].data_ptr() if outs[0] is not None else None, outs[1].data_ptr() if outs[1] is not None else None,
+              _stream_ptr(self.device))
+    if rc == _capi.CNF_ERR_UNSUPPORTED:
+      return None
+    _capi.check(rc, "cnf_trajectories")
+    return tuple(outs)
+
   def logprob_fd_vjp(self, pts, cond, dx: float, gbar, grad, want_pts_bar=True):
     """cnf_logprob_fd_vjp: backward of `logprob_fd` for the output adjoint gbar
     [B, D]: returns pts_bar (or None) and accumulates the parameter gradient

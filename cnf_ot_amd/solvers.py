@@ -2,12 +2,13 @@
 config/mfc.yaml, model construction (:41-56), the loss binding (:58-88),
 `update` = value_and_grad + Adam (:90-97), the training loop (:99-127), and the
 post-training evaluation (:129-308: `evaluate`, printed by `main`), on the HIP
-kernels.  Plots (:119-127, 309-493) are out of scope.  The double-well
+kernels.  The matplotlib calls (:119-127, 309-493) are out of scope; the arrays they
+draw are `figure_data` (`--fields out.npz` saves them).  The double-well
 density-vs-interpolator comparison (:178-188, 222-231) reads data files
 (data/fcn4a*_interp.pkl) that the reference does not ship; here it compares with
 the exact solution computed on the device (rwpo_quadrature_terms).
 
-  python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz]
+  python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
 """
 import argparse
 import sys
@@ -308,6 +309,82 @@ def rwpo_quadrature_terms(model: FlowModel, params: Params, T, beta, a, subtype,
           "ic_mass": float(sol["ic_mass"])}
 
 
+# ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
+# The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
+# by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
+FIGURE_SETTINGS: Dict[Tuple[str, Optional[str], int], Dict[str, Any]] = {
+  ("ot", None, 2): {                                                              # solvers.py:400-416
+    "r": [[-5.0, 0.0], [5.0, 0.0], [0.0, 5.0], [0.0, -5.0], [3.0, 4.0], [3.0, -4.0], [-3.0, 4.0], [-3.0, -4.0]],
+    "domain_range": [-7.5, 7.5, -7.5, 7.5], "times": ("linspace", 5)},
+  ("rwpo", "quadratic", 2): {                                                     # solvers.py:421-432, 452
+    "r": [[-2.0, -2.0], [-2.0, 2.0], [2.0, -2.0], [2.0, 2.0]],
+    "domain_range": [-4.0, 4.0, -4.0, 4.0], "times": ("linspace", 5)},
+  ("rwpo", "double_well", 2): {                                                   # solvers.py:436-452
+    "r": [[-2.0, -2.0], [-2.0, 0.0], [-2.0, 2.0], [0.0, -2.0], [0.0, 2.0], [2.0, -2.0], [2.0, 0.0], [2.0, 2.0]],
+    "domain_range": [-2.0, 2.0, -2.0, 2.0], "times": ("linspace", 5)},
+  ("fp", None, 2): {                                                              # solvers.py:468-484
+    "r": [[-3.0, -3.0], [-3.0, 0.0], [-3.0, 3.0], [0.0, 3.0], [3.0, 3.0], [3.0, 0.0], [3.0, -3.0], [0.0, -3.0]],
+    "domain_range": [-3.0, 3.0, -3.0, 3.0], "times": [0.0, 0.05, 0.1, 0.3, 1.0]},
+  ("fp", "lorenz", 3): {                                                          # solvers.py:330-376
+    "r": [[-1.0, -1.0, 3.0], [-1.0, 1.0, 3.0], [1.0, -1.0, 3.0], [1.0, 1.0, 3.0]],
+    "domain_range": [-2.0, 2.0, -2.0, 2.0], "times": ("linspace", 10),
+    "slice": 3.0,                                                                 # utils.py:665-669: z = 3
+    "section": ("linspace", -5.0, 5.0, 11),                                       # utils.py:714
+    # plot_proj_density's hstack order per direction (utils.py:719-742): (grid axes (X, Y), section axis)
+    "directions": {"x": ((1, 2), 0), "y": ((0, 2), 1), "z": ((0, 1), 2)}},
+}
+FIGURE_GRID = 100        # utils.py:615-616, 662-663, 710
+
+
+def figure_settings(config) -> Optional[Dict[str, Any]]:
+  """The FIGURE_SETTINGS entry of a config with its time array made explicit (t_array: float64 numpy), or None where
+  the reference draws nothing (any other dimension; fp at dim 3 with another field than lorenz)."""
+  g = config["general"]
+  _type, dim = g["type"], g["dim"]
+  if _type == "rwpo":
+    T, sub = config["rwpo"]["T"], config["rwpo"]["pot_type"]
+  elif _type == "fp":
+    T, sub = config["fp"]["T"], config["fp"]["velocity_field_type"]
+  elif _type == "ot":
+    T, sub = 1, config["ot"]["subtype"]                   # solvers.py:81
+  else:
+    raise Exception(f"Unknown problem type: {_type}...")
+  entry = FIGURE_SETTINGS.get((_type, sub, dim), FIGURE_SETTINGS.get((_type, None, dim)))
+  if entry is None:
+    return None
+  out = dict(entry)
+  times = entry["times"]
+  out["t_array"] = np.linspace(0.0, float(T), times[1]) if isinstance(times, tuple) else np.asarray(times, dtype=np.float64)
+  out["r"] = np.asarray(entry["r"], dtype=np.float64)
+  if "section" in entry:
+    out["section"] = np.linspace(*entry["section"][1:3], entry["section"][3])
+  return out
+
+
+def figure_data(config, model: FlowModel, params: Params, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+  """The arrays behind the figures solvers.py:309-493 draws for `config` -- device tensors, nothing drawn:
+    t_array [S], r0 [N, D], domain_range [4]
+    density [S, 100, 100]      exp(log_prob) on the grid (dim 3: the z = `slice` plane), row i = y_i, column j = x_j
+    trajectories [S, N, D]     the characteristics through r0 from t0 = 0
+    proj_density_x / _y / _z [S, 100, 100]   (fp / lorenz at dim 3) the mean over 11 sections along that axis
+  Two fused launches at dim 2, five at dim 3.  Empty dict where the reference draws nothing."""
+  st = figure_settings(config)
+  if st is None:
+    return {}
+  dev = params.flat.device
+  dim = config["general"]["dim"]
+  t_array, dom = st["t_array"], st["domain_range"]
+  out = {"t_array": torch.as_tensor(t_array, device=dev), "r0": torch.as_tensor(st["r"], device=dev).to(dtype),
+         "domain_range": torch.as_tensor(np.asarray(dom, dtype=np.float64), device=dev)}
+  fixed = None if "slice" not in st else [0.0] * (dim - 1) + [st["slice"]]
+  out["density"] = utils.density_on_grid(model, params, t_array, dom, n=FIGURE_GRID, fixed=fixed, dtype=dtype)
+  out["trajectories"] = utils.trajectories(model, params, out["r0"], t_array, t0=0.0, dtype=dtype)
+  for name, (axes, sec_axis) in st.get("directions", {}).items():
+    out["proj_density_" + name] = utils.density_on_grid(model, params, t_array, dom, n=FIGURE_GRID, axes=axes,
+                                                        section=st["section"], section_axis=sec_axis, dtype=dtype)
+  return out
+
+
 _SOLVING = {"rwpo": "Solving regularized Wasserstein proximal in {dim}D with lambda{lam}...",
             "fp": "Solving Fokker-Planck equation in {dim}D with lambda{lam}...",
             "ot": "Solving optimal transport in {dim}D with lambda{lam}..."}
@@ -318,7 +395,8 @@ def _eval_rng(seed, step):
   return ((int(seed) ^ 0x5DEECE66DA3B9F1B) + 0x9E3779B97F4A7C15 * (step + 1)) & 0xFFFFFFFFFFFFFFFF
 
 
-def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None) -> Dict[str, Any]:
+def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
+         fields: Optional[str] = None) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116)."""
   g, tr = config["general"], config["train"]
@@ -343,6 +421,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print(f"loss={float(hist[-1]):.4e}")
   if save:
     np.savez(save, params=params.flat.detach().cpu().numpy())
+  if fields:
+    np.savez(fields, **{k: v.detach().cpu().numpy() for k, v in figure_data(config, model, params).items()})
   res = evaluate(config, model, params, _eval_rng(seed, -1))
   print("Network parameters: {}".format(res["param_count"]))
   if _type == "ot":
@@ -376,9 +456,10 @@ def _parse(argv):
   p.add_argument("--epochs", type=int, default=None, help="training steps (default: train.epochs)")
   p.add_argument("--capture", action="store_true", help="replay each training step as one captured HIP graph")
   p.add_argument("--save", default=None, help="write the trained flat parameters to this .npz file")
+  p.add_argument("--fields", default=None, help="write the arrays behind the reference's figures (figure_data) to this .npz file")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
-  main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save)
+  main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields)

@@ -63,3 +63,216 @@ def calc_score_kinetic_energy(sample_fn, log_prob_fn, params, T: float = 1, beta
   t_array = np.linspace(0.0, T, t_size)
   spec = _spec(_capi.TERM_KINETIC_SCORE, dt=0.01, dx=0.01, coef=1.0 / beta)
   return _mc_energy(model, params, rng, spec, batch_size, t_array, dim, slices_per_launch, shard)
+
+
+# ---- the arrays under the reference's figures (cnf_ot/utils.py:598-798, called from solvers.py:309-493) -------------
+# plot_density_and_trajectory, plot_high_dim_density_and_trajectory, plot_proj_density, plot_velocity_field and
+# plot_traj_and_velocity evaluate the flow one time (and one section) per call and draw the result; the functions below
+# return the tensors and draw nothing.  Each is ONE fused launch over all times (cnf_eulerian_fields /
+# cnf_trajectories); where the fused kernel does not apply (dim > 14, periodized) -- or with fused=False -- the same
+# result is composed from model.apply.log_prob / inverse / forward call by call.  A grid has no input tensor whose
+# dtype could select the float64 kernels the way model.apply does: these functions take dtype= instead.
+
+def field_grid(domain_range, n=100, axes=(0, 1), fixed=None, section=None, section_axis=None):
+  """A regular grid of data space, as the reference's figures lay it out: meshgrid(linspace(x_min, x_max, nx),
+  linspace(y_min, y_max, ny)) over the event axes `axes`, point i * nx + j = (x_j, y_i) (utils.py:615-618); the other
+  coordinates `fixed` (a number or [D] values, default 0: the z = 3 of utils.py:665-669), and optionally `section`
+  values of `section_axis` (plot_proj_density's linspace(-5, 5, 11), utils.py:714).  n: an int or (nx, ny)."""
+  x_min, x_max, y_min, y_max = (float(v) for v in domain_range)
+  nx, ny = (int(n), int(n)) if np.ndim(n) == 0 else (int(n[0]), int(n[1]))
+  if section is not None and section_axis is None:
+    raise ValueError("section needs section_axis")
+  return {"domain_range": (x_min, x_max, y_min, y_max), "n": (nx, ny), "axes": (int(axes[0]), int(axes[1])),
+          "fixed": fixed, "section": None if section is None else np.asarray(section, dtype=np.float64).reshape(-1),
+          "section_axis": None if section_axis is None else int(section_axis), "_tensors": {}}
+
+
+def _fixed_vector(g, dim):
+  f = g["fixed"]
+  f = np.zeros(dim) if f is None else np.asarray(f.cpu() if torch.is_tensor(f) else f, dtype=np.float64)
+  return np.full(dim, float(f)) if f.ndim == 0 else f.reshape(-1)
+
+
+def field_grid_points(g, dim, k=None) -> np.ndarray:
+  """The [ny * nx, dim] float64 points of a `field_grid` (section value k, if it has sections), in the reference's
+  meshgrid + hstack order."""
+  x_min, x_max, y_min, y_max = g["domain_range"]
+  nx, ny = g["n"]
+  X, Y = np.meshgrid(np.linspace(x_min, x_max, nx), np.linspace(y_min, y_max, ny))
+  pts = np.tile(_fixed_vector(g, dim), (nx * ny, 1))
+  pts[:, g["axes"][0]] = X.reshape(-1)
+  pts[:, g["axes"][1]] = Y.reshape(-1)
+  if g["section"] is not None:
+    pts[:, g["section_axis"]] = g["section"][0 if k is None else k]
+  return pts
+
+
+def _engine_grid(g, dim):
+  """`field_grid` -> the grid argument of FlowEngine.eulerian_fields (lo + index * step: numpy.linspace's arithmetic)."""
+  x_min, x_max, y_min, y_max = g["domain_range"]
+  nx, ny = g["n"]
+  step = lambda lo, hi, n: (hi - lo) / (n - 1) if n > 1 else 0.0
+  return {"lo": (x_min, y_min), "step": (step(x_min, x_max, nx), step(y_min, y_max, ny)), "n": (nx, ny),
+          "axes": g["axes"], "fixed": _fixed_vector(g, dim), "section": g["section"], "section_axis": g["section_axis"]}
+
+
+def _grid_tensors(g, dim, dev, dtype):
+  """The point tensors of a `field_grid`, one per section, for the composition: built and uploaded on first use and
+  kept with the grid, so that a grid made once and passed to many calls costs its upload once."""
+  key = (dim, str(dev), dtype)
+  cache = g.setdefault("_tensors", {})
+  if key not in cache:
+    n_sec = 1 if g["section"] is None else len(g["section"])
+    cache[key] = [torch.as_tensor(field_grid_points(g, dim, k)).to(device=dev, dtype=dtype)
+                          for k in range(n_sec)]
+  return cache[key]
+
+
+def _is_grid(p):
+  return isinstance(p, dict) and "domain_range" in p
+
+
+def _times_of(t_array):
+  return np.asarray(t_array.cpu() if torch.is_tensor(t_array) else t_array, dtype=np.float64).reshape(-1)
+
+
+def _cond_of(t, dtype):
+  """A time as model.apply takes it for `dtype` points: the float32 kernels see float32(t)."""
+  return float(np.float32(t)) if dtype == torch.float32 else float(t)
+
+
+def _eulerian(model, params, pts_or_grid, t_array, dtype, fused, **want):
+  be = model.terms_backend(params)
+  dim = model.cfg.dim
+  ts = _times_of(t_array)
+  if _is_grid(pts_or_grid):
+    g, pts = pts_or_grid, None
+    dtype = torch.float32 if dtype is None else dtype
+  else:
+    p = pts_or_grid if torch.is_tensor(pts_or_grid) else torch.as_tensor(np.asarray(pts_or_grid))
+    g, pts = None, be._points(p if dtype is None else p.to(dtype), "fields", keep_f64=True)
+    dtype = pts.dtype
+  if fused:
+    res = be.eulerian_fields(ts, pts=pts, grid=None if g is None else _engine_grid(g, dim), dtype=dtype, **want)
+    if res is not None:
+      return res
+  return _eulerian_composed(model, params, be, g, pts, ts, dtype, **want)
+
+
+def _eulerian_composed(model, params, be, g, pts, ts, dtype, rho=False, logp=False, vel=False, score=False, dt=0.01,
+                       dx=0.01):
+  """The same fields from the public flow calls, one time (and one section) per call -- the reference's own loops."""
+  dim, dev = model.cfg.dim, be.device
+  n_sec = 1 if g is None or g["section"] is None else len(g["section"])
+  if n_sec > 1 and (logp or vel or score):
+    raise ValueError("a mean over several sections is defined for the density alone")
+  secs = [pts] if g is None else _grid_tensors(g, dim, dev, dtype)
+  N = secs[0].shape[0]
+  S = len(ts)
+  res = {}
+  if rho:
+    res["rho"] = torch.empty(S, N, dtype=dtype, device=dev)
+  if logp:
+    res["logp"] = torch.empty(S, N, dtype=dtype, device=dev)
+  if vel:
+    res["vel"] = torch.empty(S, N, dim, dtype=dtype, device=dev)
+  if score:
+    res["score"] = torch.empty(S, N, dim, dtype=dtype, device=dev)
+  for j, t in enumerate(ts):
+    c = _cond_of(t, dtype)
+    if rho or logp:
+      acc = torch.zeros(N, dtype=torch.float64, device=dev)
+      for p in secs:
+        lp = model.apply.log_prob(params, p, cond=c)
+        acc += torch.exp(lp.double())
+      if logp:
+        res["logp"][j] = lp
+      if rho:
+        res["rho"][j] = (acc / n_sec).to(dtype)
+    if vel:
+      xi = model.apply.inverse(params, secs[0], c)
+      h = torch.tensor(0.5 * dt, dtype=dtype)
+      cm, cp = torch.tensor(c, dtype=dtype) - h, torch.tensor(c, dtype=dtype) + h
+      res["vel"][j] = (model.apply.forward(params, xi, float(cp)) - model.apply.forward(params, xi, float(cm))) * \
+        float(torch.tensor(1.0, dtype=dtype) / torch.tensor(dt, dtype=dtype))
+    if score:
+      if dtype == torch.float32:
+        res["score"][j] = be.logprob_fd(secs[0], c, dx)
+      else:
+        for d in range(dim):
+          e = torch.zeros(dim, dtype=dtype, device=dev)
+          e[d] = 0.5 * dx
+          res["score"][j, :, d] = (model.apply.log_prob(params, secs[0] + e, cond=c)
+                                   - model.apply.log_prob(params, secs[0] - e, cond=c)) * (1.0 / dx)
+  return res
+
+
+def eulerian_fields(model, params, pts_or_grid, t_array, rho=False, logp=False, vel=False, score=False, dt: float = 0.01,
+                    dx: float = 0.01, dtype=None, fused=True) -> dict:
+  """Several fields at the same points and times from ONE launch: a dict with the entries asked for -- "rho" and
+  "logp" [S, N], "vel" and "score" [S, N, D] -- as `density_on_grid`, `velocity_field` and `score_field` define them
+  (a monitoring pass during training: density, velocity and score on one grid).  pts_or_grid: [N, D] points or a
+  `field_grid`; with several sections only rho is defined."""
+  model = _model_of(model)
+  if not (rho or logp or vel or score):
+    raise ValueError("eulerian_fields: ask for at least one field")
+  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, rho=rho, logp=logp, vel=vel, score=score, dt=dt,
+                   dx=dx)
+
+
+def density_on_grid(log_prob_fn_or_model, params, t_array, domain_range, n=100, axes=(0, 1), fixed=None, section=None,
+                    section_axis=None, dtype=None, fused=True) -> torch.Tensor:
+  """exp(log_prob) on the reference's grid at every time of t_array, [S, ny, nx] (n = an int: [S, n, n]): the images of
+  plot_density_and_trajectory (utils.py:615-625), of plot_high_dim_density_and_trajectory with fixed=3 (:662-678) and,
+  with `section` values along `section_axis`, the section mean of plot_proj_density (:711-745).  The reference shows
+  the dim-3 images transposed and flipped (`.T[:, ::-1]`): that is drawing, not done here."""
+  model = _model_of(log_prob_fn_or_model)
+  g = field_grid(domain_range, n, axes, fixed, section, section_axis)
+  rho = _eulerian(model, params, g, t_array, dtype, fused, rho=True)["rho"]
+  return rho.reshape(rho.shape[0], g["n"][1], g["n"][0])
+
+
+def velocity_field(model, params, pts_or_grid, t_array, dt: float = 0.01, dtype=None, fused=True) -> torch.Tensor:
+  """The flow's velocity at fixed points of data space, [S, N, D]: v(r, t) = (F(xi, t + dt/2) - F(xi, t - dt/2)) / dt
+  with xi = F^-1(r, t) -- the reference's central difference in t (utils.py:324-336 with general.dt) at the points of
+  plot_traj_and_velocity's quiver grid (:780-794).  pts_or_grid: [N, D] points or a `field_grid`."""
+  model = _model_of(model)
+  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, vel=True, dt=dt)["vel"]
+
+
+def score_field(model, params, pts_or_grid, t_array, dx: float = 0.01, dtype=None, fused=True) -> torch.Tensor:
+  """The score of the flow's density by the reference's central differences in x, [S, N, D]:
+  (log_prob(r + dx/2 e_d) - log_prob(r - dx/2 e_d)) / dx (utils.py:366-381 with general.dx; what plot_velocity_field
+  / plot_score evaluate on their grids)."""
+  model = _model_of(model)
+  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, score=True, dx=dx)["score"]
+
+
+def trajectories(model, params, r_, t_array, t0: float = 0.0, with_velocity: bool = False, dt: float = 0.01, dtype=None,
+                 fused=True):
+  """The characteristics through the points r_ [N, D]: r(t) = F(F^-1(r_, t0), t) for t in t_array, [S, N, D]
+  (utils.py:619,626-627; :670,679-680) -- with_velocity: the pair (trajectories, central-difference velocity along
+  them).  float64 r_ (or dtype=torch.float64) selects the float64 kernels."""
+  model = _model_of(model)
+  be = model.terms_backend(params)
+  r0 = be._points(r_, "trajectories", keep_f64=True)
+  if dtype is not None and r0.dtype != dtype:
+    r0 = r0.to(dtype)
+  dtype = r0.dtype
+  ts = _times_of(t_array)
+  if fused:
+    res = be.trajectories(r0, ts, t0, traj=True, vel=with_velocity, dt=dt)
+    if res is not None:
+      return res if with_velocity else res[0]
+  xi = model.apply.inverse(params, r0, _cond_of(t0, dtype))
+  traj = torch.stack([model.apply.forward(params, xi, _cond_of(t, dtype)) for t in ts]) if len(ts) else \
+    torch.empty(0, *r0.shape, dtype=dtype, device=be.device)
+  if not with_velocity:
+    return traj
+  vel = torch.empty_like(traj)
+  for j, t in enumerate(ts):
+    c = torch.tensor(_cond_of(t, dtype), dtype=dtype)
+    h = torch.tensor(0.5 * dt, dtype=dtype)
+    vel[j] = (model.apply.forward(params, xi, float(c + h)) - model.apply.forward(params, xi, float(c - h))) * \
+      float(torch.tensor(1.0, dtype=dtype) / torch.tensor(dt, dtype=dtype))
+  return traj, vel

@@ -149,7 +149,7 @@ int cnf_model_set_precise(CnfModel *m, int on);
 
 /* Which kernels the most recent compute call on this model ran: 1/2 = MLP flow
  * kernel with one / two samples per lane, 3 = MFMA conditioner, 4 = conditioner
- * tables, 5/6 = fused loss kernel on the MLP / on tables, 7 = float64. */
+ * tables, 5/6 = fused loss kernel on the MLP / on tables, 7 = float64, 10 = the fused field kernel. */
 int cnf_model_last_path(const CnfModel *m);
 
 /* Replaces: model.apply.forward(params, x, c) = flow.bijector.forward, and
@@ -540,6 +540,63 @@ int cnf_hopf_cole_2d(int32_t subtype, float a, double T, double beta,
                      int64_t n2, double *log_rho, double *score, double *w0,
                      double *wT, double *true_value, double *ic_mass,
                      void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- fields and characteristics of a trained flow (cnf_ot/utils.py:598-798 as solvers.py:309-493 calls it) --------
+ * The arrays under the reference's figures, for S times in ONE launch; nothing but the results reaches HBM.
+ *
+ * cnf_eulerian_fields: fields at N fixed points of data space, at each of the times t [S].  Replaces the
+ * log_prob_fn(params, XY, cond=t_i) loops of plot_density_and_trajectory (utils.py:615-625),
+ * plot_high_dim_density_and_trajectory (:662-678) and plot_proj_density (:711-745), and what plot_velocity_field /
+ * plot_traj_and_velocity (:754-797) evaluate on their grids.  The points are either pts [N, D] or -- grid != NULL,
+ * pts == NULL, N = nx * ny -- a regular 2-D grid generated in the kernel: point i * nx + j has coordinate axis_x =
+ * lo_x + j * step_x, coordinate axis_y = lo_y + i * step_y (the reference's meshgrid + hstack; a float64 product and
+ * sum rounded to the kernel's type, numpy.linspace's arithmetic), the other coordinates `fixed` [D] (device; the
+ * entries of the grid's axes are ignored), and coordinate sec_axis = sec [n_sec] (device) when sec != NULL
+ * (sec == NULL: sec_axis = -1, n_sec = 1).  Per (time t_j, point r) one data -> base pass at t_j gives the base
+ * point xi and log_prob.  Outputs, each optional (NULL: not computed, its passes not run), at least one:
+ *   rho   [S, N]     mean over the sections of exp(log_prob) (plot_proj_density's prob / len(section)); the sections
+ *                    are summed in float64 in a fixed order inside one thread: no atomics, calls are bit-identical
+ *   logp  [S, N]     log_prob                                                             (n_sec = 1 only)
+ *   vel   [S, N, D]  (F(xi, t_j + dt/2) - F(xi, t_j - dt/2)) / dt, two base -> data passes on xi  (n_sec = 1 only)
+ *   score [S, N, D]  (log_prob(r + dx/2 e_d) - log_prob(r - dx/2 e_d)) / dx, 2 D data -> base passes in plain fp32
+ *                    as in cnf_logprob_fd                                                  (n_sec = 1 only)
+ * The float32 kernel runs the density pass on the precise position path (cnf_model_set_precise's "on") and needs
+ * hardware transcendentals (the default); the _f64 entry points are the exact mode (all device arrays double,
+ * `fixed` and `sec` included).  A non-finite point gives NaN results for that point only.
+ *
+ * cnf_trajectories: the characteristics r(t) = F(F^-1(r0, t0), t) of plot_density_and_trajectory (utils.py:619,
+ * 626-627) and plot_high_dim_density_and_trajectory (:670, 679-680): one data -> base pass at t0 per point (per time
+ * while the launch is too small to fill the GPU otherwise), then the base -> data passes on the same xi: traj
+ * [S, N, D], and with vel != NULL the central-difference velocity along each trajectory, vel [S, N, D] as above.
+ * traj or vel may be NULL, not both.
+ *
+ * CNF_ERR_UNSUPPORTED (nothing enqueued): dim > 14, periodized, or float32 without hardware transcendentals --
+ * compose the result from cnf_log_prob / cnf_inverse_logdet / cnf_forward_logdet / cnf_logprob_fd.
+ * CNF_ERR_INVALID: both or neither of grid / pts, no output, a grid that does not have N points, axes outside the
+ * event or equal, dt <= 0 with vel, dx <= 0 with score, more than one section with anything but rho. */
+typedef struct CnfFieldGrid {
+  double lo_x, lo_y, step_x, step_y;
+  int32_t nx, ny;
+  int32_t axis_x, axis_y; /* the event axes the grid spans                                  */
+  int32_t sec_axis;       /* the axis of the sections, -1 for none                          */
+  int32_t n_sec;          /* >= 1                                                           */
+  const void *fixed;      /* device [D], of the entry point's real type                     */
+  const void *sec;        /* device [n_sec], of the entry point's real type, or NULL        */
+} CnfFieldGrid;
+int cnf_eulerian_fields(CnfModel *m, const CnfFieldGrid *grid, const float *pts,
+                        int64_t N, const float *t, int64_t S, float dt, float dx,
+                        float *rho, float *logp, float *vel, float *score,
+                        void *stream);
+int cnf_eulerian_fields_f64(CnfModel *m, const CnfFieldGrid *grid, const double *pts,
+                            int64_t N, const double *t, int64_t S, double dt,
+                            double dx, double *rho, double *logp, double *vel,
+                            double *score, void *stream);
+int cnf_trajectories(CnfModel *m, const float *r0, int64_t N, float t0,
+                     const float *t, int64_t S, float dt, float *traj, float *vel,
+                     void *stream);
+int cnf_trajectories_f64(CnfModel *m, const double *r0, int64_t N, double t0,
+                         const double *t, int64_t S, double dt, double *traj,
+                         double *vel, void *stream);
 
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
