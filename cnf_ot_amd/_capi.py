@@ -115,6 +115,12 @@ SYMBOLS = {
                                               ctypes.POINTER(_I64)]),
   "cnf_hopf_cole_2d": (ctypes.c_int, [ctypes.c_int32, ctypes.c_float] + [ctypes.c_double] * 6
                        + [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+  # the same solution at S times in [0, T] (times: a host array): log_rho [S, n2, n1]; score, drift, vel [S, n2, n1, 2]
+  "cnf_hopf_cole_path_workspace": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, _I64, _I64,
+                                                   ctypes.POINTER(_I64)]),
+  "cnf_hopf_cole_path_2d": (ctypes.c_int, [ctypes.c_int32, ctypes.c_float] + [ctypes.c_double] * 6
+                            + [ctypes.POINTER(ctypes.c_double), _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
+                               _I64, _P]),
   "cnf_eulerian_fields": (ctypes.c_int, [_P, ctypes.POINTER(CnfFieldGrid), _P, _I64, _P, _I64, ctypes.c_float, ctypes.c_float,
                                         _P, _P, _P, _P, _P]),
   "cnf_eulerian_fields_f64": (ctypes.c_int, [_P, ctypes.POINTER(CnfFieldGrid), _P, _I64, _P, _I64, ctypes.c_double,

@@ -760,6 +760,57 @@ def _hopf_cole(dev, T, beta, a, subtype, var0, dz, window, y_range, x1, x2, fiel
   return out
 
 
+HOPF_COLE_PATH_FIELDS = ("score", "drift", "vel")
+
+
+def rwpo_reference_path(T, beta, a, subtype, times, x1, x2=None, var0=None, dz=0.01, window=6.0, y_range=4.0,
+                        fields=HOPF_COLE_PATH_FIELDS):
+  """The regularized Wasserstein proximal solution at every time of `times` (0 <= t <= T) on the tensor grid x1 [n1] x
+  x2 [n2], from the quadrature of rwpo_reference_solution (same arguments) in one cnf_hopf_cole_path_2d call: h and the
+  value once, the times in chunks of 8 per launch.  Returns a dict of float64 device tensors: log_rho [S, n2, n1], the
+  requested `fields` [S, n2, n1, 2] among score (grad log rho_t), drift (the optimal control 2 eps grad log eta_t;
+  -grad g at T) and vel (drift - eps score, the velocity the flow's must equal), and the 0-dim true_val and ic_mass.
+  The slab of t = T equals rwpo_reference_solution's log_rho_T, score_T and wT bit for bit; t = 0 is rho0 itself.  A
+  time closer to an endpoint than (1.5 dz)^2 beta / 2, or outside [0, T], is refused (CnfError)."""
+  fields = tuple(fields)
+  bad = [f for f in fields if f not in HOPF_COLE_PATH_FIELDS]
+  if bad:
+    raise ValueError(f"rwpo_reference_path: unknown fields {bad} (known: {HOPF_COLE_PATH_FIELDS})")
+  if subtype not in _capi.POTENTIALS:
+    raise ValueError(f"unknown potential {subtype!r}")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  x1 = torch.as_tensor(x1, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+  x2 = x1 if x2 is None else torch.as_tensor(x2, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+  ts = np.ascontiguousarray(np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64).reshape(-1))
+  n1, n2, S = x1.numel(), x2.numel(), ts.size
+  if n1 == 0 or n2 == 0 or S == 0:
+    raise ValueError("rwpo_reference_path: the output grid or the time array is empty")
+  var0 = rwpo_initial_variance(T, beta) if var0 is None else var0
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_hopf_cole_path_workspace(float(dz), float(window), float(y_range), n1, n2, C.byref(nbytes)),
+              "cnf_hopf_cole_path_workspace")
+  f64 = dict(dtype=torch.float64, device=dev)
+  ws = torch.empty(-(-nbytes.value // 8), **f64)
+  scalars = torch.empty(2, **f64)
+  out = {"log_rho": torch.empty(S, n2, n1, **f64)}
+  for f in fields:
+    out[f] = torch.empty(S, n2, n1, 2, **f64)
+
+  def ptr(name):
+    return out[name].data_ptr() if name in out else None
+
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_hopf_cole_path_2d(_capi.POTENTIALS[subtype], float(a), float(T), float(beta), float(var0),
+                                          float(dz), float(window), float(y_range),
+                                          ts.ctypes.data_as(C.POINTER(C.c_double)), S, x1.data_ptr(), n1, x2.data_ptr(),
+                                          n2, ptr("log_rho"), ptr("score"), ptr("drift"), ptr("vel"), scalars.data_ptr(),
+                                          scalars.data_ptr() + 8, ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+                "cnf_hopf_cole_path_2d")
+  out["true_val"], out["ic_mass"] = scalars[0], scalars[1]
+  return out
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

@@ -309,6 +309,43 @@ def rwpo_quadrature_terms(model: FlowModel, params: Params, T, beta, a, subtype,
           "ic_mass": float(sol["ic_mass"])}
 
 
+def evaluate_path(config, model: FlowModel, params: Params, times=None) -> Dict[str, Any]:
+  """Where along [0, T] the flow departs from the exact rwpo solution (dim 2 only; ValueError otherwise): per time of
+  `times` (default: 9 equally spaced in [0, T]) on evaluate's 100 x 100 grid of [-2, 2]^2 with cell area dA, against
+  applications.rwpo_reference_path, the flow's rho and velocity from one utils.eulerian_fields call.  Lists of floats:
+    times
+    density_sq_err    sum (rho_flow - rho_t)^2                          (density_sq_err's measure, at every time)
+    velocity_rel_err  sum rho_t |v_flow - vel_t|^2 / sum rho_t |vel_t|^2
+    action_exact      1/2 sum rho_t |drift_t|^2 dA                      (the exact solution's kinetic term at t)
+    mass              sum rho_t dA                                      (how much of rho_t the grid holds)"""
+  g = config["general"]
+  if g["type"] != "rwpo" or g["dim"] != 2:
+    raise ValueError(f"evaluate_path: defined for rwpo at dim 2 only, not {g['type']} at dim {g['dim']}")
+  r = config["rwpo"]
+  T = r["T"]
+  ts = np.linspace(0.0, float(T), 9) if times is None else utils._times_of(times)
+  xs, pts = density_eval_points(params.flat.device)
+  dA = float(xs[1] - xs[0]) ** 2
+  ref = applications.rwpo_reference_path(T, r["beta"], r["a"], r["pot_type"], ts, xs, fields=("drift", "vel"))
+  flow = utils.eulerian_fields(model, params, pts, ts, rho=True, vel=True, dt=g["dt"])
+  S = len(ts)
+  rho = torch.exp(ref["log_rho"].reshape(S, -1))
+  vel, drift = ref["vel"].reshape(S, -1, 2), ref["drift"].reshape(S, -1, 2)
+  dv = ((flow["vel"].double() - vel) ** 2).sum(2)
+  return {"times": [float(t) for t in ts],
+          "density_sq_err": ((flow["rho"].double() - rho) ** 2).sum(1).tolist(),
+          "velocity_rel_err": ((rho * dv).sum(1) / (rho * (vel ** 2).sum(2)).sum(1)).tolist(),
+          "action_exact": (0.5 * dA * (rho * (drift ** 2).sum(2)).sum(1)).tolist(),
+          "mass": (dA * rho.sum(1)).tolist()}
+
+
+def print_path_errors(res: Dict[str, Any]) -> None:
+  """evaluate_path's table, one line per time"""
+  print("path errors against the exact solution:  t | density sq err | velocity rel err | exact action | mass on grid")
+  for row in zip(res["times"], res["density_sq_err"], res["velocity_rel_err"], res["action_exact"], res["mass"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f}".format(*row))
+
+
 # ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
 # The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
 # by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
@@ -396,9 +433,10 @@ def _eval_rng(seed, step):
 
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
-         fields: Optional[str] = None) -> Dict[str, Any]:
+         fields: Optional[str] = None, path_errors: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
-  `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116)."""
+  `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
+  evaluate_path's table after them (rwpo at dim 2)."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -446,6 +484,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print("L2 error via Monte-Carlo against the initial condition N(0, (T+1)/2 I): {:.3e}".format(res["l2_mc_ic"]))
     print("variance at T: {} | closed form: {:.4f}".format(" ".join(f"{v:.4f}" for v in res["var_T"]),
                                                           res["var_T_closed_form"]))
+  if path_errors:
+    print_path_errors(evaluate_path(config, model, params))
   return res
 
 
@@ -457,9 +497,12 @@ def _parse(argv):
   p.add_argument("--capture", action="store_true", help="replay each training step as one captured HIP graph")
   p.add_argument("--save", default=None, help="write the trained flat parameters to this .npz file")
   p.add_argument("--fields", default=None, help="write the arrays behind the reference's figures (figure_data) to this .npz file")
+  p.add_argument("--path-errors", action="store_true",
+                 help="print the density and velocity errors against the exact solution at 9 times (rwpo at dim 2)")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
-  main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields)
+  main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
+       path_errors=args.path_errors)

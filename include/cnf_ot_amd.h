@@ -541,6 +541,37 @@ int cnf_hopf_cole_2d(int32_t subtype, float a, double T, double beta,
                      double *wT, double *true_value, double *ic_mass,
                      void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The same solution at every time of times [S] (a HOST array, 0 <= t <= T), from the quantities above: h, the
+ * potential table and the value once per call, then for 0 < t < T, with lg = -g / (2 eps) on the whole z grid:
+ *   log eta_t(x)    = log sum_z exp(lg(z) - |x - z|^2 / (4 eps (T - t))) dz^2 - log(4 pi eps (T - t)),  m_b = mean of z
+ *   log etahat_t(x) = log sum_y exp(log rho0(y) - log h(y) - |x - y|^2 / (4 eps t)) dz^2 + log(T / t),  m_f = mean of y
+ *   log_rho = log eta_t + log etahat_t
+ *   drift   = -(x - m_b) / (T - t)             (2 eps grad log eta_t: the optimal control; -grad g at T)
+ *   score   = -(x - m_b) / (2 eps (T - t)) - (x - m_f) / (2 eps t)
+ *   vel     = drift - eps score                (the current velocity: what a flow's velocity field must equal;
+ *                                               kinetic_with_score_loss_fn penalises |v + score / beta|^2)
+ * The endpoints are exact, with no narrow kernel.  t == T: log_rho, score and vel are cnf_hopf_cole_2d's log_rho,
+ * score and wT bit for bit, drift = -grad g.  t == 0: log_rho = log rho0(x), score = -x / var0, drift =
+ * -(x - m0) / T with w0's m0, vel = drift + eps x / var0.  (cnf_hopf_cole_2d's w0 = drift + eps x is the generator's
+ * form, the velocity at 0 for var0 = 1 only: vel(0) - w0 = eps x (1 / var0 - 1).)
+ * Outputs (device, float64): log_rho [S, n2, n1]; score, drift, vel [S, n2, n1, 2], each optional.  The interior
+ * times are summed 8 per launch from one staged copy of the source table: five launches per 8 times, whatever S;
+ * a time equal to T adds one epilogue launch.  Fixed summation order, no atomics: repeated calls are bit-identical and
+ * a call with S times equals S calls with one.  No allocation, no synchronisation.
+ * CNF_ERR_INVALID (nothing is written): cnf_hopf_cole_2d's cases; n1 or n2 == 0; S < 1 or above 2^19; times NULL; a
+ * time < 0, > T or not finite; an interior time with sqrt(2 eps min(t, T - t)) < 1.5 dz (the narrower Gaussian kernel
+ * has that standard deviation; the uniform rule's aliasing error is about 2 exp(-2 pi^2 sigma^2 / dz^2), 1e-19 at
+ * sigma = 1.5 dz, so from there up the quadrature is exact at float64 level). */
+int cnf_hopf_cole_path_workspace(double dz, double window, double y_range,
+                                 int64_t n1, int64_t n2, int64_t *bytes);
+int cnf_hopf_cole_path_2d(int32_t subtype, float a, double T, double beta,
+                          double var0, double dz, double window, double y_range,
+                          const double *times, int64_t S, const double *x1,
+                          int64_t n1, const double *x2, int64_t n2,
+                          double *log_rho, double *score, double *drift,
+                          double *vel, double *true_value, double *ic_mass,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- fields and characteristics of a trained flow (cnf_ot/utils.py:598-798 as solvers.py:309-493 calls it) --------
  * The arrays under the reference's figures, for S times in ONE launch; nothing but the results reaches HBM.
  *
