@@ -4,6 +4,7 @@
 #include <mutex>
 #include <map>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -128,6 +129,22 @@ static inline bool pwl_term_on_tables(const CnfModel* m, int64_t slice_len, int6
 #define CNF_KERNEL_CONFIGS(X) \
   X(8, 5) X(16, 4) X(16, 5) X(16, 8) X(16, 10) X(32, 5) X(32, 8) X(64, 5)
 #endif
+
+// The list's one expansion.  Calls f(std::integral_constant<int, H>{}, std::integral_constant<int, K>{}) for the
+// compiled shape of cfg and returns its result; CNF_ERR_UNSUPPORTED when the shape is not compiled.  A launch site is
+// a generic lambda that names its kernels with decltype(h)::value and decltype(k)::value.
+template <class F>
+static inline int with_shape(const CnfConfig& cfg, F&& f) {
+#define X(HH, KK)                                      \
+  if (cfg.hidden_size == HH && cfg.num_bins == KK)     \
+    return f(std::integral_constant<int, HH>{}, std::integral_constant<int, KK>{});
+  CNF_KERNEL_CONFIGS(X)
+#undef X
+  return CNF_ERR_UNSUPPORTED;
+}
+static inline bool shape_compiled(const CnfConfig& cfg) {
+  return with_shape(cfg, [](auto, auto) { return CNF_OK; }) == CNF_OK;
+}
 
 // Dynamic LDS above the 64 KB default needs an explicit opt-in per kernel; the
 // CU has 160 KB.  Returns false if the request cannot be met.

@@ -1386,11 +1386,7 @@ static int config_valid(const CnfConfig* c) {
 }
 
 extern "C" int cnf_config_supported(const CnfConfig* c) {
-  if (!config_valid(c)) return 0;
-#define X(HH, KK) if (c->hidden_size == HH && c->num_bins == KK) return 1;
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return 0;
+  return config_valid(c) && shape_compiled(*c) ? 1 : 0;
 }
 
 extern "C" void cnf_config_default(CnfConfig* c, int32_t dim) {
@@ -1546,11 +1542,12 @@ extern "C" int cnf_model_read_profile(CnfModel* m, double* flow_ms, double* buil
 }
 
 // profiling helpers: a record is opened before the (optional) build kernel and closed after the flow kernel
+// (samples < 0: a launch that is not recorded)
 struct ProfScope {
   CnfModel* m; hipStream_t s; CnfModel::ProfRec r; bool on;
   ProfScope(CnfModel* m_, hipStream_t s_, bool with_build, int64_t samples, int path) : m(m_), s(s_), on(false) {
     r.e0 = r.e1 = r.e2 = nullptr; r.samples = samples; r.path = path;
-    if (!m->profiling || m->prof.size() >= 4096) return;
+    if (!m->profiling || samples < 0 || m->prof.size() >= 4096) return;
     if (hipEventCreate(&r.e1) != hipSuccess || hipEventCreate(&r.e2) != hipSuccess) return;
     if (with_build) { if (hipEventCreate(&r.e0) != hipSuccess) return; (void)hipEventRecord(r.e0, s); }
     else (void)hipEventRecord(r.e1, s);
@@ -1648,11 +1645,21 @@ static int samples_per_lane(const CnfModel* m, int64_t B) {
   return (m->fast_math && B >= (int64_t)m->num_cus * 4 * 64 * 2) ? 2 : 1;
 }
 
-#define CNF_LAUNCH(KERNEL, GRID, LDS, STREAM, ARGS)                          \
-  do {                                                                     \
-    if (!ensure_lds(KERNEL, LDS)) return CNF_ERR_UNSUPPORTED;              \
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)(GRID)), dim3(TILE), LDS, STREAM, ARGS); \
-  } while (0)
+// The one tail of every kernel family's launch: report `path` (cnf_model_last_path) -- unless the launch is gated on
+// the device: its call has reported CNF_PATH_DETECT --, opt in to the LDS, launch `threads` per workgroup and map the
+// launch error.  prof_samples >= 0: a kernel of the flow entry points, timed under cnf_model_set_profiling.
+template <class K, class A>
+static int launch(CnfModel* m, K kernel, int64_t grid, int threads, size_t lds, hipStream_t stream, const A& a, int path,
+                  bool gated = false, int64_t prof_samples = -1) {
+  if (!gated) m->last_path = path;
+  if (!ensure_lds(kernel, lds)) return CNF_ERR_UNSUPPORTED;
+  ProfScope ps(m, stream, false, prof_samples, path);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
+  ps.done();
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
+typedef void (*FlowKernel)(const FlowArgs);
 
 // flow_dpar_kernel: D >= 3, base -> data, packed-VALU conditioner, hardware transcendentals.  Chosen (use_dpar
 // = 1) while the one-sample-per-lane kernel would leave the chip under-filled.
@@ -1671,22 +1678,37 @@ static int launch_flow_dpar(CnfModel* m, const FlowArgs& a, hipStream_t stream) 
   int64_t grid = (a.B + ts - 1) / ts;
   const int64_t cap = (int64_t)m->num_cus * 8;
   if (grid > cap) grid = cap;
-#define X(HH, KK)                                                                             \
-  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                    \
-    if (!a.gate) m->last_path = CNF_PATH_DPAR;                                                \
-    ProfScope ps(m, stream, false, a.B, CNF_PATH_DPAR);                                       \
-    if (spl == 2) hipLaunchKernelGGL((flow_dpar_kernel<HH, KK, true, v2f>), dim3((unsigned)grid), dim3(64 * nw), lds, stream, a);   \
-    else hipLaunchKernelGGL((flow_dpar_kernel<HH, KK, true, float>), dim3((unsigned)grid), dim3(64 * nw), lds, stream, a);          \
-    ps.done();                                                                                \
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                            \
-  }
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return CNF_ERR_UNSUPPORTED;
+  return with_shape(m->cfg, [&](auto h, auto k) -> int {
+    constexpr int H = decltype(h)::value, K = decltype(k)::value;
+    const FlowKernel kern = spl == 2 ? flow_dpar_kernel<H, K, true, v2f> : flow_dpar_kernel<H, K, true, float>;
+    return launch(m, kern, grid, 64 * nw, lds, stream, a, CNF_PATH_DPAR, a.gate != nullptr, a.B);
+  });
 }
 
 // LDS of the precise position path beyond the tile: the 2^(-i/32) table and the float64 `first` table
 static size_t precise_lds_bytes(int K) { return sizeof(double) * (size_t)(cnf::EXP2_N + hdr_floats(K)); }
+
+// flow_kernel's instantiation for a launch, each selection written once.  `precise` is honoured for TO_BASE alone:
+// the precise position path exists for the data -> base direction.
+// The packed-VALU conditioner of shape (H, K):
+template <int H, int K, bool TO_BASE, bool PRECISE = false>
+static FlowKernel flow_kernel_of(bool precise, bool fast, int spl) {
+  if constexpr (TO_BASE && !PRECISE)
+    if (precise) return flow_kernel_of<H, K, true, true>(true, fast, spl);
+  if (!fast) return flow_kernel<H, K, TO_BASE, false, float, false, PRECISE>;
+  return spl == 2 ? flow_kernel<H, K, TO_BASE, true, v2f, false, PRECISE>
+                  : flow_kernel<H, K, TO_BASE, true, float, false, PRECISE>;
+}
+// The MFMA conditioner (H = 16, K = 5, hardware transcendentals).  d2: dim 2 at one sample per lane, the reference's
+// per-batch call pattern, has its own instantiation.
+template <bool TO_BASE, bool PRECISE = false>
+static FlowKernel flow_mfma_kernel_of(bool precise, int spl, bool d2) {
+  if constexpr (TO_BASE && !PRECISE)
+    if (precise) return flow_mfma_kernel_of<true, true>(true, spl, d2);
+  if (spl == 2) return flow_kernel<16, 5, TO_BASE, true, v2f, true, PRECISE>;
+  return d2 ? flow_kernel<16, 5, TO_BASE, true, float, true, PRECISE, false, 2>
+            : flow_kernel<16, 5, TO_BASE, true, float, true, PRECISE>;
+}
 
 template <bool TO_BASE>
 static int launch_flow(CnfModel* m, const FlowArgs& a, int spl, hipStream_t stream) {
@@ -1695,66 +1717,35 @@ static int launch_flow(CnfModel* m, const FlowArgs& a, int spl, hipStream_t stre
   int64_t grid = n_tiles;
   const int64_t cap = (int64_t)m->num_cus * 8;
   if (grid > cap) grid = cap;
-  constexpr bool PR = TO_BASE;                 // the precise position path exists for the data -> base direction
+  const bool gated = a.gate != nullptr;
   if (m->cfg.periodized) {
     // RQSFlow(periodized=True): one sample per lane, hardware transcendentals, plain fp32 positions; sin / cos of
     // the conditioner inputs by ocml.  (fast_math off: the float64 entry points are the exact mode.)
     if (!m->fast_math) return CNF_ERR_UNSUPPORTED;
     const int64_t tiles1 = (a.B + TILE - 1) / TILE;
-    const int64_t grid1 = tiles1 < (int64_t)m->num_cus * 8 ? tiles1 : (int64_t)m->num_cus * 8;
+    const int64_t grid1 = tiles1 < cap ? tiles1 : cap;
     const size_t lds1 = (size_t)(hdr_floats(m->cfg.num_bins) + 2 * a.m.D * TILE) * sizeof(float);
-    if (!a.gate) m->last_path = CNF_PATH_MLP1;
-#define X(HH, KK)                                                                             \
-    if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                  \
-      CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, true, float, false, false, true>), grid1, lds1, stream, a);  \
-      return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                          \
-    }
-    CNF_KERNEL_CONFIGS(X)
-#undef X
-    return CNF_ERR_UNSUPPORTED;
+    return with_shape(m->cfg, [&](auto h, auto k) -> int {
+      constexpr int H = decltype(h)::value, K = decltype(k)::value;
+      return launch(m, flow_kernel<H, K, TO_BASE, true, float, false, false, true>, grid1, TILE, lds1, stream, a,
+                    CNF_PATH_MLP1, gated);
+    });
   }
-  const bool precise = PR && m->precise;
+  const bool precise = TO_BASE && m->precise;
   const size_t lds = (size_t)(hdr_floats(m->cfg.num_bins) + 2 * a.m.D * ts) * sizeof(float) +
                      (precise ? precise_lds_bytes(m->cfg.num_bins) + sizeof(float) * a.m.D * ts : 0);
   // launches of up to 4 waves of single-lane work per SIMD: the MFMA conditioner, one sample per lane (measured
   // crossover with the packed-VALU kernel, dim 2 and dim 10: profiles/r02_experiments/exp_latency.log)
   const bool small = a.B <= (int64_t)m->num_cus * 4 * 64 * CNF_MFMA_SMALL_WAVES;
   if (m->fast_math && (m->use_mfma == 1 || (m->use_mfma == 2 && small)) && m->mfma_off > 0 &&
-      m->cfg.hidden_size == 16 && m->cfg.num_bins == 5) {
-    if (!a.gate) m->last_path = CNF_PATH_MFMA;
-    ProfScope ps(m, stream, false, a.B, CNF_PATH_MFMA);
-    const bool d2 = m->cfg.dim == 2 && spl == 1;        // the reference's per-batch call pattern: its own instantiation
-    if (precise) {
-      if (spl == 2) CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, v2f, true, PR>), grid, lds, stream, a);
-      else if (d2) CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, float, true, PR, false, 2>), grid, lds, stream, a);
-      else CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, float, true, PR>), grid, lds, stream, a);
-    } else {
-      if (spl == 2) CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, v2f, true>), grid, lds, stream, a);
-      else if (d2) CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, float, true, false, false, 2>), grid, lds, stream, a);
-      else CNF_LAUNCH((flow_kernel<16, 5, TO_BASE, true, float, true>), grid, lds, stream, a);
-    }
-    ps.done();
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-  }
-  if (!a.gate) m->last_path = spl == 2 ? CNF_PATH_MLP2 : CNF_PATH_MLP1;
-  ProfScope ps(m, stream, false, a.B, spl == 2 ? CNF_PATH_MLP2 : CNF_PATH_MLP1);
-#define X(HH, KK)                                                                             \
-  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                    \
-    if (precise) {                                                                            \
-      if (!m->fast_math) CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, false, float, false, PR>), grid, lds, stream, a);  \
-      else if (spl == 2) CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, true, v2f, false, PR>), grid, lds, stream, a);     \
-      else CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, true, float, false, PR>), grid, lds, stream, a);                 \
-    } else {                                                                                  \
-      if (!m->fast_math) CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, false, float>), grid, lds, stream, a);      \
-      else if (spl == 2) CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, true, v2f>), grid, lds, stream, a);         \
-      else CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, true, float>), grid, lds, stream, a);                     \
-    }                                                                                         \
-    ps.done();                                                                                \
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                            \
-  }
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return CNF_ERR_UNSUPPORTED;
+      m->cfg.hidden_size == 16 && m->cfg.num_bins == 5)
+    return launch(m, flow_mfma_kernel_of<TO_BASE>(precise, spl, m->cfg.dim == 2 && spl == 1), grid, TILE, lds, stream, a,
+                  CNF_PATH_MFMA, gated, a.B);
+  return with_shape(m->cfg, [&](auto h, auto k) -> int {
+    constexpr int H = decltype(h)::value, K = decltype(k)::value;
+    return launch(m, flow_kernel_of<H, K, TO_BASE>(precise, m->fast_math != 0, spl), grid, TILE, lds, stream, a,
+                  spl == 2 ? CNF_PATH_MLP2 : CNF_PATH_MLP1, gated, a.B);
+  });
 }
 
 // This stream's table workspace (cnf_model_reserve).  Lookup only: the compute entry points never allocate,
@@ -1814,14 +1805,66 @@ extern "C" int64_t cnf_model_reserved(CnfModel* m, void* stream) {
   return sets;
 }
 
-static const int64_t PWL_MAX_SLICES = 2048;      // slices per build + flow kernel pair
-
 static_assert(cnf::PWL_H == 16, "pwl_network (cnf_common.h) states the tables' network");
 
 extern "C" int cnf_model_has_tables(const CnfModel* m) { return m && pwl_network(m->cfg) ? 1 : 0; }
 
 extern "C" int cnf_model_term_on_tables(const CnfModel* m, int64_t slice_len, int64_t n_points, int with_grad) {
   return m && pwl_term_on_tables(m, slice_len, n_points, with_grad != 0) ? 1 : 0;
+}
+
+// How a call on the tables walks its slices: `chunk` slices per build + kernel pair, `tps` tiles per slice, on the
+// stream's workspace `tables`.
+struct SlicePlan { int64_t tps, chunk; float* tables; };
+
+// The plan for n_slices slices of slice_len points in tiles of `tile` points, each slice taking sets_per_slice table
+// sets; CNF_ERR_UNSUPPORTED when the call does not qualify (the caller then runs the MLP kernel).  No HIP call.
+static int slice_plan(CnfModel* m, hipStream_t stream, int64_t slice_len, int64_t n_slices, int64_t tile,
+                      int sets_per_slice, SlicePlan* p) {
+  const int64_t PWL_MAX_SLICES = 2048;      // slices per build + kernel pair
+  p->tps = (slice_len + tile - 1) / tile;
+  const int64_t total = n_slices * p->tps;
+  if (total > (1 << 30)) return CNF_ERR_UNSUPPORTED;
+  // the tables cost one small kernel per launch: worth it once every CU has a tile,
+  // and only while a slice is long enough to amortise building its tables
+  // (crossover with the MLP kernel: B / 26 G/s = 20 us of table building + B / 62 G/s  ->  B ~ 0.9 M samples)
+  if (m->use_pwl == 1 && (total < 2 * (int64_t)m->num_cus || slice_len < 4 * tile)) return CNF_ERR_UNSUPPORTED;
+  // at most PWL_MAX_SLICES slices per kernel pair: the workspace stays bounded (2 048 x L x 48 KB) however many
+  // slices a call has
+  p->chunk = n_slices < PWL_MAX_SLICES ? n_slices : PWL_MAX_SLICES;
+  // the stream's reservation decides: none (or one too small to keep every CU busy) -> the MLP kernel
+  int64_t sets = 0;
+  pwl_workspace(m, stream, &p->tables, &sets);
+  if (sets / sets_per_slice < p->chunk) p->chunk = sets / sets_per_slice;
+  if (p->chunk < 1) return CNF_ERR_UNSUPPORTED;
+  if (m->use_pwl == 1 && p->chunk < n_slices && p->chunk * p->tps < (int64_t)m->num_cus) return CNF_ERR_UNSUPPORTED;
+  return CNF_OK;
+}
+
+// Enqueues the tables of ns slices, conditions c[0 .. ns) + offset, into `tables`
+static void build_tables(const CnfModel* m, hipStream_t stream, const float* c, float offset, int64_t ns,
+                         float* tables) {
+  const int L = m->cfg.num_layers;
+  hipLaunchKernelGGL(cnf::pwl_build_kernel, dim3((unsigned)(ns * L)), dim3(512), 0, stream,
+                     (const float*)(m->prep + cnf::hdr_floats(5)), m->per_layer, c, offset, L, m->scd.sp_offset, tables);
+}
+
+typedef void (*PwlKernel)(const cnf::PwlArgs);
+
+// flow_pwl_kernel's instantiation for a launch.  full: every row of the L tables is in LDS, else the first PWL_LROWS
+// rows; l2: L = 2 (every configuration of the reference), full, has its own instantiation with the layer loop unrolled
+template <bool TO_BASE, bool PRECISE, bool SEEDED>
+static PwlKernel flow_pwl_kernel_of(bool full, bool l2) {
+  constexpr int ALL = cnf::PWL_NPIECE, WIN = cnf::PWL_LROWS;
+  if (l2) return cnf::flow_pwl_kernel<5, TO_BASE, true, PRECISE, ALL, 2, SEEDED>;
+  return full ? cnf::flow_pwl_kernel<5, TO_BASE, true, PRECISE, ALL, 0, SEEDED>
+              : cnf::flow_pwl_kernel<5, TO_BASE, true, PRECISE, WIN, 0, SEEDED>;
+}
+// precise: the precise position path (data -> base); seeded: base noise drawn in the kernel (base -> data)
+static PwlKernel flow_pwl_kernel_of(bool to_base, bool precise, bool seeded, bool full, bool l2) {
+  if (precise) return flow_pwl_kernel_of<true, true, false>(full, l2);
+  if (to_base) return flow_pwl_kernel_of<true, false, false>(full, l2);
+  return seeded ? flow_pwl_kernel_of<false, false, true>(full, l2) : flow_pwl_kernel_of<false, false, false>(full, l2);
 }
 
 // The piecewise-linear path (cnf_pwl.h): dim 2, H = 16, K = 5, two MLP layers, a condition that is
@@ -1862,41 +1905,14 @@ static int run_flow_pwl(CnfModel* m, bool to_base, const float* in, const float*
   // (profiles/r02_experiments: other workgroup sizes and LDS requests -- 2 / 4 / 6 waves per SIMD -- were all slower)
   const int pwl_threads = cnf::PWL_MAX_THREADS;
   const size_t pwl_min_lds = 82 * 1024;
-  const int64_t PWL_TS = 2 * pwl_threads;
-  const int64_t tps = (slice_len + PWL_TS - 1) / PWL_TS;
-  const int64_t total = n_slices * tps;
-  if (total > (1 << 30)) return CNF_ERR_UNSUPPORTED;
-  // the tables cost one small kernel per launch: worth it once every CU has a tile,
-  // and only while a slice is long enough to amortise building its tables
-  // (crossover with the MLP kernel: B / 26 G/s = 20 us of table building + B / 62 G/s  ->  B ~ 0.9 M samples)
-  if (m->use_pwl == 1 && (total < 2 * (int64_t)m->num_cus || slice_len < 4 * PWL_TS)) return CNF_ERR_UNSUPPORTED;
+  SlicePlan plan;
+  if (slice_plan(m, stream, slice_len, n_slices, 2 * pwl_threads, 1, &plan) != CNF_OK) return CNF_ERR_UNSUPPORTED;
+  const int64_t tps = plan.tps, chunk = plan.chunk;
+  float* tables = plan.tables;
+  if (built && (chunk < n_slices || built != tables)) return CNF_ERR_UNSUPPORTED;
   if (pwl_min_lds > lds) lds = pwl_min_lds;
-  typedef void (*PwlKernel)(const cnf::PwlArgs);
-  constexpr int ALL = cnf::PWL_NPIECE, WIN = cnf::PWL_LROWS;
-  // L = 2 (every configuration of the reference) has its own instantiation with the layer loop unrolled
-  const bool l2 = full && L == 2;
-  const PwlKernel kern =
-      precise ? (l2 ? (PwlKernel)cnf::flow_pwl_kernel<5, true, true, true, ALL, 2>
-                    : full ? (PwlKernel)cnf::flow_pwl_kernel<5, true, true, true, ALL> : (PwlKernel)cnf::flow_pwl_kernel<5, true, true, true, WIN>)
-      : to_base ? (l2 ? (PwlKernel)cnf::flow_pwl_kernel<5, true, true, false, ALL, 2>
-                      : full ? (PwlKernel)cnf::flow_pwl_kernel<5, true, true, false, ALL> : (PwlKernel)cnf::flow_pwl_kernel<5, true, true, false, WIN>)
-      : noise ? (l2 ? (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, ALL, 2, true>          // (base noise drawn in the kernel)
-                    : full ? (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, ALL, 0, true> : (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, WIN, 0, true>)
-                : (l2 ? (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, ALL, 2>
-                      : full ? (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, ALL> : (PwlKernel)cnf::flow_pwl_kernel<5, false, true, false, WIN>);
+  const PwlKernel kern = flow_pwl_kernel_of(to_base, precise, noise != nullptr, full, full && L == 2);
   if (!ensure_lds(kern, lds)) return CNF_ERR_UNSUPPORTED;
-  // at most PWL_MAX_SLICES slices per kernel pair: the workspace stays bounded (2 048 x L x 48 KB) however many
-  // slices a call has
-  int64_t chunk = n_slices < PWL_MAX_SLICES ? n_slices : PWL_MAX_SLICES;
-  float* tables = nullptr;
-  {
-    // the stream's reservation decides: none (or one too small to keep every CU busy) -> the MLP kernel
-    int64_t sets = 0;
-    pwl_workspace(m, stream, &tables, &sets);
-    if (sets < chunk) chunk = sets;
-    if (chunk < 1 || (built && (chunk < n_slices || built != tables))) return CNF_ERR_UNSUPPORTED;
-    if (m->use_pwl == 1 && chunk < n_slices && chunk * tps < (int64_t)m->num_cus) return CNF_ERR_UNSUPPORTED;
-  }
   uint32_t* flag = nullptr;
   uint32_t epoch = 0;
   if (detect) {
@@ -1907,15 +1923,12 @@ static int run_flow_pwl(CnfModel* m, bool to_base, const float* in, const float*
     hipLaunchKernelGGL(cnf::cond_uniform_kernel, dim3((unsigned)g), dim3(256), 0, stream, c, B, flag, epoch);
     *gate = flag; *gate_epoch = epoch;
   }
-  const double sp_offset = log(exp(1.0 - (double)m->cfg.min_knot_slope) - 1.0);
   m->last_path = detect ? CNF_PATH_DETECT : CNF_PATH_TABLES;
   for (int64_t s0 = 0; s0 < n_slices; s0 += chunk) {
     const int64_t ns = n_slices - s0 < chunk ? n_slices - s0 : chunk;
     const int64_t first = s0 * slice_len;
     ProfScope ps(m, stream, true, (B - first) < ns * slice_len ? (B - first) : ns * slice_len, CNF_PATH_TABLES);
-    if (!built)
-      hipLaunchKernelGGL(cnf::pwl_build_kernel, dim3((unsigned)(ns * L)), dim3(512), 0, stream,
-                         (const float*)(m->prep + cnf::hdr_floats(5)), m->per_layer, c + s0, 0.0f, L, sp_offset, tables);
+    if (!built) build_tables(m, stream, c + s0, 0.0f, ns, tables);
     ps.built();
     cnf::PwlArgs a;
     a.m = model_args(m);
@@ -1945,16 +1958,33 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
                       nullptr, tables, true);
 }
 
+// (one chunk of a term that pwl_term_on_tables has put on the tables: the reservation is the one question left)
 int cnf_internal_build_tables(CnfModel* m, hipStream_t stream, const float* c, int64_t n, float** tables) {
   if (!pwl_config_ok(m) || n < 1) return CNF_ERR_UNSUPPORTED;
   int64_t sets = 0;
   pwl_workspace(m, stream, tables, &sets);
   if (sets < n) return CNF_ERR_UNSUPPORTED;
-  const int L = m->cfg.num_layers;
-  const double sp_offset = log(exp(1.0 - (double)m->cfg.min_knot_slope) - 1.0);
-  hipLaunchKernelGGL(cnf::pwl_build_kernel, dim3((unsigned)(n * L)), dim3(512), 0, stream,
-                     (const float*)(m->prep + cnf::hdr_floats(5)), m->per_layer, c, 0.0f, L, sp_offset, *tables);
+  build_tables(m, stream, c, 0.0f, n, *tables);
   return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
+// The arguments of a flow_kernel launch over B points in tiles of tile_samples: no gate, no finite differences,
+// points read from `in`; a caller sets what differs.
+template <class R>
+static FlowArgsT<R> flow_args(const CnfModel* m, const R* in, const R* c, int64_t c_block, R* out, R* aux, int aux_mode,
+                              int64_t B, int64_t tile_samples) {
+  FlowArgsT<R> a;
+  a.m = model_args(m);
+  a.in = in; a.c = c; a.out = out; a.aux = aux;
+  a.B = B; a.c_block = c_block; a.aux_mode = aux_mode; a.div_magic = m->div_magic;
+  if (c_block >= B) a.c_mode = C_SINGLE;
+  else if (c_block == 1) a.c_mode = C_PER_SAMPLE;
+  else if (c_block % tile_samples == 0) a.c_mode = C_TILE_UNIFORM;
+  else a.c_mode = C_GENERIC;
+  a.gate = nullptr; a.gate_epoch = 0; a.gate_want = 0;
+  a.fd2 = 0; a.fd_h = 0; a.fd_inv_dx = 0;
+  a.seed = 0; a.first_sample = 0; a.slice_stride = 0;
+  return a;
 }
 
 static int run_flow(CnfModel* m, bool to_base, const float* in, const float* c, int64_t c_block,
@@ -1978,23 +2008,13 @@ static int run_flow(CnfModel* m, bool to_base, const float* in, const float* c, 
     const int r = run_flow_pwl(m, to_base, in, c, c_block, out, aux, aux_mode, B, (hipStream_t)stream, false, nullptr, nullptr, noise);
     if (r != CNF_ERR_UNSUPPORTED) return r;
   }
-  FlowArgs a;
-  a.m = model_args(m);
-  a.in = in; a.c = c; a.out = out; a.aux = aux;
-  a.B = B; a.c_block = c_block;
-  a.gate = gate; a.gate_epoch = gate_epoch; a.gate_want = 1;     // MLP kernel: only if a difference was stamped
-  a.fd2 = 0; a.fd_h = 0.f; a.fd_inv_dx = 0.f;
-  a.seed = noise ? noise->seed : 0; a.first_sample = noise ? noise->first_sample : 0; a.slice_stride = noise ? noise->slice_stride : 0;
-  a.aux_mode = aux_mode;
-  a.div_magic = m->div_magic;
   int spl = m->fast_math ? samples_per_lane(m, B) : 1;
   // two samples per lane double the LDS tile: fall back when it would not fit
-  if (spl == 2 && (size_t)(hdr_floats(m->cfg.num_bins) + 3 * a.m.D * TILE * 2) * sizeof(float) +
+  if (spl == 2 && (size_t)(hdr_floats(m->cfg.num_bins) + 3 * m->cfg.dim * TILE * 2) * sizeof(float) +
                       precise_lds_bytes(m->cfg.num_bins) > 160 * 1024) spl = 1;
-  if (c_block >= B) a.c_mode = C_SINGLE;
-  else if (c_block == 1) a.c_mode = C_PER_SAMPLE;
-  else if (c_block % (TILE * spl) == 0) a.c_mode = C_TILE_UNIFORM;
-  else a.c_mode = C_GENERIC;
+  FlowArgs a = flow_args<float>(m, in, c, c_block, out, aux, aux_mode, B, TILE * spl);
+  a.gate = gate; a.gate_epoch = gate_epoch; a.gate_want = 1;     // MLP kernel: only if a difference was stamped
+  if (noise) { a.seed = noise->seed; a.first_sample = noise->first_sample; a.slice_stride = noise->slice_stride; }
   if (!to_base) {
     const int r = launch_flow_dpar(m, a, (hipStream_t)stream);
     if (r != CNF_ERR_UNSUPPORTED) return r;
@@ -2053,19 +2073,12 @@ extern "C" int cnf_logprob_fd(CnfModel* m, const float* pts, const float* c, int
   const int D = m->cfg.dim;
   if (B * 2 * D >= ((int64_t)1 << 40)) return CNF_ERR_INVALID;
   if (wait_for_params(m, (hipStream_t)stream) != CNF_OK) return CNF_ERR_HIP;
-  FlowArgs a;
-  a.m = model_args(m);
-  a.in = pts; a.c = c; a.out = nullptr; a.aux = score;
-  a.B = B * 2 * D;                              // evaluation points
-  a.c_block = c_block;
-  a.aux_mode = AUX_LOGPROB;
-  a.div_magic = m->div_magic;
-  a.gate = nullptr; a.gate_epoch = 0; a.gate_want = 0;
-  a.fd2 = 2 * D; a.fd_h = 0.5f * dx; a.fd_inv_dx = 1.0f / dx;
-  a.seed = 0; a.first_sample = 0; a.slice_stride = 0;
-  a.c_mode = c_block >= B ? C_SINGLE : C_GENERIC;
-  int spl = m->fast_math ? samples_per_lane(m, a.B) : 1;
+  const int64_t n_eval = B * 2 * D;                 // evaluation points
+  int spl = m->fast_math ? samples_per_lane(m, n_eval) : 1;
   if (spl == 2 && (size_t)(hdr_floats(m->cfg.num_bins) + 2 * D * TILE * 2) * sizeof(float) > 160 * 1024) spl = 1;
+  FlowArgs a = flow_args<float>(m, pts, c, c_block, nullptr, score, AUX_LOGPROB, n_eval, TILE * spl);
+  a.fd2 = 2 * D; a.fd_h = 0.5f * dx; a.fd_inv_dx = 1.0f / dx;
+  a.c_mode = c_block >= B ? C_SINGLE : C_GENERIC;       // c_block counts points r_i, not evaluation points
   // plain fp32: the difference of two nearby log_prob values cancels what the precise position path would fix
   const int precise = m->precise;
   m->precise = 0;
@@ -2179,30 +2192,18 @@ static int loss_terms_pwl(CnfModel* m, const CnfLossSpec* spec, const float* pts
   const int64_t ts = 2 * threads;
   const size_t lds = (size_t)(((cnf::hdr_floats(5) + 3) & ~3) + n_sets * L * cnf::PWL_LTBL + 2 * ts) * sizeof(float);
   if (lds > 160 * 1024) return CNF_ERR_UNSUPPORTED;
-  const int64_t tps = (B + ts - 1) / ts;
-  const int64_t total = n_slices * tps;
-  if (total > (1 << 30)) return CNF_ERR_UNSUPPORTED;
-  if (m->use_pwl == 1 && (total < 2 * (int64_t)m->num_cus || B < 4 * ts)) return CNF_ERR_UNSUPPORTED;
+  SlicePlan plan;
+  if (slice_plan(m, stream, B, n_slices, ts, n_sets, &plan) != CNF_OK) return CNF_ERR_UNSUPPORTED;
+  const int64_t tps = plan.tps, chunk = plan.chunk;
+  float* tables = plan.tables;
   if (!ensure_lds(cnf::loss_pwl_kernel<5, true>, lds)) return CNF_ERR_UNSUPPORTED;
-  int64_t chunk = n_slices < PWL_MAX_SLICES ? n_slices : PWL_MAX_SLICES;
-  float* tables = nullptr;
-  {
-    int64_t sets = 0;
-    pwl_workspace(m, stream, &tables, &sets);
-    if (sets / n_sets < chunk) chunk = sets / n_sets;
-    if (chunk < 1) return CNF_ERR_UNSUPPORTED;
-    if (m->use_pwl == 1 && chunk < n_slices && chunk * tps < (int64_t)m->num_cus) return CNF_ERR_UNSUPPORTED;
-  }
-  const double sp_offset = log(exp(1.0 - (double)m->cfg.min_knot_slope) - 1.0);
   m->last_path = CNF_PATH_LOSS_TABLES;
   for (int64_t s0 = 0; s0 < n_slices; s0 += chunk) {
     const int64_t ns = n_slices - s0 < chunk ? n_slices - s0 : chunk;
     const int64_t set_stride = ns * L * (int64_t)cnf::PWL_TBL;
     for (int s = 0; s < n_sets; ++s) {          // conditions t - dt/2, t + dt/2, t (kinetic kinds) or t
       const float off = !kin ? 0.0f : (s == 0 ? -0.5f * spec->dt : (s == 1 ? 0.5f * spec->dt : 0.0f));
-      hipLaunchKernelGGL(cnf::pwl_build_kernel, dim3((unsigned)(ns * L)), dim3(512), 0, stream,
-                         (const float*)(m->prep + cnf::hdr_floats(5)), m->per_layer, t + s0, off, L, sp_offset,
-                         tables + s * set_stride);
+      build_tables(m, stream, t + s0, off, ns, tables + s * set_stride);
     }
     cnf::LossPwlArgs a;
     a.m = model_args(m); a.spec = *spec; a.t = t + s0; a.sums = sums + s0; a.tables = tables;
@@ -2236,8 +2237,6 @@ static int loss_terms_impl(CnfModel* m, const CnfLossSpec* spec, const float* pt
     const int r = loss_terms_pwl(m, spec, pts, slice_stride, seed, first_sample, t, n_slices, B, sums, stream);
     if (r != CNF_ERR_UNSUPPORTED) return r;
   }
-  m->last_path = CNF_PATH_LOSS_MLP;
-
   LossArgs a;
   a.m = model_args(m); a.spec = *spec; a.pts = pts; a.t = t; a.sums = sums;
   a.B = B; a.n_slices = n_slices; a.pts_slice_stride = slice_stride;
@@ -2253,16 +2252,13 @@ static int loss_terms_impl(CnfModel* m, const CnfLossSpec* spec, const float* pt
   int64_t grid = ((B + ts - 1) / ts) * n_slices;
   const int64_t cap = (int64_t)m->num_cus * 8;
   if (grid > cap) grid = cap;
-#define X(HH, KK)                                                                             \
-  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                    \
-    if (!m->fast_math) CNF_LAUNCH((loss_kernel<HH, KK, false, float>), grid, lds, stream, a);                 \
-    else if (spl == 2) CNF_LAUNCH((loss_kernel<HH, KK, true, v2f>), grid, lds, stream, a);                    \
-    else CNF_LAUNCH((loss_kernel<HH, KK, true, float>), grid, lds, stream, a);                                \
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                            \
-  }
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return CNF_ERR_UNSUPPORTED;
+  return with_shape(m->cfg, [&](auto h, auto k) -> int {
+    constexpr int H = decltype(h)::value, K = decltype(k)::value;
+    typedef void (*LossKernel)(const LossArgs);
+    LossKernel kern = loss_kernel<H, K, false, float>;
+    if (m->fast_math) kern = spl == 2 ? loss_kernel<H, K, true, v2f> : loss_kernel<H, K, true, float>;
+    return launch(m, kern, grid, TILE, lds, stream, a, CNF_PATH_LOSS_MLP);
+  });
 }
 
 extern "C" int cnf_loss_terms(CnfModel* m, const CnfLossSpec* spec, const float* pts, int pts_shared,
@@ -2290,15 +2286,13 @@ static int launch_flow_f64(CnfModel* m, const FlowArgsD& a, hipStream_t stream) 
   const int64_t cap = (int64_t)m->num_cus * 8;
   if (grid > cap) grid = cap;
   const size_t lds = (size_t)(hdr_floats(m->cfg.num_bins) + 2 * a.m.D * TILE) * sizeof(double);
-#define X(HH, KK)                                                                    \
-  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                           \
-    if (m->cfg.periodized) CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, false, double, false, false, true>), grid, lds, stream, a); \
-    else CNF_LAUNCH((flow_kernel<HH, KK, TO_BASE, false, double>), grid, lds, stream, a); \
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                   \
-  }
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return CNF_ERR_UNSUPPORTED;
+  return with_shape(m->cfg, [&](auto h, auto k) -> int {
+    constexpr int H = decltype(h)::value, K = decltype(k)::value;
+    typedef void (*FlowKernelD)(const FlowArgsD);
+    const FlowKernelD kern = m->cfg.periodized ? flow_kernel<H, K, TO_BASE, false, double, false, false, true>
+                                               : flow_kernel<H, K, TO_BASE, false, double>;
+    return launch(m, kern, grid, TILE, lds, stream, a, CNF_PATH_F64);
+  });
 }
 
 static int run_flow_f64(CnfModel* m, bool to_base, const double* in, const double* c, int64_t c_block,
@@ -2308,18 +2302,7 @@ static int run_flow_f64(CnfModel* m, bool to_base, const double* in, const doubl
   if (!m->params_set) return CNF_ERR_INVALID;
   if (B == 0) return CNF_OK;
   if (wait_for_params(m, (hipStream_t)stream) != CNF_OK) return CNF_ERR_HIP;
-  m->last_path = CNF_PATH_F64;
-  FlowArgsD a;
-  a.m = model_args(m);
-  a.in = in; a.c = c; a.out = out; a.aux = aux;
-  a.B = B; a.c_block = c_block; a.aux_mode = aux_mode; a.div_magic = m->div_magic;
-  a.gate = nullptr; a.gate_epoch = 0; a.gate_want = 0;
-  a.fd2 = 0; a.fd_h = 0.0; a.fd_inv_dx = 0.0;
-  a.seed = 0; a.first_sample = 0; a.slice_stride = 0;
-  if (c_block >= B) a.c_mode = C_SINGLE;
-  else if (c_block == 1) a.c_mode = C_PER_SAMPLE;
-  else if (c_block % TILE == 0) a.c_mode = C_TILE_UNIFORM;
-  else a.c_mode = C_GENERIC;
+  const FlowArgsD a = flow_args<double>(m, in, c, c_block, out, aux, aux_mode, B, TILE);
   return to_base ? launch_flow_f64<true>(m, a, (hipStream_t)stream) : launch_flow_f64<false>(m, a, (hipStream_t)stream);
 }
 
@@ -2359,10 +2342,7 @@ static bool fields_supported(const CnfModel* m) {
   constexpr bool F64 = std::is_same<R, double>::value;
   if (m->cfg.periodized || m->cfg.dim > 14 || (!F64 && !m->fast_math)) return false;
   if (fields_lds_bytes<R>(m) > 160 * 1024) return false;
-#define X(HH, KK) if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) return true;
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return false;
+  return shape_compiled(m->cfg);
 }
 
 template <class R>
@@ -2379,16 +2359,10 @@ static int launch_fields(CnfModel* m, cnf::FieldArgsT<R>& a, hipStream_t stream)
   a.slice_chunk = (a.fixed_base && tiles >= 2 * (int64_t)m->num_cus) ? (int32_t)(a.S < (1 << 20) ? a.S : (1 << 20)) : 1;
   const int64_t items = tiles * ((a.S + a.slice_chunk - 1) / a.slice_chunk);
   const int64_t grid = balanced_grid(items, (int64_t)m->num_cus * 8);
-#define X(HH, KK)                                                                             \
-  if (m->cfg.hidden_size == HH && m->cfg.num_bins == KK) {                                    \
-    m->last_path = F64 ? CNF_PATH_F64 : CNF_PATH_FIELDS;                                      \
-    if constexpr (F64) CNF_LAUNCH((cnf::fields_kernel<HH, KK, false, double>), grid, lds, stream, a);  \
-    else CNF_LAUNCH((cnf::fields_kernel<HH, KK, true, float>), grid, lds, stream, a);          \
-    return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;                            \
-  }
-  CNF_KERNEL_CONFIGS(X)
-#undef X
-  return CNF_ERR_UNSUPPORTED;
+  return with_shape(m->cfg, [&](auto h, auto k) -> int {      // float32: hardware transcendentals; float64: ocml
+    return launch(m, cnf::fields_kernel<decltype(h)::value, decltype(k)::value, !F64, R>, grid, TILE, lds, stream, a,
+                  F64 ? CNF_PATH_F64 : CNF_PATH_FIELDS);
+  });
 }
 
 template <class R>

@@ -605,6 +605,47 @@ def test_table_path_many_slices(dev):
   eng.set_pwl(1)
 
 
+def test_table_path_chunked_by_a_small_reservation(dev):
+  """A reservation smaller than the slice count, together with several table sets per slice: 7 slices of 4 098 samples
+  (two full 2 048-sample tiles and a 2-sample tail tile) on 3 reserved sets run as flow chunks of 3, 3 and 1 slices,
+  and the kinetic term (2 sets per slice) as one slice per chunk.  Per-sample results do not depend on the chunking:
+  bit for bit those of a 7-set reservation.  The per-slice kinetic sums are accumulated in an order that depends on
+  the grid: the one-chunk result (14 sets) to the 5e-5 that test_gpu_losses.py grants two evaluations of that term."""
+  from cnf_ot_amd import FlowConfig, FlowEngine, Params, applications as app, _capi
+  cfg = FlowConfig(dim=2)
+  eng = FlowEngine(cfg, dev).load(Params.random(cfg, 0.2, seed=14, device=dev))
+  eng.set_pwl(2)
+  S, Bs = 7, 4098
+  x = eng.normal(8, S * Bs)
+  t = torch.linspace(0.05, 0.95, S, device=dev)
+  kinetic = app._spec(_capi.TERM_KINETIC, dt=0.01)
+  torch.cuda.synchronize()
+
+  def reserved(n_sets, calls):
+    side = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(side):
+      _capi.check(eng.lib.cnf_model_reserve(eng._h, side.cuda_stream, n_sets), "cnf_model_reserve")
+      eng._reserved[side.cuda_stream] = 1 << 20                # keep the engine from growing it
+      out = []
+      for call, path in calls:
+        out.append(call())
+        assert eng.last_path() == path
+    torch.cuda.synchronize()
+    assert eng.lib.cnf_model_reserved(eng._h, side.cuda_stream) == n_sets
+    return out
+
+  flow = [(lambda: eng.sample_logprob(x, t), "tables"), (lambda: eng.log_prob(x, t), "tables")]
+  loss = [(lambda: eng.loss_terms_seeded(kinetic, 11, t, Bs, first_sample=5, slice_stride=Bs), "loss_tables")]
+  (y3, lp3), lq3, kin3 = reserved(3, flow + loss)
+  (y7, lp7), lq7 = reserved(7, flow)
+  kin14, = reserved(14, loss)
+  assert torch.equal(y3, y7) and torch.equal(lp3, lp7) and torch.equal(lq3, lq7)
+  rel = ((kin3 - kin14).abs() / kin14.abs().clamp_min(1e-30)).max().item()
+  print(f"\n[chunked kinetic] 1 slice per chunk vs one chunk: max relative difference over {S} slices {rel:.2e}")
+  assert torch.isfinite(kin14).all() and (kin14 > 0).all() and rel <= 5e-5
+  eng.set_pwl(1)
+
+
 def test_table_path_on_two_streams(dev):
   """The conditioner tables live in a workspace per (model, stream): calls of
   one model issued on two streams, with different slice counts (one grows its
