@@ -127,6 +127,13 @@ SYMBOLS = {
                                             ctypes.c_double, _P, _P, _P, _P, _P]),
   "cnf_trajectories": (ctypes.c_int, [_P, _P, _I64, ctypes.c_float, _P, _I64, ctypes.c_float, _P, _P, _P]),
   "cnf_trajectories_f64": (ctypes.c_int, [_P, _P, _I64, ctypes.c_double, _P, _I64, ctypes.c_double, _P, _P, _P]),
+  # the Euler-Maruyama particle reference of the fp problems (snap_step: a host array) and the same statistics of points
+  "cnf_fp_particles_workspace": (ctypes.c_int, [_I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_fp_particles": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_double, ctypes.c_double,
+                                      _I64, ctypes.c_double, _U64, _I64, _I64, _P, ctypes.POINTER(_I64), ctypes.c_int32,
+                                      ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _I64, _P]),
+  "cnf_point_stats": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CnfFieldGrid), _P, _P, _P,
+                                     _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

@@ -811,6 +811,145 @@ def rwpo_reference_path(T, beta, a, subtype, times, x1, x2=None, var0=None, dz=0
   return out
 
 
+# ---- the particle reference of the fp problems --------------------------------------------------------------------
+# flow_matching_loss_fn (applications.py:279-374) fits v_flow + sigma grad log rho = drift: the continuity form of
+# d rho / dt = -div(rho drift) + sigma lap rho, the law of dX = drift(X) dt + sqrt(2 sigma) dW.  An Euler-Maruyama
+# ensemble of that SDE (the reference's tests/test_lorenz.py sketches one) is a ground truth for every drift and every
+# dimension: cnf_fp_particles (include/cnf_ot_amd.h), float64 state, one particle per lane.
+FP_DRIFT_DIM = {"gradient": 2, "smile": 2, "nongradient": 2, "lorenz": 3}       # ou: any dimension
+FP_MAX_SNAPSHOTS = 64
+
+
+def fp_initial_variance(T):
+  """The per-dimension variance (T + 1) / 2 of the initial condition the fp training fits: fp_loss_fn's reverse KL at
+  beta = 4 (applications.py:432, reverse_kl_loss_fn :137-143)."""
+  return (T + 1.0) / 2.0
+
+
+def stats_grid(grid, axes, dim):
+  """The histogram grid of fp_reference_particles / utils.point_stats as a CnfFieldGrid: `grid` is a utils.field_grid
+  (its own axes count) or (domain_range, n) over the event axes `axes`; cell j is centred on the grid point
+  lo + j (hi - lo) / (n - 1), density_on_grid's points.  None for grid = None."""
+  if grid is None:
+    return None
+  if isinstance(grid, dict):
+    dom, n, axes = grid["domain_range"], grid["n"], grid["axes"]
+  else:
+    dom, n = grid
+  x_min, x_max, y_min, y_max = (float(v) for v in dom)
+  nx, ny = (int(n), int(n)) if np.ndim(n) == 0 else (int(n[0]), int(n[1]))
+  ax, ay = int(axes[0]), int(axes[1])
+  if nx < 2 or ny < 2 or not (x_max > x_min and y_max > y_min):
+    raise ValueError(f"histogram grid: needs n >= 2 points per axis over a non-empty range, not {n} over {dom}")
+  if ax == ay or not (0 <= ax < dim and 0 <= ay < dim):
+    raise ValueError(f"histogram grid: axes {(ax, ay)} are equal or outside an event of dimension {dim}")
+  return _capi.CnfFieldGrid(x_min, y_min, (x_max - x_min) / (nx - 1), (y_max - y_min) / (ny - 1), nx, ny, ax, ay, -1, 1,
+                            None, None)
+
+
+def stats_from_sums(sums, hist, n_total, g, dim):
+  """The dictionary of fp_reference_particles / utils.point_stats from raw sums [S, 2 + D + D D] (float64) and counts
+  hist [S, ny, nx] (or None): count and bad [S] (finite / non-finite points), mean [S, D] and cov [S, D, D] =
+  sum x x^T / count - mean mean^T over the finite ones, hist (int64), density = hist / (n_total cell area), and the raw
+  sums (those of two shards add)."""
+  S = sums.shape[0]
+  n = sums[:, 0]
+  mean = sums[:, 2:2 + dim] / n[:, None]
+  cov = sums[:, 2 + dim:].reshape(S, dim, dim) / n[:, None, None] - mean[:, :, None] * mean[:, None, :]
+  out = {"count": n, "bad": sums[:, 1], "mean": mean, "cov": cov, "sums": sums, "hist": None, "density": None}
+  if hist is not None:
+    out["hist"] = hist.to(torch.int64)
+    out["density"] = out["hist"].double() / (float(n_total) * g.step_x * g.step_y)
+  return out
+
+
+def _stats_buffers(dev, N, dim, S, g, want_sums=True):
+  """(sums, hist, workspace) device buffers of one cnf_fp_particles / cnf_point_stats call"""
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_fp_particles_workspace(N, dim, S, C.byref(nbytes)), "cnf_fp_particles_workspace")
+  sums = torch.empty(S, 2 + dim + dim * dim, dtype=torch.float64, device=dev) if want_sums else None
+  ws = torch.empty(-(-nbytes.value // 8), dtype=torch.float64, device=dev) if want_sums else None
+  hist = None if g is None else torch.empty(S, g.ny, g.nx, dtype=torch.int32, device=dev)      # (uint32 counts < 2^31)
+  return sums, hist, ws
+
+
+def fp_step_indices(times, h, T):
+  """times -> Euler-Maruyama step indices; ValueError for a time that is not a multiple of h to within 1e-9 T, is
+  negative, or for times that do not ascend or are more than 64."""
+  ts = np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64).reshape(-1)
+  if not (h > 0.0 and math.isfinite(h)):
+    raise ValueError(f"fp_reference_particles: the step h must be positive, not {h}")
+  if ts.size < 1 or ts.size > FP_MAX_SNAPSHOTS or not np.isfinite(ts).all():
+    raise ValueError(f"fp_reference_particles: between 1 and {FP_MAX_SNAPSHOTS} finite times, not {ts.size}")
+  steps = np.rint(ts / h).astype(np.int64)
+  if (np.abs(steps * h - ts) > 1e-9 * float(T)).any():
+    raise ValueError(f"fp_reference_particles: every time must be a multiple of h = {h} (to within 1e-9 T): {ts.tolist()}")
+  if steps[0] < 0 or (np.diff(steps) <= 0).any():
+    raise ValueError(f"fp_reference_particles: the times must be >= 0 and ascend: {ts.tolist()}")
+  return ts, steps
+
+
+def fp_reference_particles(dim, T, a, sigma, subtype, times, n_particles=1 << 20, h=1e-3, seed=0, var0=None, x0=None,
+                           grid=None, axes=(0, 1), positions=False, shard=None, all_reduce=True):
+  """The fp problem's density along `times` from an Euler-Maruyama ensemble of dX = drift(X) dt + sqrt(2 sigma) dW
+  (drift `subtype` with parameter a, as flow_matching_loss_fn evaluates it) started from N(0, var0 I) -- var0 = None:
+  fp_initial_variance(T), the training's own initial condition -- or from the given x0 [n_particles, dim]: n_particles
+  float64 paths of step h in one cnf_fp_particles launch, the normals drawn in the kernel from the cnf_fill_normal
+  stream of `seed`.  Particle p's draws depend on (seed, p) alone: the ranks of `shard` split the particles by
+  first_particle and the sums and counts are all-reduced (all_reduce=False: this rank's block alone, e.g. one half of
+  an ensemble), so the result does not depend on the number of ranks beyond the sums' last bits.
+  Returns a dict of device tensors, as stats_from_sums: times [S]; count, bad [S]; mean [S, D]; cov [S, D, D]; sums;
+  with `grid` (a utils.field_grid or (domain_range, n), over `axes`) hist [S, ny, nx] and density = hist / (n_particles
+  cell area), cell j centred on grid point j -- density_on_grid's points; with positions=True pos [S, count, D], this
+  rank's particles.  ValueError before any device work for an unknown drift or one for another dimension, a time that is
+  not a multiple of h (1e-9 T), and the C ABI's other refusals."""
+  if subtype not in _capi.DRIFTS:
+    raise ValueError(f"unknown drift {subtype!r}")
+  dim, n_particles = int(dim), int(n_particles)
+  if not 1 <= dim <= 14 or FP_DRIFT_DIM.get(subtype, dim) != dim:
+    raise ValueError(f"fp_reference_particles: drift {subtype!r} is not defined at dim {dim}")
+  ts, steps = fp_step_indices(times, float(h), T)
+  var0 = fp_initial_variance(T) if var0 is None else float(var0)
+  if n_particles < 1 or not (var0 > 0.0 and math.isfinite(var0)) or not (sigma >= 0.0):
+    raise ValueError(f"fp_reference_particles: needs n_particles >= 1, var0 > 0 and sigma >= 0")
+  g = stats_grid(grid, axes, dim)
+  shard = shard if shard is not None else current_shard()
+  start, count = shard_range(n_particles, shard)
+  if count < 1:
+    raise ValueError(f"fp_reference_particles: {n_particles} particles leave rank {shard.rank} of {shard.world} none")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  if x0 is not None:
+    x0 = torch.as_tensor(x0)
+    if tuple(x0.shape) != (n_particles, dim):
+      raise ValueError(f"fp_reference_particles: x0 must be [{n_particles}, {dim}], not {tuple(x0.shape)}")
+    x0 = x0[start:start + count].to(device=dev, dtype=torch.float64).contiguous()
+  u64, off = seed_to_u64(seed)
+  S = len(steps)
+  # the stream's stride per particle follows n_steps: T / h steps (or the last time's, beyond T), so that every choice
+  # of times in [0, T] looks at the same paths; nothing is integrated past the last time
+  n_steps = max(int(round(float(T) / float(h))), int(steps[-1]))
+  lib, C = _capi.lib(), _capi.ctypes
+  sums, hist, ws = _stats_buffers(dev, count, dim, S, g)
+  pos = torch.empty(S, count, dim, dtype=torch.float64, device=dev) if positions else None
+  snap = (C.c_int64 * S)(*[int(k) for k in steps])
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_fp_particles(_capi.DRIFTS[subtype], dim, float(a), float(sigma), float(h), n_steps, var0,
+                                     u64, off + start, count, None if x0 is None else x0.data_ptr(), snap, S,
+                                     None if g is None else C.byref(g), None if pos is None else pos.data_ptr(),
+                                     sums.data_ptr(), None if hist is None else hist.data_ptr(), ws.data_ptr(),
+                                     ws.numel() * 8, _stream_ptr(dev)), "cnf_fp_particles")
+  hist = None if hist is None else hist.to(torch.int64)
+  if all_reduce:
+    sums = all_reduce_sums(sums, shard)
+    hist = None if hist is None else all_reduce_sums(hist, shard)
+  out = stats_from_sums(sums, hist, n_particles, g, dim)
+  out["times"] = torch.as_tensor(ts, device=dev)
+  if positions:
+    out["pos"] = pos
+  return out
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcnf_ot_amd.so")
-SOURCES = ["cnf_flow.hip", "cnf_grad.hip", "cnf_hopf_cole.hip"]
+SOURCES = ["cnf_flow.hip", "cnf_grad.hip", "cnf_hopf_cole.hip", "cnf_fp_particles.hip"]
 HEADERS = ["cnf_device.h", "cnf_terms.h", "cnf_common.h", "cnf_backward.h", "cnf_pwl.h", "cnf_pwl_build.h",
            os.path.join("..", "..", "include", "cnf_ot_amd.h")]
 VARIANT_PATH = os.path.join(LIB_DIR, "BUILD_VARIANT")     # "full" or "minimal": what the .so in tree contains

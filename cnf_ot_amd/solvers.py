@@ -346,6 +346,75 @@ def print_path_errors(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f}".format(*row))
 
 
+def evaluate_fp_path(config, model: FlowModel, params: Params, times=None, n_particles=1 << 20, h=1e-3, seed=0,
+                     start="gaussian") -> Dict[str, Any]:
+  """Where along [0, T] the flow of an fp configuration departs from the Fokker-Planck solution, for every drift and
+  dimension the figures cover (ValueError for another problem type or a configuration without figure settings): per
+  time of `times` (default: the figure's, each rounded to a multiple of h), n_particles flow samples (model.apply.sample of `seed`) against the
+  Euler-Maruyama ensemble of applications.fp_reference_particles (same count, step h, same seed), histograms on the
+  figure's domain with FIGURE_GRID^2 cells over axes (0, 1).  Lists of floats, one per time:
+    times
+    mean_err        |mean of the flow samples - particle mean|
+    cov_rel_err     |cov_flow - cov_particles|_F / |cov_particles|_F
+    tv              1/2 sum |p - q| between the flow samples' and the particles' histograms (p = counts / n_particles)
+    tv_floor        the same between the two halves of the particle ensemble (each over its n_particles / 2): the
+                    Monte-Carlo noise that makes tv readable (two samples of n_particles / 2: sqrt(2) above the noise
+                    between two of n_particles)
+    density_sq_err  sum (rho_flow(grid points) - density)^2, evaluate_path's measure, the flow's rho from
+                    utils.eulerian_fields; dim 2 only (None elsewhere: the histogram is a marginal there)
+    bad             particles that were not finite
+  start="flow": the ensemble starts from the flow's own samples at t = 0 instead of N(0, (T + 1) / 2 I), which takes
+  the initial-condition fit out of the path error.  Single process (the ensemble is run as its two halves)."""
+  g = config["general"]
+  if g["type"] != "fp":
+    raise ValueError(f"evaluate_fp_path: defined for fp only, not {g['type']}")
+  if start not in ("gaussian", "flow"):
+    raise ValueError(f"evaluate_fp_path: start is 'gaussian' or 'flow', not {start!r}")
+  st = figure_settings(config)
+  if st is None:
+    raise ValueError(f"evaluate_fp_path: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
+  n_particles = int(n_particles)
+  if n_particles < 2 or n_particles % 2:
+    raise ValueError(f"evaluate_fp_path: n_particles must be even (the noise floor compares two halves), not {n_particles}")
+  from .distributed import Shard
+  f, dim = config["fp"], g["dim"]
+  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
+  # (the figure's own times need not be multiples of h -- linspace(0, 1, 10) at dim 3: the default snaps them to it)
+  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
+  applications.fp_step_indices(ts, float(h), T)
+  S = len(ts)
+  grid = utils.field_grid(st["domain_range"], FIGURE_GRID, axes=(0, 1))
+  samples = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n_particles,)) for t in ts])
+  flow = utils.point_stats(samples, grid)
+  x0 = model.apply.sample(params, cond=0.0, seed=seed, sample_shape=(n_particles,)).double() if start == "flow" else None
+  halves = [applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, x0=x0, grid=grid,
+                                                shard=Shard(r, 2), all_reduce=False) for r in (0, 1)]
+  ref = applications.stats_from_sums(halves[0]["sums"] + halves[1]["sums"], halves[0]["hist"] + halves[1]["hist"],
+                                     n_particles, applications.stats_grid(grid, None, dim), dim)
+  p, q = flow["hist"].double() / n_particles, ref["hist"].double() / n_particles
+  ha, hb = (hv["hist"].double() / (n_particles // 2) for hv in halves)
+  dens = None
+  if dim == 2:
+    rho = utils.eulerian_fields(model, params, grid, ts, rho=True)["rho"].double()
+    dens = ((rho - ref["density"].reshape(S, -1)) ** 2).sum(1).tolist()
+  return {"times": [float(t) for t in ts],
+          "mean_err": torch.linalg.norm(flow["mean"] - ref["mean"], dim=1).tolist(),
+          "cov_rel_err": (torch.linalg.norm((flow["cov"] - ref["cov"]).reshape(S, -1), dim=1)
+                          / torch.linalg.norm(ref["cov"].reshape(S, -1), dim=1)).tolist(),
+          "tv": (0.5 * (p - q).abs().sum((1, 2))).tolist(),
+          "tv_floor": (0.5 * (ha - hb).abs().sum((1, 2))).tolist(),
+          "density_sq_err": dens,
+          "bad": ref["bad"].tolist()}
+
+
+def print_fp_path_errors(res: Dict[str, Any]) -> None:
+  """evaluate_fp_path's table, one line per time"""
+  print("path errors against the particle reference:  t | mean err | cov rel err | tv | tv floor | density sq err | bad")
+  dens = res["density_sq_err"] or [float("nan")] * len(res["times"])
+  for row in zip(res["times"], res["mean_err"], res["cov_rel_err"], res["tv"], res["tv_floor"], dens, res["bad"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.4f} | {:.4f} | {:.3e} | {:.0f}".format(*row))
+
+
 # ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
 # The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
 # by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
@@ -436,7 +505,7 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
          fields: Optional[str] = None, path_errors: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
-  evaluate_path's table after them (rwpo at dim 2)."""
+  evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp)."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -484,7 +553,9 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print("L2 error via Monte-Carlo against the initial condition N(0, (T+1)/2 I): {:.3e}".format(res["l2_mc_ic"]))
     print("variance at T: {} | closed form: {:.4f}".format(" ".join(f"{v:.4f}" for v in res["var_T"]),
                                                           res["var_T_closed_form"]))
-  if path_errors:
+  if path_errors and _type == "fp":
+    print_fp_path_errors(evaluate_fp_path(config, model, params))
+  elif path_errors:
     print_path_errors(evaluate_path(config, model, params))
   return res
 
@@ -498,7 +569,8 @@ def _parse(argv):
   p.add_argument("--save", default=None, help="write the trained flat parameters to this .npz file")
   p.add_argument("--fields", default=None, help="write the arrays behind the reference's figures (figure_data) to this .npz file")
   p.add_argument("--path-errors", action="store_true",
-                 help="print the density and velocity errors against the exact solution at 9 times (rwpo at dim 2)")
+                 help="print the density and velocity errors against the exact solution at 9 times (rwpo at dim 2), or the "
+                      "errors against the particle reference at the figure's times (fp)")
   return p.parse_args(argv)
 
 

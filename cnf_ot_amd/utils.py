@@ -276,3 +276,29 @@ def trajectories(model, params, r_, t_array, t0: float = 0.0, with_velocity: boo
     vel[j] = (model.apply.forward(params, xi, float(c + h)) - model.apply.forward(params, xi, float(c - h))) * \
       float(torch.tensor(1.0, dtype=dtype) / torch.tensor(dt, dtype=dtype))
   return traj, vel
+
+
+def point_stats(pts, grid=None, axes=(0, 1)) -> dict:
+  """Moments and a 2-D histogram of given points -- what a flow's own samples go through to be compared with
+  applications.fp_reference_particles, by the same accumulation kernel code (cnf_point_stats): pts [S, N, D] (or
+  [N, D]: S = 1) float32 on the device.  The same dictionary (applications.stats_from_sums): count, bad [S], mean
+  [S, D], cov [S, D, D], sums, and with `grid` (a `field_grid` or (domain_range, n), over the event axes `axes`) hist
+  [S, ny, nx] and density = hist / (N cell area), cell j centred on grid point j.  Non-finite points count as bad."""
+  from .applications import _OnDevice, _stats_buffers, _stream_ptr, stats_from_sums, stats_grid
+  pts = torch.as_tensor(pts)
+  if pts.dim() == 2:
+    pts = pts[None]
+  if pts.dim() != 3 or pts.shape[1] < 1 or not 1 <= pts.shape[2] <= 14 or not 1 <= pts.shape[0] <= 64:
+    raise ValueError(f"point_stats: expected [S <= 64, N >= 1, D <= 14] points, got {tuple(pts.shape)}")
+  S, N, D = pts.shape
+  g = stats_grid(grid, axes, D)
+  if not pts.is_cuda:
+    pts = pts.to(torch.device("cuda", torch.cuda.current_device()))
+  pts = pts.to(torch.float32).contiguous()
+  dev = pts.device
+  sums, hist, ws = _stats_buffers(dev, N, D, S, g)
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_point_stats(pts.data_ptr(), N, D, S, None if g is None else _capi.ctypes.byref(g),
+                                            sums.data_ptr(), None if hist is None else hist.data_ptr(), ws.data_ptr(),
+                                            ws.numel() * 8, _stream_ptr(dev)), "cnf_point_stats")
+  return stats_from_sums(sums, hist, N, g, D)

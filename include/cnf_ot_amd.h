@@ -629,6 +629,51 @@ int cnf_trajectories_f64(CnfModel *m, const double *r0, int64_t N, double t0,
                          const double *t, int64_t S, double dt, double *traj,
                          double *vel, void *stream);
 
+/* ---- a particle reference for the Fokker-Planck problems (applications.py:279-374; the reference's tests/test_lorenz.py
+ * sketches it) ----------------------------------------------------------------------------------------------------
+ * flow_matching_loss_fn fits v_flow + sigma grad log rho = drift, the continuity form of
+ * d rho / dt = -div(rho drift) + sigma lap rho: the density is the law of dX = drift(X) dt + sqrt(2 sigma) dW.
+ * cnf_fp_particles integrates N particles of dimension D from X_0 ~ N(0, var0 I) by n_steps Euler-Maruyama steps
+ *   x <- x + h drift(x) + sqrt(2 sigma h) z
+ * in float64, drift = CnfDrift with parameter `a` exactly as the loss kernels evaluate it (one definition; its float32
+ * constants a, 28/9 and 8/3 widened).  The normals are the cnf_fill_normal(seed, .) stream widened exactly: global
+ * particle p = first_particle + i owns elements [p R, p R + (n_steps + 1) D), R = (n_steps + 1) D rounded up to a
+ * multiple of 4; the first D give x0 = sqrt(var0) z, step k = 1.. the next D each.  x0 [N, D] (device, double;
+ * optional) replaces the drawn start without moving the steps' stream positions.  first_particle splits an ensemble
+ * over ranks or calls.  snap_step [S] (HOST, strictly ascending, in [0, n_steps], S <= 64) travels in the kernel
+ * arguments: step 0 is the start, and nothing is integrated past the last snapshot.  Outputs (device), each optional,
+ * at least one, overwritten:
+ *   pos  [S, N, D]           double
+ *   sums [S, 2 + D + D D]    double: the number of finite particles, of non-finite ones, sum x_d, sum x_d x_e --
+ *                            raw sums, so the shards of an ensemble add
+ *   hist [S, ny, nx]         uint32 counts on `grid` (lo, step, n and axis_x / axis_y; its other members are ignored):
+ *                            cell j is centred on the grid point lo + j step, its index is
+ *                            floor((x - (lo - step / 2)) / step) by an IEEE float64 division; particles outside the
+ *                            grid are not counted
+ * A particle whose state is not finite at a snapshot enters neither that snapshot's sums nor its histogram and is
+ * counted as non-finite.  Two calls are bit-identical: the counts are integers, and the sums are formed over a fixed
+ * partition of the call's particles into chunks of 256, the chunks' partials added in ascending order, whatever the
+ * launch.  `workspace` (needed with sums; cnf_fp_particles_workspace(N, D, S) bytes) is the caller's: no allocation,
+ * no synchronisation.
+ * cnf_point_stats: the same sums and hist over given points pts [S, N, D] (device, float32, widened) -- what the
+ * flow's own samples go through -- by the same accumulation code.
+ * CNF_ERR_INVALID (nothing enqueued): a drift outside CnfDrift or one for another dimension (SMILE, NONGRADIENT: 2;
+ * LORENZ: 3); D < 1 or > 14; h, var0 or N <= 0 or not finite (N above 2^31); sigma < 0; n_steps < 0 (or above 2^30);
+ * first_particle < 0; S < 1 or > 64; snapshot steps that do not ascend or lie outside [0, n_steps]; no output; hist
+ * without a grid, with n < 1, a step <= 0 or more than 2^24 cells; axes equal or outside the event; sums with a
+ * workspace that is NULL or too small. */
+int cnf_fp_particles_workspace(int64_t N, int32_t D, int32_t S, int64_t *bytes);
+int cnf_fp_particles(int32_t drift, int32_t D, float a, double sigma, double h,
+                     int64_t n_steps, double var0, uint64_t seed,
+                     int64_t first_particle, int64_t N, const double *x0,
+                     const int64_t *snap_step, int32_t S,
+                     const CnfFieldGrid *grid, double *pos, double *sums,
+                     uint32_t *hist, void *workspace, int64_t workspace_bytes,
+                     void *stream);
+int cnf_point_stats(const float *pts, int64_t N, int32_t D, int32_t S,
+                    const CnfFieldGrid *grid, double *sums, uint32_t *hist,
+                    void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
