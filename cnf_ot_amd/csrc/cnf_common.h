@@ -1,5 +1,6 @@
-// cnf_common.h -- structs shared by the translation units of libcnf_ot_amd.so
-// (cnf_flow.hip: forward kernels + C ABI; cnf_grad.hip: backward + Adam).
+// cnf_common.h -- structs shared by the translation units of libcnf_ot_amd.so that work on a CnfModel (cnf_model.hip,
+// cnf_rng.hip, cnf_flow.hip, cnf_grad.hip): the model object, the kernels' view of it, the dim-2 table route, the
+// list of compiled shapes and the argument checks.  The declarations of functions that cross units: cnf_host.h.
 #pragma once
 #include <mutex>
 #include <map>
@@ -243,13 +244,6 @@ static inline int wait_for_params(CnfModel* m, hipStream_t stream) {
     if (hipStreamWaitEvent(stream, m->prep_event, 0) != hipSuccess) return CNF_ERR_HIP;
   return CNF_OK;
 }
-
-// cnf_flow.hip: builds the dim-2 conditioner tables (cnf_pwl.h) of n slices -- conditions c[0 .. n) on the device --
-// into the stream's reserved workspace and returns them; CNF_ERR_UNSUPPORTED if the configuration has no table path
-// or the stream's reservation (cnf_model_reserve) is smaller than n.  Used by the table form of cnf_pass_vjp.
-int cnf_internal_build_tables(CnfModel* m, hipStream_t stream, const float* c, int64_t n, float** tables);
-int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, const float* c, int64_t slice_len,
-                             int64_t n_slices, const float* tables, float* out);
 
 static inline cnf::ModelArgs model_args(const CnfModel* m) {
   cnf::ModelArgs a;

@@ -1,4 +1,8 @@
-// cnf_flow.hip -- gfx950 kernels and C ABI of the conditional RQS flow engine.
+// cnf_flow.hip -- the kernels that run the flow, and their host layer: the parameter snapshot (prepare_kernel,
+// circular_slopes_kernel, cnf_model_set_params), the flow (flow_kernel, flow_dpar_kernel, flow_pwl_kernel, the table
+// route), the fused loss terms (loss_kernel, loss_pwl_kernel) and the fields (fields_kernel).  They share one unit
+// because their generated code depends on it (profiles/split_units/README.md).  The model object: cnf_model.hip;
+// the noise fills: cnf_rng.hip; shared device code: cnf_flow_tile.h; what crosses units: cnf_host.h.
 // Declarations and the reference interfaces they replace: include/cnf_ot_amd.h.
 //
 // Kernel design (DESIGN.md has the numbers):
@@ -14,8 +18,8 @@
 //  * the shared `first` spline is pre-normalised (float64, once per parameter
 //    set) into a 12-float-per-bin table that is staged in LDS and gathered by
 //    per-lane bin index.
-#include "cnf_common.h"
-#include <cstdlib>
+#include "cnf_flow_tile.h"
+#include "cnf_host.h"
 #include "cnf_pwl_build.h"
 
 #include <math.h>
@@ -24,43 +28,6 @@
 #include <string.h>
 
 namespace cnf {
-
-
-enum CMode { C_SINGLE = 0, C_PER_SAMPLE = 1, C_TILE_UNIFORM = 2, C_GENERIC = 3 };
-enum AuxMode { AUX_LOGDET = 0, AUX_LOGPROB = 1 };
-
-
-template <class R> struct FlowArgsT {
-  ModelArgs m;
-  const R* in;           // [B, D]
-  const R* c;            // conditions
-  R* out;                // [B, D] or null
-  R* aux;                // [B] logdet / logprob, or null
-  int64_t B;
-  int64_t c_block;
-  int32_t c_mode, aux_mode;
-  int32_t div_magic;     // ceil(2^32 / D): e / D == umulhi(e, magic) for e < 2^16
-  // device-side choice between two kernels enqueued for the same call (uniform-condition detection,
-  // cond_uniform_kernel): this kernel runs only if (*gate == gate_epoch) == gate_want; null: always
-  const uint32_t* gate;
-  uint32_t gate_epoch;
-  int32_t gate_want;
-  // finite-difference mode (cnf_logprob_fd; data -> base only): `in` holds B / fd2 points r_i and evaluation
-  // point j = i * fd2 + 2 d + s is r_i + (s ? -fd_h : +fd_h) e_d (fd2 = 2 D); aux[i * D + d] receives
-  // (log_prob(j) - log_prob(j + 1)) * fd_inv_dx.  fd2 = 0: off.
-  int32_t fd2;
-  R fd_h, fd_inv_dx;
-  // in == null (float32, base -> data only; cnf_sample_logprob_seeded): the points are base noise drawn in the kernel,
-  // sample i = stream sample first_sample + (i / c_block) * slice_stride + i % c_block of the cnf_fill_normal stream
-  uint64_t seed;
-  int64_t first_sample, slice_stride;
-};
-typedef FlowArgsT<float> FlowArgs;
-typedef FlowArgsT<double> FlowArgsD;
-
-template <class A> __device__ __forceinline__ bool gate_closed(const A& a) {
-  return a.gate && ((*a.gate == a.gate_epoch) ? 1 : 0) != a.gate_want;
-}
 
 // boundary_slopes='circular' (RQSFlow(periodized=True), flows.py:131): the last knot's unnormalized slope IS the
 // first knot's.  Run after prepare_kernel on the same stream: in the weight snapshot, column 3K of every output
@@ -208,237 +175,6 @@ __global__ void prepare_kernel(const float* __restrict__ params, float* __restri
   tl[T_INV_DLO] = (float)(1.0 / dl[0]); tl[T_INV_DHI] = (float)(1.0 / dl[K]);
 }
 
-// ---------------------------------------------------------------------------
-// LDS tile: [hdr table][U: D x TS][O: D x TS], TS = 256 * SPL samples per
-// workgroup.  Lane t owns samples SPL*t .. SPL*t+SPL-1 of the tile: its column
-// is U[d*TS + SPL*t] (one ds_read_b32 / ds_read_b64 per dimension,
-// conflict-free).
-// ---------------------------------------------------------------------------
-// e / D for e < 2^16 (a tile has at most 512 * 64 elements): one v_mul_hi_u32
-// instead of the ~20-instruction 32-bit division sequence.
-template <class R>
-__device__ __forceinline__ void tile_load(const R* __restrict__ g, R* U, int D, uint32_t magic, int TS,
-                                          int64_t tile_start, int64_t B) {
-  const int64_t base = tile_start * D;
-  const int n_el = (int)(B - tile_start < TS ? B - tile_start : TS) * D;
-  for (int e = threadIdx.x; e < TS * D; e += TILE) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;   // magic 0: D = 1
-    U[d * TS + s] = e < n_el ? g[base + e] : (R)0;
-  }
-}
-
-// One tile of base noise straight into LDS: the tile's TS*D stream elements are
-// contiguous; a thread draws whole Philox blocks (4 normals) and scatters them.
-__device__ __forceinline__ void tile_noise(uint64_t seed, uint64_t first_element, float* U, int D, uint32_t magic,
-                                           int TS, int64_t n_valid_samples, int nthreads = TILE) {
-  const int n_el = (int)(n_valid_samples < TS ? n_valid_samples : TS) * D;
-  const uint64_t blk0 = first_element >> 2;
-  const int n_blk = (int)(((first_element + (uint64_t)(TS * D) - 1) >> 2) - blk0) + 1;
-  for (int q = threadIdx.x; q < n_blk; q += nthreads) {
-    const uint64_t blk = blk0 + (uint64_t)q;
-    float z[4];
-    philox_normals4(seed, blk, z);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t e = (int64_t)((blk << 2) + r) - (int64_t)first_element;
-      if (e >= 0 && e < TS * D) {
-        const int s = magic ? (int)__umulhi((uint32_t)e, magic) : (int)e, d = (int)e - s * D;
-        U[d * TS + s] = e < n_el ? z[r] : 0.0f;
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float normal_at(uint64_t seed, uint64_t e) {     // element e of the cnf_fill_normal stream
-  float z[4];
-  philox_normals4(seed, e >> 2, z);
-  return z[e & 3];
-}
-
-// The tile of a seeded flow call (FlowArgsT::in == null): one contiguous run of the stream where the tile lies in
-// one slice (or the slices follow each other in the stream), element by element otherwise.
-__device__ __forceinline__ void tile_noise_flow(const FlowArgsT<float>& a, float* U, int D, uint32_t magic, int TS,
-                                                int64_t tile_start, int nthreads) {
-  const int64_t left = a.B - tile_start;
-  const int64_t last = tile_start + (left < TS ? left : TS) - 1;
-  const bool one = a.c_block >= a.B;
-  const int64_t s0 = one ? 0 : tile_start / a.c_block, s1 = one ? 0 : last / a.c_block;
-  if (s0 == s1 || a.slice_stride == a.c_block) {
-    const int64_t st = a.first_sample + s0 * a.slice_stride + (tile_start - s0 * a.c_block);
-    tile_noise(a.seed, (uint64_t)st * (uint64_t)D, U, D, magic, TS, left, nthreads);
-    return;
-  }
-  const int n_el = (int)(left < TS ? left : TS) * D;
-  for (int e = threadIdx.x; e < TS * D; e += nthreads) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;
-    float v = 0.0f;
-    if (e < n_el) {
-      const int64_t i = tile_start + s, sl = i / a.c_block;
-      const int64_t st = a.first_sample + sl * a.slice_stride + (i - sl * a.c_block);
-      v = normal_at(a.seed, (uint64_t)st * (uint64_t)D + (uint64_t)d);
-    }
-    U[d * TS + s] = v;
-  }
-}
-__device__ __forceinline__ void tile_noise_flow(const FlowArgsT<double>&, double*, int, uint32_t, int, int64_t, int) {}
-
-template <class R>
-__device__ __forceinline__ void tile_store(R* __restrict__ g, const R* U, int D, uint32_t magic, int TS,
-                                           int64_t tile_start, int64_t B) {
-  const int64_t base = tile_start * D;
-  const int n_el = (int)(B - tile_start < TS ? B - tile_start : TS) * D;
-  for (int e = threadIdx.x; e < TS * D; e += TILE) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;
-    if (e < n_el) g[base + e] = U[d * TS + s];
-  }
-}
-
-template <class R>
-__device__ __forceinline__ R load_cond1(const FlowArgsT<R>& a, int64_t tile_start, int64_t i) {
-  if (a.fd2) {                                   // evaluation point -> its base point's condition
-    if (a.c_mode == C_SINGLE) return a.c[0];
-    return i < a.B ? a.c[(i / a.fd2) / a.c_block] : (R)0;
-  }
-  switch (a.c_mode) {
-    case C_SINGLE: return a.c[0];
-    case C_PER_SAMPLE: return i < a.B ? a.c[i] : (R)0;
-    case C_TILE_UNIFORM: return a.c[tile_start / a.c_block];
-    default: return i < a.B ? a.c[i / a.c_block] : (R)0;
-  }
-}
-template <class T> __device__ __forceinline__ T load_cond(const FlowArgsT<typename Lanes<T>::real>& a, int64_t tile_start, int64_t i);
-template <> __device__ __forceinline__ float load_cond<float>(const FlowArgs& a, int64_t ts, int64_t i) {
-  return load_cond1(a, ts, i);
-}
-template <> __device__ __forceinline__ double load_cond<double>(const FlowArgsD& a, int64_t ts, int64_t i) {
-  return load_cond1(a, ts, i);
-}
-template <> __device__ __forceinline__ v2f load_cond<v2f>(const FlowArgs& a, int64_t ts, int64_t i) {
-  if (a.c_mode == C_SINGLE || a.c_mode == C_TILE_UNIFORM) return splat<v2f>(load_cond1(a, ts, i));
-  return v2f{load_cond1(a, ts, i), load_cond1(a, ts, i + 1)};
-}
-
-// finite-difference mode: the tile's evaluation points are built from the base points on the fly
-template <class R>
-__device__ __forceinline__ void tile_load_fd(const FlowArgsT<R>& a, R* U, int D, uint32_t magic, int TS, int64_t tile_start) {
-  const int n_el = (int)(a.B - tile_start < TS ? a.B - tile_start : TS) * D;
-  for (int e = threadIdx.x; e < TS * D; e += TILE) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;
-    R v = (R)0;
-    if (e < n_el) {
-      const int64_t j = tile_start + s, i = j / a.fd2;
-      const int k = (int)(j - i * a.fd2);
-      v = a.in[i * D + d];
-      if ((k >> 1) == d) v += (k & 1) ? -a.fd_h : a.fd_h;
-    }
-    U[d * TS + s] = v;
-  }
-}
-// (log_prob(+) - log_prob(-)) / dx of the pair (j, j + 1), j even
-__device__ __forceinline__ void store_fd(const FlowArgs& a, int64_t j, v2f lp) {
-  if (j + 1 < a.B) a.aux[j >> 1] = (lp.x - lp.y) * a.fd_inv_dx;
-}
-__device__ __forceinline__ void store_fd(const FlowArgs& a, int64_t j, float lp) {
-  const float other = __shfl_xor(lp, 1, 64);
-  if (!(j & 1) && j + 1 < a.B) a.aux[j >> 1] = (lp - other) * a.fd_inv_dx;
-}
-__device__ __forceinline__ void store_fd(const FlowArgsD&, int64_t, double) {}
-
-__device__ __forceinline__ float hsum(float v) { return v; }
-__device__ __forceinline__ v2f hsum(v2f v) { return v; }
-
-// One pass of the whole flow over the thread's own sample(s), in place in LDS.
-// TO_BASE=false: base -> data (chain.inverse, spline inverse, conditions on the
-// layer input: conditional.py:169-177, autoregressive.py:109-136).
-// TO_BASE=true : data -> base (chain.forward, spline forward, conditions on
-// already-produced outputs: conditional.py:159-167, autoregressive.py:76-107).
-// Returns the accumulated log|det J|; the result is left in `U` (swapped).
-// PRECISE (TO_BASE only): the precise position path of cnf_device.h; `e2tab` is its 2^(-i/32) table in LDS and
-// `bacc` receives sum_d x_d^2 of the recovered base point in float64.
-// DFIX > 0: the event dimension is this compile-time constant (the single-batch kernel at dim 2: the dimension
-// loop, the conditioner offsets and the tile transposes lose their runtime arithmetic)
-template <int H, int K, bool TO_BASE, bool FAST, class T, bool MFMA = false, bool PRECISE = false, bool PERIODIC = false, int DFIX = 0>
-__device__ __forceinline__ T flow_pass(const ModelArgs& a, const typename Lanes<T>::real* tab,
-                                       typename Lanes<T>::real*& U, typename Lanes<T>::real*& O, T c,
-                                       const double* e2tab = nullptr, const double* tabd = nullptr,
-                                       typename Lanes<T>::real* LO = nullptr, BaseAcc<T>* bacc = nullptr) {
-  typedef typename Lanes<T>::real R;
-  static_assert(!PRECISE || (TO_BASE && !std::is_same<T, double>::value), "precise path: data -> base, fp32 kernels");
-  const SplineConstsT<R>& sc = sc_of<R>(a);
-  static_assert(!MFMA || (H == 16 && K == 5), "the MFMA conditioner is built for H = 16, P = 16");
-  static_assert(!PERIODIC || (!MFMA && !PRECISE), "periodized: the scalar-weight conditioner, plain positions");
-  constexpr int P = 3 * K + 1;
-  constexpr bool INV = !TO_BASE;
-  constexpr int SPL = Lanes<T>::N;
-  constexpr int TS = TILE * SPL;
-  uniform_ptr weights = as_uniform(a.prep + hdr_floats(K));
-  const int D = DFIX ? DFIX : a.D;
-  T acc = splat<T>(0.0f);
-  for (int step = 0; step < a.L; ++step) {
-    const int l = TO_BASE ? a.L - 1 - step : step;
-    const bool odd = l & 1;                       // flows.py:141-143 perms
-    const int first_idx = odd ? D - 1 : 0, idx_step = odd ? -1 : 1;
-    R* cu = U + SPL * threadIdx.x;
-    R* co = O + SPL * threadIdx.x;
-    T o, ld, olo;
-    const bool last = step == a.L - 1;
-    [[maybe_unused]] R* clo = nullptr;
-    if constexpr (PRECISE) {
-      // LO[d]: what rounding dimension d's value to fp32 dropped (this thread's column; in place: read as the
-      // layer's input, overwritten with its output).  The data themselves are exact fp32: zero before layer 1.
-      clo = LO + SPL * threadIdx.x;
-      const T vlo = step == 0 ? splat<T>(0.0f) : lds_get<T>(clo, first_idx, TS);
-      table_spline_precise<K, FAST>(tab, tabd, lds_get<T>(cu, first_idx, TS), vlo, sc, o, ld, olo);
-      lds_put(clo, first_idx, TS, olo);
-      if (last) bacc->add(o, olo);
-    } else {
-      table_spline<K, INV, FAST, T>(tab, lds_get<T>(cu, first_idx, TS), sc, o, ld);
-    }
-    lds_put(co, first_idx, TS, o);
-    acc += ld;
-    uniform_ptr w = weights + l * a.per_layer;
-    const float* wq = a.wq + l * a.per_layer_q;
-    for (int d = 1; d < D; ++d) {
-      const int i = first_idx + d * idx_step;
-      T th[P];
-      if constexpr (MFMA && !std::is_same<T, double>::value) {
-        // (at dim 2 the MFMA-layout first layer is three back-to-back vector loads: faster than scalar loads +
-        // a transpose for a lone wave -- 6.1 vs 6.4 us per 65 536-sample call; from dim 3 the row loop dominates)
-        conditioner_mfma<T>(reinterpret_cast<const f4*>(wq), d, a.M, c, TO_BASE ? co : cu, first_idx, idx_step, TS, th,
-                            D >= 3 ? w : nullptr);
-        wq += cond_floats_mfma(d, a.M);
-        w += cond_floats(d, H, a.M, P);
-      } else {
-        conditioner<H, P, T, PERIODIC>(w, d, a.M, c, TO_BASE ? co : cu, first_idx, idx_step, TS, th);
-        w += cond_floats_p(d, H, a.M, P, PERIODIC);
-      }
-      if constexpr (PRECISE) {
-        const T vlo = step == 0 ? splat<T>(0.0f) : lds_get<T>(clo, i, TS);
-        cond_spline_precise<K, FAST, false>(th, lds_get<T>(cu, i, TS), vlo, sc, a.scd, e2tab, o, ld, olo);
-        lds_put(clo, i, TS, olo);
-        if (last) bacc->add(o, olo);
-      } else {
-        cond_spline<K, INV, FAST, T>(th, lds_get<T>(cu, i, TS), sc, o, ld);
-      }
-      lds_put(co, i, TS, o);
-      acc += ld;
-    }
-    R* t = U; U = O; O = t;
-  }
-  return acc;
-}
-
-__device__ __forceinline__ void store_aux(float* aux, int64_t i, int64_t B, float r) {
-  if (i < B) aux[i] = r;
-}
-__device__ __forceinline__ void store_aux(double* aux, int64_t i, int64_t B, double r) {
-  if (i < B) aux[i] = r;
-}
-__device__ __forceinline__ void store_aux(float* aux, int64_t i, int64_t B, v2f r) {
-  if (i + 1 < B && ((reinterpret_cast<uintptr_t>(aux + i) & 7) == 0)) *reinterpret_cast<v2f*>(aux + i) = r;
-  else { if (i < B) aux[i] = r.x; if (i + 1 < B) aux[i + 1] = r.y; }
-}
-
 template <int H, int K, bool TO_BASE, bool FAST, class T, bool MFMA = false, bool PRECISE = false, bool PERIODIC = false, int DFIX = 0>
 __global__ __launch_bounds__(TILE, 2) void flow_kernel(const FlowArgsT<typename Lanes<T>::real> a) {
   typedef typename Lanes<T>::real R;
@@ -519,27 +255,6 @@ __global__ __launch_bounds__(TILE, 2) void flow_kernel(const FlowArgsT<typename 
 // conditioner + one spline per wave and a barrier, and the shard becomes 256-512 workgroups of D - 1 waves.  The
 // waves' log-det shares are summed in a fixed order (deterministic).
 // ---------------------------------------------------------------------------
-template <class R>
-__device__ __forceinline__ void tile_load_n(const R* __restrict__ g, R* U, int D, uint32_t magic, int TS,
-                                            int64_t tile_start, int64_t B, int nthreads) {
-  const int64_t base = tile_start * D;
-  const int n_el = (int)(B - tile_start < TS ? B - tile_start : TS) * D;
-  for (int e = threadIdx.x; e < TS * D; e += nthreads) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;
-    U[d * TS + s] = e < n_el ? g[base + e] : (R)0;
-  }
-}
-template <class R>
-__device__ __forceinline__ void tile_store_n(R* __restrict__ g, const R* U, int D, uint32_t magic, int TS,
-                                             int64_t tile_start, int64_t B, int nthreads) {
-  const int64_t base = tile_start * D;
-  const int n_el = (int)(B - tile_start < TS ? B - tile_start : TS) * D;
-  for (int e = threadIdx.x; e < n_el; e += nthreads) {
-    const int s = magic ? (int)__umulhi((uint32_t)e, magic) : e, d = e - s * D;
-    g[base + e] = U[d * TS + s];
-  }
-}
-
 template <int H, int K, bool FAST, class T>
 __global__ __launch_bounds__(1024) void flow_dpar_kernel(const FlowArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -611,8 +326,6 @@ __global__ __launch_bounds__(1024) void flow_dpar_kernel(const FlowArgs a) {
 // two consecutive samples, whose 4 input floats are one 16-byte load and whose
 // outputs are one 16-byte + one 8-byte store -- no LDS staging of the points.
 // ---------------------------------------------------------------------------
-constexpr int PWL_MAX_THREADS = 1024;
-
 struct PwlArgs {
   ModelArgs m;
   const float* in;
@@ -641,98 +354,6 @@ __global__ void cond_uniform_kernel(const float* __restrict__ c, int64_t B, uint
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x)
     diff |= __float_as_uint(c[i]) != c0;
   if (__syncthreads_or(diff) && threadIdx.x == 0) *flag = epoch;
-}
-
-// The dim-2 flow on one sample pair held in registers, conditioner from the tables (`tbl`: the L
-// tables in LDS, `gtbl`: the same in global memory for rows past the LDS window).  In place;
-// returns the accumulated log|det J| of the direction.
-// SHIFT_FREE_OK: use the shift-free spline evaluation where the sample's grid cell allows it (the flow kernels;
-// the loss kernel, at its register limit with three table sets, always evaluates the general form).
-// LFIX > 0: the number of flow layers is this compile-time constant -- the layer loop is unrolled, the layer's
-// parity (which coordinate is conditioned on which) and its table's LDS offset are literals instead of per-layer
-// selects and address arithmetic.
-// LEAN_OK (flow_pwl_kernel): the sampling direction takes the shorter instruction stream of DESIGN 5.1d -- the
-// quadratic's root without a Newton step (the `first` spline everywhere, the conditioned one in shift-free waves),
-// one logarithm per layer, one tail test per layer.  The loss kernel keeps its arithmetic.
-template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, bool SHIFT_FREE_OK = false, int LROWS = PWL_LROWS, int LFIX = 0,
-          bool LEAN_OK = false>
-__device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, const float* __restrict__ gtbl,
-                                            int L, const SplineConsts sc, v2f& u0, v2f& u1,
-                                            const PreciseConsts* pc = nullptr, const double* e2tab = nullptr,
-                                            const double* tabd = nullptr, BaseAcc<v2f>* bacc = nullptr) {
-  constexpr bool INV = !TO_BASE;
-  constexpr bool LEAN = LEAN_OK && INV && FAST;
-  static_assert(!PRECISE || TO_BASE, "precise path: data -> base");
-  v2f acc = splat<v2f>(0.0f);
-  [[maybe_unused]] v2f lo0 = splat<v2f>(0.0f), lo1 = lo0;      // precise path: what rounding u0 / u1 to fp32 dropped
-  if (LFIX) L = LFIX;
-#pragma unroll
-  for (int step = 0; step < (LFIX ? LFIX : L); ++step) {
-    const int l = TO_BASE ? L - 1 - step : step;
-    const bool odd = l & 1;                     // flows.py:141-143 perms
-    const v2f uf = odd ? u1 : u0, uo = odd ? u0 : u1;
-    v2f of, oo, ld, olo_f, olo_o;
-    bool general;
-    const float* tl = tbl + l * pwl_ltbl(LROWS);
-    const float* gl = gtbl + (int64_t)l * PWL_TBL;
-    if constexpr (PRECISE) {
-      table_spline_precise<K, FAST>(tab, tabd, uf, odd ? lo1 : lo0, sc, of, ld, olo_f);
-      if (step == L - 1) bacc->add(of, olo_f);
-      acc += ld;
-      v2f th[PWL_P];
-      pwl_eval<LROWS>(tl, gl, of, th, general);
-      cond_spline_precise<K, FAST, true>(th, uo, odd ? lo0 : lo1, sc, *pc, e2tab, oo, ld, olo_o);
-      if (step == L - 1) bacc->add(oo, olo_o);
-      lo0 = odd ? olo_o : olo_f;
-      lo1 = odd ? olo_f : olo_o;
-    } else {
-      // base -> data: the conditioner sees the layer's INPUT, so its table search and row reads (a chain of three
-      // dependent LDS round trips) are issued first and complete under the arithmetic of the `first` spline
-      PwlRows rr;
-      v2f qa[K], qb[K];
-      if (!TO_BASE) {
-        pwl_find<LROWS>(tl, uf, rr, general);
-        rr.dua = pwl_logit_pairs<LROWS>(rr.ra, gl, rr.pa, uf.x, qa);
-        rr.dub = pwl_logit_pairs<LROWS>(rr.rb, gl, rr.pb, uf.y, qb);
-      }
-      // One logarithm per layer where every lane takes the shift-free form: both splines return the argument of
-      // their log|f'| (the derivative itself) and the product goes through one v_log_f32.  The conditioned
-      // factor is bounded there (slope logits in [-3, 40], bins >= 1e-4 of a range of 20: ~1e-9 .. 1e6), so the
-      // product leaves the fp32 range only for a `first` spline with derivatives beyond 1e-29 .. 1e32.
-      constexpr bool LOGPROD = LEAN;
-      // Both splines read the layer's inputs (uf, uo): one wave-level test guards both linear-tail fix-ups.
-      bool tails = true;
-      if constexpr (LEAN) tails = __builtin_amdgcn_ballot_w64(maybe_outside(uf, uo, sc.lo, sc.hi)) != 0;
-      v2f larg = splat<v2f>(1.0f);
-      if constexpr (LOGPROD) {
-        table_spline<K, INV, FAST, v2f, true, LEAN>(tab, uf, sc, of, larg, tails);
-      } else {
-        table_spline<K, INV, FAST, v2f, false, LEAN>(tab, uf, sc, of, ld, tails);
-        acc += ld;
-      }
-      if (TO_BASE) {
-        pwl_find<LROWS>(tl, of, rr, general);
-        rr.dua = pwl_logit_pairs<LROWS>(rr.ra, gl, rr.pa, of.x, qa);
-        rr.dub = pwl_logit_pairs<LROWS>(rr.rb, gl, rr.pb, of.y, qb);
-      }
-      auto slopes = [&](int ka, int kb, v2f& ta, v2f& tb) {
-        ta = pwl_slope_pair<LROWS>(rr.ra, gl, rr.pa, ka, rr.dua);
-        tb = pwl_slope_pair<LROWS>(rr.rb, gl, rr.pb, kb, rr.dub);
-      };
-      if (!SHIFT_FREE_OK || __builtin_amdgcn_ballot_w64(general) != 0)      // wave-uniform: a lane's cell is marked
-      {       // marked cells (ill-conditioned pieces, far-out inputs): the general form, and its own logarithm
-        cond_spline_rows<K, INV, FAST, false, false, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
-        if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg); ld += INV ? -lg : lg; }
-      } else {
-        cond_spline_rows<K, INV, FAST, true, LOGPROD, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
-        if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg * ld); ld = INV ? -lg : lg; }
-      }
-    }
-    acc += ld;
-    u0 = odd ? oo : of;
-    u1 = odd ? of : oo;
-  }
-  return acc;
 }
 
 template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, int LROWS = PWL_LROWS, int LFIX = 0, bool SEEDED = false>
@@ -1293,316 +914,12 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
   ssum.flush(a.sums);
 }
 
-// ---------------------------------------------------------------------------
-// Base noise: Philox4x32-10 + Box-Muller; one counter block (4 normals) per
-// thread.  Element e of the stream uses block e>>2, word pair (e&3)>>1.
-// ---------------------------------------------------------------------------
-// seed_dev (optional): the key is read from device memory -- state[1] of a training step's device-side state
-// (cnf_step_begin) -- so that a captured step draws new noise on every replay
-__global__ void fill_normal_kernel(uint64_t seed, uint64_t first_element, int64_t n,
-                                   float* __restrict__ out, const uint64_t* __restrict__ seed_dev) {
-  if (seed_dev) seed = seed_dev[1];
-  const uint64_t first_blk = first_element >> 2;
-  const uint64_t last_blk = (first_element + (uint64_t)n - 1) >> 2;
-  for (uint64_t blk = first_blk + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; blk <= last_blk;
-       blk += (uint64_t)gridDim.x * blockDim.x) {
-    float z[4];
-    philox_normals4(seed, blk, z);
-    const uint64_t e0 = blk << 2;
-    if (e0 >= first_element && e0 + 3 < first_element + (uint64_t)n && (((e0 - first_element) & 3) == 0) &&
-        ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
-      *reinterpret_cast<float4*>(out + (e0 - first_element)) = make_float4(z[0], z[1], z[2], z[3]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint64_t e = e0 + r;
-        if (e >= first_element && e < first_element + (uint64_t)n) out[e - first_element] = z[r];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// JAX-compatible base draw: jax.random.normal(key, (n, D), float64) as the reference makes it
-// (conditional.py:378,399 -> distrax Normal -> jax.random.normal; float64 because solvers.py:23 enables x64), for the
-// classic (non-"partitionable") threefry bit generation: element j of the flattened [size] draw takes the 64 bits
-// (o0 << 32) | o1 of the Threefry-2x32-20 block with counter (j, size + j) and key (k0, k1)
-// [threefry_2x32 splits the iota of 2 size counters in halves; the 64-bit combine takes the halves of the output],
-// maps them to a uniform in [nextafter(-1, 0), 1) through the mantissa of a double in [1, 2), and returns
-// sqrt(2) erfinv(u).  The Threefry function is pinned by the Random123 known-answer vectors (tests); the bit ->
-// normal mapping restates jax._src.random (un-pinned JAX version, not installable here: cannot be compared with
-// JAX itself -- "parity unpinned" for this entry point).
-// ---------------------------------------------------------------------------
-__host__ __device__ inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__host__ __device__ inline void threefry2x32_20(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t& o0,
-                                                uint32_t& o1) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  const int rot[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  uint32_t x0 = c0 + ks[0], x1 = c1 + ks[1];
-  for (int g = 0; g < 5; ++g) {
-    for (int r = 0; r < 4; ++r) { x0 += x1; x1 = rotl32(x1, rot[g & 1][r]); x1 ^= x0; }
-    x0 += ks[(g + 1) % 3];
-    x1 += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-  o0 = x0; o1 = x1;
-}
-
-__global__ __launch_bounds__(256) void fill_normal_threefry_kernel(uint32_t k0, uint32_t k1, uint64_t size, uint64_t first, int64_t n,
-                                            float* __restrict__ out32, double* __restrict__ out64) {
-  const double lo = -0.99999999999999988897769753748;        // nextafter(-1, 0)
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t j = first + (uint64_t)i;
-    uint32_t o0, o1;
-    threefry2x32_20(k0, k1, (uint32_t)j, (uint32_t)(size + j), o0, o1);
-    const uint64_t bits = ((uint64_t)o0 << 32) | (uint64_t)o1;
-    const double f = __longlong_as_double((long long)((bits >> 12) | 0x3FF0000000000000ull)) - 1.0;
-    const double u = fmax(lo, f * (1.0 - lo) + lo);
-    const double z = 1.41421356237309504880 * erfinv(u);
-    if (out64) out64[i] = z;
-    if (out32) out32[i] = (float)z;
-  }
-}
-
 }  // namespace cnf
 
 // ===========================================================================
 // C ABI
 // ===========================================================================
 using namespace cnf;
-
-
-
-static int config_valid(const CnfConfig* c) {
-  if (!c) return 0;
-  if (c->dim < 1 || c->dim > 64) return 0;
-  if (c->num_layers < 1 || c->num_layers > 64) return 0;
-  if (c->hidden_size < 1 || c->mlp_num_layers < 1 || c->mlp_num_layers > 16) return 0;
-  if (c->num_bins < 1 || c->num_bins > 64) return 0;
-  if (!(c->range_min < c->range_max)) return 0;
-  if (!(c->min_bin_size > 0.f) || !(c->min_knot_slope > 0.f) || !(c->min_knot_slope < 1.f)) return 0;
-  if (c->num_bins * c->min_bin_size > c->range_max - c->range_min) return 0;   // distrax raises
-  if (c->periodized != 0 && c->periodized != 1) return 0;
-  return 1;
-}
-
-extern "C" int cnf_config_supported(const CnfConfig* c) {
-  return config_valid(c) && shape_compiled(*c) ? 1 : 0;
-}
-
-extern "C" void cnf_config_default(CnfConfig* c, int32_t dim) {
-  if (!c) return;
-  c->dim = dim; c->num_layers = 2; c->hidden_size = 16; c->mlp_num_layers = 2; c->num_bins = 5;
-  c->range_min = -10.f; c->range_max = 10.f; c->min_bin_size = 1e-4f; c->min_knot_slope = 1e-4f;
-  c->periodized = 0;
-}
-
-extern "C" int64_t cnf_param_count(const CnfConfig* c) {
-  if (!config_valid(c)) return CNF_ERR_INVALID;
-  const int P = 3 * c->num_bins + 1;
-  int64_t n = P;
-  for (int d = 1; d < c->dim; ++d)
-    n += (int64_t)c->num_layers * cond_floats_p(d, c->hidden_size, c->mlp_num_layers, P, c->periodized != 0);
-  return n;
-}
-
-extern "C" const char* cnf_strerror(int code) {
-  switch (code) {
-    case CNF_OK: return "ok";
-    case CNF_ERR_INVALID: return "invalid argument";
-    case CNF_ERR_UNSUPPORTED: return "no kernel compiled for this (hidden_size, num_bins)";
-    case CNF_ERR_NOMEM: return "out of memory";
-    case CNF_ERR_HIP: return "HIP runtime error";
-    default: return "unknown error";
-  }
-}
-
-extern "C" const char* cnf_build_arch(void) { return "gfx950"; }
-
-extern "C" int cnf_model_create(const CnfConfig* cfg, CnfModel** out) {
-  if (!out) return CNF_ERR_INVALID;
-  *out = nullptr;
-  if (!config_valid(cfg)) return CNF_ERR_INVALID;
-  if (!cnf_config_supported(cfg)) return CNF_ERR_UNSUPPORTED;
-  CnfModel* m = new (std::nothrow) CnfModel();       // value-initialised: scalars and pointers start at zero
-  if (!m) return CNF_ERR_NOMEM;
-  m->cfg = *cfg;
-  const int K = cfg->num_bins, P = 3 * K + 1;
-  m->n_params = cnf_param_count(cfg);
-  m->per_layer = 0;
-  for (int d = 1; d < cfg->dim; ++d)
-    m->per_layer += cond_floats_p(d, cfg->hidden_size, cfg->mlp_num_layers, P, cfg->periodized != 0);
-  m->sc.lo = cfg->range_min; m->sc.hi = cfg->range_max;
-  m->sc.min_bin = cfg->min_bin_size; m->sc.min_slope = cfg->min_knot_slope;
-  m->sc.span_eff = (float)(((double)cfg->range_max - (double)cfg->range_min) - (double)K * (double)cfg->min_bin_size);
-  m->sc.sp_offset = (float)log(exp(1.0 - (double)cfg->min_knot_slope) - 1.0);
-  m->fast_math = 1;
-  if (hipGetDevice(&m->device) != hipSuccess) { delete m; return CNF_ERR_HIP; }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, m->device) != hipSuccess) { delete m; return CNF_ERR_HIP; }
-  m->num_cus = prop.multiProcessorCount;
-  // The MFMA conditioner: fp32 MFMA and fp32 VALU do not overlap on gfx950 (their busy times add up:
-  // profiles/r01c), so at equal peak rate the packed-VALU conditioner is 4-5 % faster once the chip is full.  A
-  // launch of one wave per SIMD is a different regime: a lone wave issues one VALU instruction per 8 cycles
-  // (profiles/r01_issue_probe), and the MFMA form has ~45 % fewer of them and no scalar weight loads to wait
-  // for -- 6.1 vs 9.8 us per 65 536-sample call (profiles/r02_experiments/exp_latency.log).  2 = by launch size.
-  m->use_mfma = 2;
-  m->use_pwl = 1;
-  m->use_dpar = 1;
-  // (D = 1 would need 2^32: encoded as 0, tile_load/tile_store take s = e)
-  m->div_magic = cfg->dim == 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + (uint64_t)cfg->dim - 1) / (uint64_t)cfg->dim);
-  m->per_layer_q = 0; m->mfma_off = 0;
-  size_t q_floats = 0;
-  if (cfg->hidden_size == 16 && P == 16 && cfg->dim > 1 && !cfg->periodized) {      // (no MFMA form of the sin / cos layer)
-    for (int d = 1; d < cfg->dim; ++d) m->per_layer_q += cond_floats_mfma(d, cfg->mlp_num_layers);
-    m->mfma_off = (hdr_floats(K) + (m->n_params - P) + 3) & ~(int64_t)3;
-    q_floats = (size_t)m->per_layer_q * cfg->num_layers;
-  }
-  // float64 copy of the `first` table (exact-mode kernels), 8-byte aligned, after everything else
-  m->tabd_off = (hdr_floats(K) + (m->n_params - P) + 4 + (int64_t)q_floats + 1) & ~(int64_t)1;
-  // 2^(-i/32), i = 0 .. 1024, float64: the table of the precise position path (cnf_device.h)
-  m->e2_off = m->tabd_off + 2 * hdr_floats(K);
-  m->precise = 1;
-  const size_t bytes = (size_t)(m->e2_off + 2 * cnf::EXP2_N) * sizeof(float) + 64;
-  m->scd.lo = (double)cfg->range_min; m->scd.hi = (double)cfg->range_max;
-  m->scd.min_bin = (double)cfg->min_bin_size; m->scd.min_slope = (double)cfg->min_knot_slope;
-  m->scd.span_eff = (m->scd.hi - m->scd.lo) - (double)K * m->scd.min_bin;
-  m->scd.sp_offset = log(exp(1.0 - m->scd.min_slope) - 1.0);
-  if (hipMalloc((void**)&m->prep, bytes) != hipSuccess) { delete m; return CNF_ERR_NOMEM; }
-  {
-    double e2[cnf::EXP2_N];
-    for (int i = 0; i < cnf::EXP2_N; ++i) e2[i] = exp2(-(double)i / (double)cnf::EXP2_STEPS);
-    if (hipMemcpy(m->prep + m->e2_off, e2, sizeof(e2), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(m->prep); delete m; return CNF_ERR_HIP;
-    }
-  }
-  if (hipEventCreateWithFlags(&m->prep_event, hipEventDisableTiming) != hipSuccess) {
-    (void)hipFree(m->prep); delete m; return CNF_ERR_HIP;
-  }
-  *out = m;
-  return CNF_OK;
-}
-
-static void prof_clear(CnfModel* m) {
-  for (auto& r : m->prof) {
-    if (r.e0) (void)hipEventDestroy(r.e0);
-    if (r.e1) (void)hipEventDestroy(r.e1);
-    if (r.e2) (void)hipEventDestroy(r.e2);
-  }
-  m->prof.clear();
-}
-
-extern "C" void cnf_model_destroy(CnfModel* m) {
-  if (!m) return;
-  if (m->prep) (void)hipFree(m->prep);
-  if (m->grad_slabs) (void)hipFree(m->grad_slabs);
-  if (m->pwl_stats) (void)hipFree(m->pwl_stats);
-  for (auto& kv : m->pwl_ws) {
-    if (kv.second.tables) (void)hipFree(kv.second.tables);
-    for (float* p : kv.second.retired) (void)hipFree(p);
-  }
-  if (m->prep_event) (void)hipEventDestroy(m->prep_event);
-  prof_clear(m);
-  delete m;
-}
-
-/* Which kernels the most recent compute call of this model ran: a CnfPath value (cnf_common.h).
- * Tests use it to assert that a forced path was really taken; bench.py labels its roofline with it. */
-extern "C" int cnf_model_last_path(const CnfModel* m) { return m ? m->last_path : CNF_ERR_INVALID; }
-
-/* Internal (bench.py): with profiling on, the flow entry points record HIP events around their kernels
- * (table path: before the table build, between build and flow kernel, after the flow kernel), at most
- * 4096 launches.  cnf_model_read_profile waits for them and returns the SUMS in milliseconds of the
- * dominant (flow) kernel and of the table build, the number of kernel launches and the samples they
- * processed, then clears the records. */
-extern "C" int cnf_model_set_profiling(CnfModel* m, int on) {
-  if (!m) return CNF_ERR_INVALID;
-  m->profiling = on ? 1 : 0;
-  if (!on) prof_clear(m);
-  return CNF_OK;
-}
-
-extern "C" int cnf_model_read_profile(CnfModel* m, double* flow_ms, double* build_ms, int64_t* launches,
-                                      int64_t* samples) {
-  if (!m) return CNF_ERR_INVALID;
-  double f = 0.0, b = 0.0;
-  int64_t n = 0, smp = 0;
-  for (auto& r : m->prof) {
-    if (hipEventSynchronize(r.e2) != hipSuccess) return CNF_ERR_HIP;
-    float ms = 0.f;
-    if (r.e0) { if (hipEventElapsedTime(&ms, r.e0, r.e1) != hipSuccess) return CNF_ERR_HIP; b += ms; }
-    if (hipEventElapsedTime(&ms, r.e1, r.e2) != hipSuccess) return CNF_ERR_HIP;
-    f += ms; ++n; smp += r.samples;
-  }
-  prof_clear(m);
-  if (flow_ms) *flow_ms = f;
-  if (build_ms) *build_ms = b;
-  if (launches) *launches = n;
-  if (samples) *samples = smp;
-  return CNF_OK;
-}
-
-// profiling helpers: a record is opened before the (optional) build kernel and closed after the flow kernel
-// (samples < 0: a launch that is not recorded)
-struct ProfScope {
-  CnfModel* m; hipStream_t s; CnfModel::ProfRec r; bool on;
-  ProfScope(CnfModel* m_, hipStream_t s_, bool with_build, int64_t samples, int path) : m(m_), s(s_), on(false) {
-    r.e0 = r.e1 = r.e2 = nullptr; r.samples = samples; r.path = path;
-    if (!m->profiling || samples < 0 || m->prof.size() >= 4096) return;
-    if (hipEventCreate(&r.e1) != hipSuccess || hipEventCreate(&r.e2) != hipSuccess) return;
-    if (with_build) { if (hipEventCreate(&r.e0) != hipSuccess) return; (void)hipEventRecord(r.e0, s); }
-    else (void)hipEventRecord(r.e1, s);
-    on = true;
-  }
-  void built() { if (on && r.e0) (void)hipEventRecord(r.e1, s); }
-  void done() { if (on) { (void)hipEventRecord(r.e2, s); m->prof.push_back(r); on = false; } }
-};
-
-/* Internal knob used by the tests and the bench: 1 = hardware transcendentals
- * (default), 0 = ocml expf/logf/sqrtf + IEEE division. */
-extern "C" int cnf_model_set_fast_math(CnfModel* m, int on) {
-  if (!m) return CNF_ERR_INVALID;
-  m->fast_math = on ? 1 : 0;
-  return CNF_OK;
-}
-
-/* Internal knob: 1 = MFMA conditioner wherever available, 0 = packed-VALU conditioner, 2 = MFMA for launches
- * that leave the chip under-filled (default). */
-extern "C" int cnf_model_set_mfma(CnfModel* m, int mode) {
-  if (!m || mode < 0 || mode > 2) return CNF_ERR_INVALID;
-  m->use_mfma = mode;
-  return CNF_OK;
-}
-
-/* Internal knob: 1 = piecewise-linear conditioner tables at dim 2 for large launches (default),
- * 2 = for every launch they apply to (tests), 0 = always evaluate the MLP. */
-extern "C" int cnf_model_set_pwl(CnfModel* m, int mode) {
-  if (!m || mode < 0 || mode > 2) return CNF_ERR_INVALID;
-  m->use_pwl = mode;
-  return CNF_OK;
-}
-
-/* 1 (default): cnf_log_prob / cnf_inverse_logdet (data -> base) carry the knot positions, the offset in the
- * bin and the base term in float64 (cnf_device.h "precise position path"); 0: plain fp32 throughout. */
-extern "C" int cnf_model_set_precise(CnfModel* m, int on) {
-  if (!m) return CNF_ERR_INVALID;
-  m->precise = on ? 1 : 0;
-  return CNF_OK;
-}
-
-/* Internal knob: wave-per-dimension kernel for base -> data at dim >= 3: 1 = by batch size (default),
- * 2 = always, 0 = never. */
-extern "C" int cnf_model_set_dpar(CnfModel* m, int mode) {
-  if (!m || mode < 0 || mode > 2) return CNF_ERR_INVALID;
-  m->use_dpar = mode;
-  return CNF_OK;
-}
-
-/* Internal knob: 0 = choose by batch size, 1 / 2 = force samples per lane. */
-extern "C" int cnf_model_set_samples_per_lane(CnfModel* m, int spl) {
-  if (!m || spl < 0 || spl > 2) return CNF_ERR_INVALID;
-  m->force_spl = spl;
-  return CNF_OK;
-}
 
 extern "C" int cnf_model_set_params(CnfModel* m, const float* params, void* stream) {
   if (!m || !params) return CNF_ERR_INVALID;
@@ -1632,6 +949,22 @@ extern "C" int cnf_model_set_params(CnfModel* m, const float* params, void* stre
   return CNF_OK;
 }
 
+
+// profiling helpers: a record is opened before the (optional) build kernel and closed after the flow kernel
+// (samples < 0: a launch that is not recorded)
+struct ProfScope {
+  CnfModel* m; hipStream_t s; CnfModel::ProfRec r; bool on;
+  ProfScope(CnfModel* m_, hipStream_t s_, bool with_build, int64_t samples, int path) : m(m_), s(s_), on(false) {
+    r.e0 = r.e1 = r.e2 = nullptr; r.samples = samples; r.path = path;
+    if (!m->profiling || samples < 0 || m->prof.size() >= 4096) return;
+    if (hipEventCreate(&r.e1) != hipSuccess || hipEventCreate(&r.e2) != hipSuccess) return;
+    if (with_build) { if (hipEventCreate(&r.e0) != hipSuccess) return; (void)hipEventRecord(r.e0, s); }
+    else (void)hipEventRecord(r.e1, s);
+    on = true;
+  }
+  void built() { if (on && r.e0) (void)hipEventRecord(r.e1, s); }
+  void done() { if (on) { (void)hipEventRecord(r.e2, s); m->prof.push_back(r); on = false; } }
+};
 
 constexpr int CNF_MFMA_SMALL_WAVES = 4;        // waves of single-lane work per SIMD up to which use_mfma = 2 picks MFMA
 
@@ -1746,71 +1079,6 @@ static int launch_flow(CnfModel* m, const FlowArgs& a, int spl, hipStream_t stre
     return launch(m, flow_kernel_of<H, K, TO_BASE>(precise, m->fast_math != 0, spl), grid, TILE, lds, stream, a,
                   spl == 2 ? CNF_PATH_MLP2 : CNF_PATH_MLP1, gated, a.B);
   });
-}
-
-// This stream's table workspace (cnf_model_reserve).  Lookup only: the compute entry points never allocate,
-// free or synchronise.  *sets = 0 when the stream has no reservation.
-static void pwl_workspace(CnfModel* m, hipStream_t stream, float** tables, int64_t* sets, uint32_t** flag = nullptr,
-                          uint32_t* epoch = nullptr) {
-  std::lock_guard<std::mutex> lock(m->pwl_mu);
-  auto it = m->pwl_ws.find((void*)stream);
-  if (it == m->pwl_ws.end()) { *tables = nullptr; *sets = 0; return; }
-  *tables = it->second.tables; *sets = it->second.sets;
-  // the uniform-condition stamp lives behind the tables; a call that uses it takes a fresh epoch
-  if (flag) { *flag = reinterpret_cast<uint32_t*>(it->second.tables + it->second.sets * m->cfg.num_layers * (int64_t)cnf::PWL_TBL);
-              *epoch = ++it->second.epoch; }
-}
-
-extern "C" int64_t cnf_model_table_bytes(const CnfModel* m) {
-  return m ? (int64_t)sizeof(float) * m->cfg.num_layers * cnf::PWL_TBL : 0;
-}
-
-extern "C" int cnf_model_reserve(CnfModel* m, void* stream, int64_t n_sets) {
-  if (!m || n_sets < 0) return CNF_ERR_INVALID;
-  std::lock_guard<std::mutex> lock(m->pwl_mu);
-  CnfModel::PwlWorkspace& ws = m->pwl_ws[stream];          // value-initialised on first use
-  if (ws.sets >= n_sets && n_sets > 0) return CNF_OK;
-  if (ws.tables && n_sets > 0) {
-    // Growing: the old block is RETIRED, not freed -- a HIP graph captured on this stream has its address baked into
-    // kernel arguments and may be replayed at any later time (a stream synchronisation protects running kernels, not
-    // future replays).  Retired blocks live until cnf_model_destroy or an explicit release (n_sets = 0); reservations
-    // grow geometrically (FlowEngine.reserve), so they add up to less than the current block.
-    ws.retired.push_back(ws.tables);
-    ws.tables = nullptr; ws.sets = 0;
-  }
-  if (n_sets == 0) {      // explicit release: the caller vouches that nothing (no graph either) uses this stream's tables
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return CNF_ERR_HIP;
-    if (ws.tables) (void)hipFree(ws.tables);
-    for (float* p : ws.retired) (void)hipFree(p);
-    m->pwl_ws.erase(stream);
-    return CNF_OK;
-  }
-  if (hipMalloc((void**)&ws.tables, (size_t)cnf_model_table_bytes(m) * (size_t)n_sets + 64) != hipSuccess) {
-    ws.tables = nullptr; ws.sets = 0;        // (calls on this stream fall back to the MLP kernels; retired blocks stay)
-    return CNF_ERR_NOMEM;
-  }
-  // the stamp of cond_uniform_kernel starts at 0; epochs count from 1
-  if (hipMemset(reinterpret_cast<char*>(ws.tables) + (size_t)cnf_model_table_bytes(m) * (size_t)n_sets, 0, 64) != hipSuccess) {
-    (void)hipFree(ws.tables); ws.tables = nullptr; ws.sets = 0;
-    return CNF_ERR_HIP;
-  }
-  ws.sets = n_sets; ws.epoch = 0;
-  return CNF_OK;
-}
-
-extern "C" int64_t cnf_model_reserved(CnfModel* m, void* stream) {
-  if (!m) return CNF_ERR_INVALID;
-  float* t; int64_t sets;
-  pwl_workspace(m, (hipStream_t)stream, &t, &sets);
-  return sets;
-}
-
-static_assert(cnf::PWL_H == 16, "pwl_network (cnf_common.h) states the tables' network");
-
-extern "C" int cnf_model_has_tables(const CnfModel* m) { return m && pwl_network(m->cfg) ? 1 : 0; }
-
-extern "C" int cnf_model_term_on_tables(const CnfModel* m, int64_t slice_len, int64_t n_points, int with_grad) {
-  return m && pwl_term_on_tables(m, slice_len, n_points, with_grad != 0) ? 1 : 0;
 }
 
 // How a call on the tables walks its slices: `chunk` slices per build + kernel pair, `tps` tiles per slice, on the
@@ -2053,18 +1321,6 @@ extern "C" int cnf_sample_logprob_seeded(CnfModel* m, uint64_t seed, int64_t fir
   return run_flow(m, false, nullptr, c, c_block, y, logp, AUX_LOGPROB, B, stream, &noise);
 }
 
-extern "C" int cnf_fill_normal_threefry(uint32_t key0, uint32_t key1, uint64_t size, uint64_t first_element, int64_t n,
-                                        float* out_f32, double* out_f64, void* stream) {
-  if (n < 0 || (n > 0 && !out_f32 && !out_f64) || first_element + (uint64_t)n > size || size > 0x7fffffffull)
-    return CNF_ERR_INVALID;        // (2 size 32-bit counters: jax's single-block case)
-  if (n == 0) return CNF_OK;
-  int64_t grid = (n + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(fill_normal_threefry_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, key0, key1,
-                     size, first_element, n, out_f32, out_f64);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
 extern "C" int cnf_logprob_fd(CnfModel* m, const float* pts, const float* c, int64_t c_block, float dx,
                               float* score, int64_t B, void* stream) {
   if (!m || !pts || !c || !score || B < 0 || c_block < 1 || !(dx > 0.f)) return CNF_ERR_INVALID;
@@ -2085,97 +1341,6 @@ extern "C" int cnf_logprob_fd(CnfModel* m, const float* pts, const float* c, int
   const int r = launch_flow<true>(m, a, spl, (hipStream_t)stream);
   m->precise = precise;
   return r;
-}
-
-extern "C" int cnf_fill_normal(uint64_t seed, uint64_t first_element, int64_t n, float* out,
-                               void* stream) {
-  if (n < 0 || (n > 0 && !out)) return CNF_ERR_INVALID;
-  if (n == 0) return CNF_OK;
-  const uint64_t n_blk = ((first_element + (uint64_t)n - 1) >> 2) - (first_element >> 2) + 1;
-  uint64_t grid = (n_blk + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, seed,
-                     first_element, n, out, (const uint64_t*)nullptr);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
-// ---- the random inputs of a training step drawn from a key in DEVICE memory ---------------------------------------
-// state: uint64[2] on the device = { step count, key }.  The caller writes the key (one 8-byte copy) before a step;
-// every draw below reads it on the device, so the whole step -- draws, loss, gradient, Adam -- can be captured into
-// a HIP graph once and replayed with a new key each time.  Streams of one key: the normal stream of
-// cnf_fill_normal (Philox counter words 2, 3 = 0, 0), uniforms (word 2 = 1) and 3-bit integers (word 2 = 2).
-namespace cnf {
-__global__ void step_begin_kernel(uint64_t* state) { if (threadIdx.x == 0 && blockIdx.x == 0) state[0] += 1; }
-
-// out[i] = scale * u, u = 24-bit uniform in [0, 1) from word (first + i) & 3 of block (first + i) >> 2 of stream 1
-__global__ void fill_uniform_kernel(const uint64_t* __restrict__ state, uint64_t first, int64_t n, float scale,
-                                    float* __restrict__ out) {
-  const uint64_t key = state[1];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t e = first + (uint64_t)i;
-    uint32_t u[4];
-    philox4x32((uint32_t)(e >> 2), (uint32_t)(e >> 34), 1u, 0u, (uint32_t)key, (uint32_t)(key >> 32), u);
-    out[i] = scale * ((float)(u[e & 3] >> 8) * (1.0f / 16777216.0f));
-  }
-}
-
-// The 8-mode mixture source of kl_loss_fn (applications.py:34-71) for n samples of dim 2: out[i] = z[i] + centre of
-// component (first_sample + i), the component = the top 3 bits of word e & 3 of block e >> 2 of stream 2
-__global__ void mixture_source_kernel(const uint64_t* __restrict__ state, uint64_t first_sample, int64_t n,
-                                      const float* __restrict__ z, float* __restrict__ out, int32_t* __restrict__ comp_out) {
-  constexpr float R = 5.0f;
-  const float cx[8] = {0.0f, 1.0f, 0.0f, -1.0f, 0.6f, 0.6f, -0.6f, -0.6f};
-  const float cy[8] = {1.0f, 0.0f, -1.0f, 0.0f, 0.8f, -0.8f, -0.8f, 0.8f};
-  const uint64_t key = state[1];
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t e = first_sample + (uint64_t)i;
-    uint32_t u[4];
-    philox4x32((uint32_t)(e >> 2), (uint32_t)(e >> 34), 2u, 0u, (uint32_t)key, (uint32_t)(key >> 32), u);
-    const int k = (int)(u[e & 3] >> 29);
-    float mx = 0.0f, my = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { mx = k == j ? cx[j] : mx; my = k == j ? cy[j] : my; }
-    if (out) { out[2 * i] = z[2 * i] + R * mx; out[2 * i + 1] = z[2 * i + 1] + R * my; }
-    if (comp_out) comp_out[i] = k;
-  }
-}
-}  // namespace cnf
-
-extern "C" int cnf_step_begin(uint64_t* state, void* stream) {
-  if (!state) return CNF_ERR_INVALID;
-  hipLaunchKernelGGL(cnf::step_begin_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
-extern "C" int cnf_fill_normal_dev(const uint64_t* state, uint64_t first_element, int64_t n, float* out, void* stream) {
-  if (!state || n < 0 || (n > 0 && !out)) return CNF_ERR_INVALID;
-  if (n == 0) return CNF_OK;
-  const uint64_t n_blk = ((first_element + (uint64_t)n - 1) >> 2) - (first_element >> 2) + 1;
-  uint64_t grid = (n_blk + 255) / 256;
-  if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (uint64_t)0,
-                     first_element, n, out, state);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
-extern "C" int cnf_fill_uniform_dev(const uint64_t* state, uint64_t first, int64_t n, float scale, float* out, void* stream) {
-  if (!state || n < 0 || (n > 0 && !out)) return CNF_ERR_INVALID;
-  if (n == 0) return CNF_OK;
-  int64_t grid = (n + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(cnf::fill_uniform_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, state, first, n, scale, out);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
-extern "C" int cnf_mixture_source_dev(const uint64_t* state, uint64_t first_sample, int64_t n, const float* z, float* out,
-                                      int32_t* comp, void* stream) {
-  if (!state || n < 0 || (n > 0 && !out && !comp) || (out && !z)) return CNF_ERR_INVALID;
-  if (n == 0) return CNF_OK;
-  int64_t grid = (n + 255) / 256;
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(cnf::mixture_source_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, state, first_sample,
-                     n, z, out, comp);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 
 

@@ -14,6 +14,7 @@
 //     the result is deterministic); grad_finish_kernel sums the slabs.
 // Built for the reference's network only: hidden 16, 2 hidden layers, 5 bins.
 #include "cnf_backward.h"
+#include "cnf_host.h"
 #include "cnf_pwl.h"
 
 #include <math.h>

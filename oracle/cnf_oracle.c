@@ -131,7 +131,7 @@ int cnf_oracle_normal_f64(uint64_t seed, uint64_t first_element, int64_t n,
 
 /* ---- Threefry-2x32-20 (Salmon et al. 2011, Random123) and the JAX-style normal draw --------------------------
  * Restates jax._src.prng.threefry_2x32 / threefry_random_bits (classic, non-partitionable path) and
- * jax._src.random._uniform / _normal_real for float64: see cnf_ot_amd/csrc/cnf_flow.hip fill_normal_threefry_kernel.
+ * jax._src.random._uniform / _normal_real for float64: see cnf_ot_amd/csrc/cnf_rng.hip fill_normal_threefry_kernel.
  * The block function is pinned by the Random123 known-answer vectors (tests/test_oracle_flow.py). */
 static uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
