@@ -93,6 +93,7 @@ SYMBOLS = {
   "cnf_kinetic_potential_vjp": (ctypes.c_int, [_P, _P, _I64, _P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32,
                                                ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
   "cnf_logprob_fd": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_float, _P, _I64, _P]),
+  "cnf_score": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _I64, _I64, _P, _P, _P]),
   "cnf_logprob_fd_vjp": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_float, _P, _P, _P, _P, _I64, _P]),
   "cnf_score_fd_vjp": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32,
                                       ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _I64, _P]),
@@ -149,7 +150,8 @@ _INTERNAL = {
   "cnf_model_read_profile": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
 }
-PATH_NAMES = {0: "none", 1: "mlp1", 2: "mlp2", 3: "mfma", 4: "tables", 5: "loss_mlp", 6: "loss_tables", 7: "f64", 8: "detect", 9: "dpar", 10: "fields"}
+PATH_NAMES = {0: "none", 1: "mlp1", 2: "mlp2", 3: "mfma", 4: "tables", 5: "loss_mlp", 6: "loss_tables", 7: "f64", 8: "detect", 9: "dpar", 10: "fields",
+              11: "score"}
 
 _lib = None
 

@@ -93,6 +93,7 @@ enum CnfPath {
   CNF_PATH_DPAR = 9,        // flow_dpar_kernel: one wave per conditioned dimension (dim >= 3, base -> data)
   CNF_PATH_DETECT = 8,      // per-sample condition: uniformity check + table kernels + MLP kernel, gated on the device
   CNF_PATH_FIELDS = 10,     // fields_kernel (cnf_eulerian_fields, cnf_trajectories)
+  CNF_PATH_SCORE = 11,      // score_kernel (cnf_score)
 };
 
 // ---- The dim-2 conditioner-table route, stated once (host code; no HIP call anywhere below) -------------------------

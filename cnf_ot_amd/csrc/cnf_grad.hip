@@ -645,6 +645,73 @@ __global__ __launch_bounds__(GTS_MAX, 2) void vjp_kernel(const VjpArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// score_kernel: the exact score of the flow's density (cnf_score),
+//   log rho(x, c) = -|z|^2 / 2 - D/2 log 2 pi + ildj(x, c),  z = F^-1(x, c)
+//   grad_x log rho = (dz/dx)^T (-z) + grad_x ildj
+// = the input adjoint of ONE data -> base pass seeded, from its own stash, with ybar = -z and ldbar = 1.  A kernel of
+// its own and not a mode of vjp_kernel: no ybar / ldbar loads, no gradient slabs, no staging, and nothing added to the
+// instruction stream of the training step.  A tile = GTS points of ONE slice (condition c[slice], wave-uniform).
+// ---------------------------------------------------------------------------
+struct ScoreArgs {
+  ModelArgs m;
+  const float* pts;      // [n_slices * count, D]; pts_slice_stride = 0: [count, D], the same points for every slice
+  const float* c;        // [n_slices]
+  float* score;          // [n_slices * count, D]
+  float* log_prob;       // [n_slices * count] or null
+  int64_t count, n_slices, pts_slice_stride;
+  uint32_t div_magic;
+};
+
+template <bool FAST, int DFIX = 0>
+__global__ __launch_bounds__(GTS_MAX, 2) void score_kernel(const ScoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int HDR = hdr_floats(GK);
+  const int D = DFIX ? DFIX : a.m.D, L = a.m.L, DT = D * GROW;
+  float* St = lds + PRE_FLOATS;
+  float* Aa = St + (L + 1) * DT;
+  float* Ab = Aa + DT;
+  for (int i = threadIdx.x; i < HDR; i += GTS) lds[i] = a.m.prep[i];
+  tile_consts(lds);
+  const int tid = threadIdx.x;
+  FirstAcc fa;      // (WGRAD = false: written, never read: removed by the compiler)
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { fa.Wb[j] = 0.0f; fa.Hb[j] = 0.0f; }
+#pragma unroll
+  for (int j = 0; j <= GK; ++j) fa.Db[j] = 0.0f;
+  const int64_t tiles_per_slice = (a.count + GTS - 1) / GTS, n_tiles = tiles_per_slice * a.n_slices;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t slice = tile / tiles_per_slice;
+    const int64_t tile_start = (tile - slice * tiles_per_slice) * GTS;
+    __syncthreads();
+    tile_load1(a.pts + slice * a.pts_slice_stride * D, St, D, a.div_magic, tile_start, a.count);
+    const float c = a.c[slice];
+    __syncthreads();
+    // the splines' clamps and bin searches turn a NaN / Inf coordinate into a finite point (flow_kernel): v - v is 0
+    // for a finite v and NaN otherwise
+    float poison = 0.0f;
+    for (int e = 0; e < D; ++e) { const float v = St[e * GROW + tid]; poison += v - v; }
+    const float ldsum = pass_fwd_stash<FAST, DFIX>(a.m, lds, St, c, true);
+    const float* sL = St + L * DT + tid;
+    // log_prob = -|z|^2 / 2 - D/2 log 2 pi + ildj: z and ildj are the fp32 pass's, only this sum is float64 (D FMAs
+    // per point) -- at dim 10 it reaches -70, where each of D fp32 additions would round by 4e-6
+    double base = -(D * HALF_LOG_2PI);
+    for (int e = 0; e < D; ++e) { const double z = sL[e * GROW]; base = fma(-0.5 * z, z, base); }
+    const float lp = (float)(base + (double)ldsum) + poison;
+    for (int e = 0; e < D; ++e) Aa[e * GROW + tid] = -sL[e * GROW];      // d(-|z|^2 / 2) / dz_e
+    float* ain = pass_bwd<FAST, false, DFIX>(a.m, lds, St, Aa, Ab, 1.0f, c, true, nullptr, nullptr, fa);
+    for (int e = 0; e < D; ++e) ain[e * GROW + tid] += poison;
+    const int64_t row0 = slice * a.count + tile_start;
+    if (a.log_prob && tile_start + tid < a.count) a.log_prob[row0 + tid] = lp;
+    __syncthreads();
+    const int n_el = (int)(a.count - tile_start < GTS ? a.count - tile_start : GTS) * D;      // coalesced store of the rows
+    for (int e = tid; e < GTS * D; e += GTS) {
+      const int s = a.div_magic ? (int)__umulhi((uint32_t)e, a.div_magic) : e, d = e - s * D;
+      if (e < n_el) a.score[row0 * D + e] = ain[d * GROW + s];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // The backward of ONE flow pass at dim 2 on the conditioner tables (cnf_pwl.h), with PER-PIECE SUFFICIENT
 // STATISTICS in place of per-sample weight gradients.  On a piece of a slice's table both ReLU activity patterns
 // are constant and theta, h2, h1 are affine in the conditioner's scalar input u, so every weight gradient is linear
@@ -1798,6 +1865,27 @@ extern "C" int cnf_input_vjp(CnfModel* m, int to_base, const float* pts, const f
                              const float* ybar, const float* ldbar, float* xbar, int64_t B, void* stream) {
   if (!xbar) return CNF_ERR_INVALID;
   return pass_vjp_impl(m, to_base, pts, c, c_block, ybar, ldbar, xbar, nullptr, nullptr, B, stream);
+}
+
+extern "C" int cnf_score(CnfModel* m, const float* pts, int32_t pts_shared, const float* c, int64_t n_slices,
+                         int64_t count, float* score, float* log_prob, void* stream_) {
+  if (!m || !pts || !c || !score || n_slices < 0 || count < 0) return CNF_ERR_INVALID;
+  if (!m->params_set) return CNF_ERR_INVALID;
+  if (!cnf_grad_supported(&m->cfg)) return CNF_ERR_UNSUPPORTED;
+  if (n_slices == 0 || count == 0) return CNF_OK;
+  const int D = m->cfg.dim, L = m->cfg.num_layers;
+  const int ts = pick_tile([&](int t) { return vjp_lds_bytes(D, L, t, false); });
+  const size_t lds = vjp_lds_bytes(D, L, ts, false);      // (cnf_grad_supported: the larger grad_lds_bytes fits a CU)
+  hipStream_t stream = (hipStream_t)stream_;
+  if (wait_for_params(m, stream) != CNF_OK) return CNF_ERR_HIP;
+  ScoreArgs a;
+  a.m = model_args(m); a.pts = pts; a.c = c; a.score = score; a.log_prob = log_prob;
+  a.count = count; a.n_slices = n_slices; a.pts_slice_stride = pts_shared ? 0 : count; a.div_magic = m->div_magic;
+  void (*const kernel)(const ScoreArgs) =
+    !m->fast_math ? score_kernel<false> : (D == 2 ? score_kernel<true, 2> : score_kernel<true>);
+  if (launch_backward(m, kernel, a, ((count + ts - 1) / ts) * n_slices, ts, lds, false, stream) < 0) return CNF_ERR_UNSUPPORTED;
+  m->last_path = CNF_PATH_SCORE;      // (only a call that launched reports its path)
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 
 extern "C" int cnf_kinetic_potential_vjp(CnfModel* m, const float* z, int64_t count, const float* c, int32_t S, float dt,

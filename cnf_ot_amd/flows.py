@@ -517,6 +517,30 @@ class FlowEngine:
                                            xbar.data_ptr(), B, _stream_ptr(self.device)), "cnf_input_vjp")
     return xbar
 
+  def score(self, pts, cond, shared=False, with_log_prob=False):
+    """cnf_score: the exact score grad_x log_prob of the flow's density, one fused forward + reverse pass per point --
+    the derivative itself, not the reference's difference quotient (`logprob_fd`); float32.  cond: S conditions (a
+    scalar: S = 1).  pts [S * N, D], slice s under cond[s] -- or, shared=True, the same pts [N, D] under every
+    condition.  Returns score [S * N, D], with_log_prob: (score, log_prob [S * N]) from the same launch.  Raises
+    CnfError(CNF_ERR_UNSUPPORTED) on a model the backward kernels do not serve; float64 points included."""
+    if torch.is_tensor(pts) and pts.dtype == torch.float64:
+      raise _capi.CnfError(_capi.CNF_ERR_UNSUPPORTED, "cnf_score (the backward kernels are float32)")
+    pts = self._points(pts, "score")
+    c = self.slice_conds(cond)
+    S = c.numel()
+    if S == 0:
+      raise ValueError("cond is empty")
+    if not shared and pts.shape[0] % S:
+      raise ValueError(f"cond with {S} values does not tile a batch of {pts.shape[0]}")
+    N = pts.shape[0] if shared else pts.shape[0] // S
+    out = torch.empty(S * N, self.cfg.dim, dtype=torch.float32, device=self.device)
+    lp = torch.empty(S * N, dtype=torch.float32, device=self.device) if with_log_prob else None
+    if N > 0:
+      with _OnDevice(self.device):
+        _capi.check(self.lib.cnf_score(self._h, pts.data_ptr(), 1 if shared else 0, c.data_ptr(), S, N, out.data_ptr(),
+                                       lp.data_ptr() if lp is not None else None, _stream_ptr(self.device)), "cnf_score")
+    return (out, lp) if with_log_prob else out
+
   def pass_vjp(self, pts, cond, ybar, ldbar, to_base, grad=None, want_xbar=True):
     """cnf_pass_vjp: input adjoints (returned, or None) and, into `grad`, the
     parameter gradient of one flow pass for the output adjoints (ybar, ldbar)."""
@@ -971,6 +995,27 @@ class _Apply:
     g = eng.input_vjp(xx, c, ldbar=torch.ones(xx.shape[0], device=eng.device), to_base=False)
     return g[0] if single else g
 
+  def score(self, params, pts, cond=None, with_log_prob=False):
+    """grad_x log_prob(pts; cond), exactly (FlowEngine.score): [N, D] for one condition, [S, N, D] for S conditions
+    at the same points; with_log_prob: the pair (score, log_prob [N] or [S, N]) from the same launch.  NOT one of the
+    functions of the reference's Flow tuple, which forms its scores by central differences of log_prob
+    (utils.py:366-381): an attribute of model.apply next to the tuple's eight fields."""
+    if cond is None:
+      raise ValueError("score needs `cond` (the flow is conditional, cond_shape=(1,))")
+    eng = self._engine(params, pts)
+    res = eng.score(pts, cond, shared=True, with_log_prob=with_log_prob)
+    s, lp = res if with_log_prob else (res, None)
+    S, D = eng.slice_conds(cond).numel(), eng.cfg.dim
+    if S > 1:
+      s, lp = s.reshape(S, -1, D), None if lp is None else lp.reshape(S, -1)
+    return (s, lp) if with_log_prob else s
+
+
+class _FlowApply(Flow):
+  """The reference's Flow tuple (same fields, same order) that can also carry attributes outside the tuple:
+  model.apply.score.  The attribute lives in the instance's __dict__: _replace / _make and a pickle round trip build
+  a plain tuple of the eight fields and drop it."""
+
 
 class FlowModel:
   """What the reference's driver holds after
@@ -985,8 +1030,9 @@ class FlowModel:
     self.assume_unchanged_params = bool(assume_unchanged_params)
     self._engines = {}
     a = _Apply(self)
-    self.apply = Flow(a.log_prob, a.sample, a.sample_and_log_prob, a.forward, a.inverse,
-                      a.forward_jac, a.inverse_jac, a.gauge_potential)
+    self.apply = _FlowApply(a.log_prob, a.sample, a.sample_and_log_prob, a.forward, a.inverse,
+                            a.forward_jac, a.inverse_jac, a.gauge_potential)
+    self.apply.score = a.score
 
   def engine(self, device) -> FlowEngine:
     device = torch.device(device)

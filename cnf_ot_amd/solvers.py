@@ -309,7 +309,7 @@ def rwpo_quadrature_terms(model: FlowModel, params: Params, T, beta, a, subtype,
           "ic_mass": float(sol["ic_mass"])}
 
 
-def evaluate_path(config, model: FlowModel, params: Params, times=None) -> Dict[str, Any]:
+def evaluate_path(config, model: FlowModel, params: Params, times=None, with_score=False) -> Dict[str, Any]:
   """Where along [0, T] the flow departs from the exact rwpo solution (dim 2 only; ValueError otherwise): per time of
   `times` (default: 9 equally spaced in [0, T]) on evaluate's 100 x 100 grid of [-2, 2]^2 with cell area dA, against
   applications.rwpo_reference_path, the flow's rho and velocity from one utils.eulerian_fields call.  Lists of floats:
@@ -317,7 +317,11 @@ def evaluate_path(config, model: FlowModel, params: Params, times=None) -> Dict[
     density_sq_err    sum (rho_flow - rho_t)^2                          (density_sq_err's measure, at every time)
     velocity_rel_err  sum rho_t |v_flow - vel_t|^2 / sum rho_t |vel_t|^2
     action_exact      1/2 sum rho_t |drift_t|^2 dA                      (the exact solution's kinetic term at t)
-    mass              sum rho_t dA                                      (how much of rho_t the grid holds)"""
+    mass              sum rho_t dA                                      (how much of rho_t the grid holds)
+  with_score=True adds
+    score_rel_err     sum rho_t |s_flow - s_t|^2 / sum rho_t |s_t|^2    (s_t = grad log rho_t of the exact solution,
+                                                                         s_flow the flow's exact score, model.apply.score)
+  and leaves the other entries as they are."""
   g = config["general"]
   if g["type"] != "rwpo" or g["dim"] != 2:
     raise ValueError(f"evaluate_path: defined for rwpo at dim 2 only, not {g['type']} at dim {g['dim']}")
@@ -326,24 +330,35 @@ def evaluate_path(config, model: FlowModel, params: Params, times=None) -> Dict[
   ts = np.linspace(0.0, float(T), 9) if times is None else utils._times_of(times)
   xs, pts = density_eval_points(params.flat.device)
   dA = float(xs[1] - xs[0]) ** 2
-  ref = applications.rwpo_reference_path(T, r["beta"], r["a"], r["pot_type"], ts, xs, fields=("drift", "vel"))
+  ref = applications.rwpo_reference_path(T, r["beta"], r["a"], r["pot_type"], ts, xs,
+                                         fields=("score", "drift", "vel") if with_score else ("drift", "vel"))
   flow = utils.eulerian_fields(model, params, pts, ts, rho=True, vel=True, dt=g["dt"])
   S = len(ts)
   rho = torch.exp(ref["log_rho"].reshape(S, -1))
   vel, drift = ref["vel"].reshape(S, -1, 2), ref["drift"].reshape(S, -1, 2)
   dv = ((flow["vel"].double() - vel) ** 2).sum(2)
-  return {"times": [float(t) for t in ts],
-          "density_sq_err": ((flow["rho"].double() - rho) ** 2).sum(1).tolist(),
-          "velocity_rel_err": ((rho * dv).sum(1) / (rho * (vel ** 2).sum(2)).sum(1)).tolist(),
-          "action_exact": (0.5 * dA * (rho * (drift ** 2).sum(2)).sum(1)).tolist(),
-          "mass": (dA * rho.sum(1)).tolist()}
+  res = {"times": [float(t) for t in ts],
+         "density_sq_err": ((flow["rho"].double() - rho) ** 2).sum(1).tolist(),
+         "velocity_rel_err": ((rho * dv).sum(1) / (rho * (vel ** 2).sum(2)).sum(1)).tolist(),
+         "action_exact": (0.5 * dA * (rho * (drift ** 2).sum(2)).sum(1)).tolist(),
+         "mass": (dA * rho.sum(1)).tolist()}
+  if with_score:
+    s_t = ref["score"].reshape(S, -1, 2)
+    s_flow = model.apply.score(params, pts, cond=ts).reshape(S, -1, 2)
+    ds = ((s_flow.double() - s_t) ** 2).sum(2)
+    res["score_rel_err"] = ((rho * ds).sum(1) / (rho * (s_t ** 2).sum(2)).sum(1)).tolist()
+  return res
 
 
 def print_path_errors(res: Dict[str, Any]) -> None:
-  """evaluate_path's table, one line per time"""
-  print("path errors against the exact solution:  t | density sq err | velocity rel err | exact action | mass on grid")
-  for row in zip(res["times"], res["density_sq_err"], res["velocity_rel_err"], res["action_exact"], res["mass"]):
-    print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f}".format(*row))
+  """evaluate_path's table, one line per time (the score column where evaluate_path(with_score=True) made it)"""
+  score = "score_rel_err" in res
+  print("path errors against the exact solution:  t | density sq err | velocity rel err | exact action | mass on grid"
+        + (" | score rel err" if score else ""))
+  for i, row in enumerate(zip(res["times"], res["density_sq_err"], res["velocity_rel_err"], res["action_exact"],
+                              res["mass"])):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f}".format(*row)
+          + (" | {:.3e}".format(res["score_rel_err"][i]) if score else ""))
 
 
 def evaluate_fp_path(config, model: FlowModel, params: Params, times=None, n_particles=1 << 20, h=1e-3, seed=0,

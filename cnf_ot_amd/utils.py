@@ -141,7 +141,9 @@ def _cond_of(t, dtype):
   return float(np.float32(t)) if dtype == torch.float32 else float(t)
 
 
-def _eulerian(model, params, pts_or_grid, t_array, dtype, fused, **want):
+def _eulerian(model, params, pts_or_grid, t_array, dtype, fused, exact_score=False, **want):
+  if exact_score and want.get("score"):
+    return _eulerian_exact_score(model, params, pts_or_grid, t_array, dtype, fused, **want)
   be = model.terms_backend(params)
   dim = model.cfg.dim
   ts = _times_of(t_array)
@@ -157,6 +159,30 @@ def _eulerian(model, params, pts_or_grid, t_array, dtype, fused, **want):
     if res is not None:
       return res
   return _eulerian_composed(model, params, be, g, pts, ts, dtype, **want)
+
+
+def _eulerian_exact_score(model, params, pts_or_grid, t_array, dtype, fused, score=True, dx=None, **others):
+  """The score entry from cnf_score (FlowEngine.score: one launch over all times, the points shared), every other
+  field as without the flag.  Refusals come first and nothing falls back to the difference quotient: it is another
+  quantity."""
+  be = model.terms_backend(params)
+  dim = model.cfg.dim
+  if _is_grid(pts_or_grid):
+    if pts_or_grid["section"] is not None and len(pts_or_grid["section"]) > 1:
+      raise ValueError("a mean over several sections is defined for the density alone")
+    pts = None
+  else:      # (as without the flag: the points' own dtype stands where dtype= is not given)
+    pts = pts_or_grid if torch.is_tensor(pts_or_grid) else torch.as_tensor(np.asarray(pts_or_grid))
+    dtype = pts.dtype if dtype is None else dtype
+  if dtype == torch.float64:
+    raise _capi.CnfError(_capi.CNF_ERR_UNSUPPORTED, "cnf_score (the backward kernels are float32)")
+  pts = _grid_tensors(pts_or_grid, dim, be.device, torch.float32)[0] if pts is None else pts.to(torch.float32)
+  ts = _times_of(t_array)
+  res = {"score": be.score(pts, ts, shared=True).reshape(len(ts), -1, dim)} if len(ts) else \
+    {"score": torch.empty(0, len(pts), dim, dtype=torch.float32, device=be.device)}
+  if any(others.get(k) for k in ("rho", "logp", "vel")):
+    res.update(_eulerian(model, params, pts_or_grid, t_array, dtype, fused, **others))
+  return res
 
 
 def _eulerian_composed(model, params, be, g, pts, ts, dtype, rho=False, logp=False, vel=False, score=False, dt=0.01,
@@ -208,16 +234,18 @@ def _eulerian_composed(model, params, be, g, pts, ts, dtype, rho=False, logp=Fal
 
 
 def eulerian_fields(model, params, pts_or_grid, t_array, rho=False, logp=False, vel=False, score=False, dt: float = 0.01,
-                    dx: float = 0.01, dtype=None, fused=True) -> dict:
+                    dx: float = 0.01, dtype=None, fused=True, exact_score=False) -> dict:
   """Several fields at the same points and times from ONE launch: a dict with the entries asked for -- "rho" and
   "logp" [S, N], "vel" and "score" [S, N, D] -- as `density_on_grid`, `velocity_field` and `score_field` define them
   (a monitoring pass during training: density, velocity and score on one grid).  pts_or_grid: [N, D] points or a
-  `field_grid`; with several sections only rho is defined."""
+  `field_grid`; with several sections only rho is defined.  exact_score=True: the score entry is the derivative
+  grad_x log_prob itself (`score_field(exact=True)`: a launch of its own, dx ignored), the other entries come from
+  the fused launch as before."""
   model = _model_of(model)
   if not (rho or logp or vel or score):
     raise ValueError("eulerian_fields: ask for at least one field")
-  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, rho=rho, logp=logp, vel=vel, score=score, dt=dt,
-                   dx=dx)
+  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, exact_score=exact_score, rho=rho, logp=logp,
+                   vel=vel, score=score, dt=dt, dx=dx)
 
 
 def density_on_grid(log_prob_fn_or_model, params, t_array, domain_range, n=100, axes=(0, 1), fixed=None, section=None,
@@ -240,12 +268,17 @@ def velocity_field(model, params, pts_or_grid, t_array, dt: float = 0.01, dtype=
   return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, vel=True, dt=dt)["vel"]
 
 
-def score_field(model, params, pts_or_grid, t_array, dx: float = 0.01, dtype=None, fused=True) -> torch.Tensor:
+def score_field(model, params, pts_or_grid, t_array, dx: float = 0.01, dtype=None, fused=True, exact=False) -> torch.Tensor:
   """The score of the flow's density by the reference's central differences in x, [S, N, D]:
   (log_prob(r + dx/2 e_d) - log_prob(r - dx/2 e_d)) / dx (utils.py:366-381 with general.dx; what plot_velocity_field
-  / plot_score evaluate on their grids)."""
+  / plot_score evaluate on their grids).
+  exact=True: the derivative grad_x log_prob itself, not the reference's difference quotient -- one fused forward +
+  reverse pass per point (cnf_score), dx ignored, float32 (a grid's points are its float64 coordinates rounded to
+  float32).  On a model cnf_score does not serve (periodized, a network other than hidden 16 / 2 layers / 5 bins,
+  dim > 14) and for dtype=torch.float64 it raises CnfError(CNF_ERR_UNSUPPORTED): there is no fall-back to the
+  quotient, which is a different quantity."""
   model = _model_of(model)
-  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, score=True, dx=dx)["score"]
+  return _eulerian(model, params, pts_or_grid, t_array, dtype, fused, exact_score=exact, score=True, dx=dx)["score"]
 
 
 def trajectories(model, params, r_, t_array, t0: float = 0.0, with_velocity: bool = False, dt: float = 0.01, dtype=None,

@@ -149,7 +149,8 @@ int cnf_model_set_precise(CnfModel *m, int on);
 
 /* Which kernels the most recent compute call on this model ran: 1/2 = MLP flow
  * kernel with one / two samples per lane, 3 = MFMA conditioner, 4 = conditioner
- * tables, 5/6 = fused loss kernel on the MLP / on tables, 7 = float64, 10 = the fused field kernel. */
+ * tables, 5/6 = fused loss kernel on the MLP / on tables, 7 = float64, 10 = the fused field kernel,
+ * 11 = the exact-score kernel (cnf_score). */
 int cnf_model_last_path(const CnfModel *m);
 
 /* Replaces: model.apply.forward(params, x, c) = flow.bijector.forward, and
@@ -429,6 +430,27 @@ int cnf_logprob_fd_vjp(CnfModel *m, const float *pts, const float *c,
                        int64_t c_block, float dx, const float *gbar,
                        float *pts_bar, float *grad, const float *params,
                        int64_t B, void *stream);
+
+/* The exact score of the flow's density and, optionally, log_prob, from ONE launch:
+ *   score[s*count + i, :] = grad_x log_prob(x_si; c[s]),   log_prob[s*count + i]  (may be NULL)
+ * for n_slices conditions c[s] and `count` points per slice: pts [n_slices*count, D], or, with pts_shared != 0,
+ * the same [count, D] points for every slice (a grid at several times).  This is the derivative that the
+ * reference's difference quotient (log_prob(r + dx/2 e_d) - log_prob(r - dx/2 e_d)) / dx approximates
+ * (utils.py:366-381, applications.py:264-273; cnf_logprob_fd is that quotient): with z = F^-1(x, c),
+ *   log_prob = -|z|^2 / 2 - D/2 log 2 pi + ildj,   grad_x log_prob = (dz/dx)^T (-z) + grad_x ildj,
+ * one data -> base pass with its layer inputs kept and its reverse pass seeded with (-z, 1) -- what
+ * cnf_inverse_logdet + a negation + cnf_input_vjp(to_base = 1) compose from two forward passes; no dx, and one
+ * reverse pass where the quotient takes 2 D forward passes.  An evaluation quantity: the loss terms keep the
+ * reference's quotient.  fp32: the base point z and ildj come from the plain-fp32 pass (not the precise position
+ * path); log_prob alone is summed in float64 from those fp32 values and rounded once, so it is close to, but not
+ * bit for bit, what cnf_log_prob gives under cnf_model_set_precise(0).  A non-finite point gives a non-finite score
+ * row and log_prob for that point only.
+ * Checks come first: CNF_ERR_INVALID for NULL pts / c / score, negative sizes or parameters not set;
+ * CNF_ERR_UNSUPPORTED (nothing written or enqueued) where cnf_grad_supported is false.  n_slices == 0 or count == 0:
+ * CNF_OK, no launch.  Neither allocates nor synchronises (legal inside a stream capture) and needs no
+ * cnf_grad_enable: no gradient slab is written. */
+int cnf_score(CnfModel *m, const float *pts, int32_t pts_shared, const float *c,
+              int64_t n_slices, int64_t count, float *score, float *log_prob, void *stream);
 
 /* The score terms' value AND backward in one launch (value_and_grad of kinetic_with_score_loss_fn /
  * flow_matching_loss_fn, applications.py:245-374, composed from separate flow launches -- the form
