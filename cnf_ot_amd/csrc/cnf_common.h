@@ -62,6 +62,8 @@ struct CnfModel {
   int64_t grad_max_blocks;
   int use_pwl;            // 1: piecewise-linear conditioner tables at dim 2 (cnf_pwl.h)
   int use_dpar;           // 1: wave-per-dimension kernel for small base -> data launches at dim >= 3
+  int pwl_builder;        // table builder: 0 by table count (default), 1 the reference builder, 2 the lean one
+  int last_pwl_builder;   // the builder (1 / 2) of the most recent table build, 0 before the first
   // table workspaces [sets][L][PWL_TBL], one per stream (calls on different streams never share one).
   // Allocated ONLY by cnf_model_reserve; the compute entry points look theirs up and never allocate.
   // cnf_grad_enable: per-piece gradient statistics of the table backward (cnf_grad.hip), PWL_STAT_SLICES slices

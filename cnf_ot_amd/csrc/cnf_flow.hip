@@ -1110,11 +1110,26 @@ static int slice_plan(CnfModel* m, hipStream_t stream, int64_t slice_len, int64_
 }
 
 // Enqueues the tables of ns slices, conditions c[0 .. ns) + offset, into `tables`
-static void build_tables(const CnfModel* m, hipStream_t stream, const float* c, float offset, int64_t ns,
-                         float* tables) {
+// with the lean builder (one wave per table) from PWL_LEAN_MIN_TABLES tables up, below it the reference builder (512
+// threads per table); cnf_model_set_pwl_builder forces either.  Both write the same bytes.
+// A lone wave takes ~30 us for its table, with 16 tables in flight per CU (one round up to 4 096 tables); the
+// reference builder takes ~11 us per round of 2 tables per CU, 512 tables: 10.6 us against ~30 at 32 and 96 tables,
+// 13 against ~32 at 512, 36 against 39 at 1 536, 46 against 41 at 2 048, 89 against 56 at 4 096 (measured: profiles/r06_lean_builder has both
+// builders from 32 to 4 096 tables).  The sampling step's chunks (4 096 and 3 616 tables) are above the crossover, the
+// loss and backward paths (32 - 96) below.
+constexpr int64_t PWL_LEAN_MIN_TABLES = 2048;
+static void build_tables(CnfModel* m, hipStream_t stream, const float* c, float offset, int64_t ns, float* tables) {
   const int L = m->cfg.num_layers;
-  hipLaunchKernelGGL(cnf::pwl_build_kernel, dim3((unsigned)(ns * L)), dim3(512), 0, stream,
-                     (const float*)(m->prep + cnf::hdr_floats(5)), m->per_layer, c, offset, L, m->scd.sp_offset, tables);
+  const float* w = m->prep + cnf::hdr_floats(5);
+  const bool lean = m->pwl_builder == 0 ? ns * L >= PWL_LEAN_MIN_TABLES : m->pwl_builder != 1;
+  m->last_pwl_builder = lean ? 2 : 1;
+  const dim3 grid((unsigned)(ns * L));
+  if (!lean)
+    hipLaunchKernelGGL(cnf::pwl_build_kernel, grid, dim3(512), 0, stream, w, m->per_layer, c, offset, L,
+                       m->scd.sp_offset, tables);
+  else
+    hipLaunchKernelGGL(cnf::pwl_build_lean_kernel<64>, grid, dim3(64), 0, stream, w, m->per_layer, c, offset, L,
+                       m->scd.sp_offset, tables);
 }
 
 typedef void (*PwlKernel)(const cnf::PwlArgs);
@@ -1233,6 +1248,18 @@ int cnf_internal_build_tables(CnfModel* m, hipStream_t stream, const float* c, i
   pwl_workspace(m, stream, tables, &sets);
   if (sets < n) return CNF_ERR_UNSUPPORTED;
   build_tables(m, stream, c, 0.0f, n, *tables);
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
+// Test / measurement entry point (cnf_ot_amd_debug.h): the table sets of n conditions c[0 .. n) + c_offset, built by the
+// builder the knob selects, into the caller's device buffer out[n, L, PWL_TBL]
+extern "C" int cnf_internal_build_tables_into(CnfModel* m, void* stream, const float* c, float c_offset, int64_t n,
+                                              float* out) {
+  if (!m || !c || !out || n < 1 || n * m->cfg.num_layers > (1 << 30)) return CNF_ERR_INVALID;
+  if (!m->params_set) return CNF_ERR_INVALID;
+  if (!pwl_network(m->cfg) || (reinterpret_cast<uintptr_t>(out) & 15)) return CNF_ERR_UNSUPPORTED;
+  if (wait_for_params(m, (hipStream_t)stream) != CNF_OK) return CNF_ERR_HIP;
+  build_tables(m, (hipStream_t)stream, c, c_offset, n, out);
   return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 

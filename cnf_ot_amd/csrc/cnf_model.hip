@@ -208,6 +208,19 @@ extern "C" int cnf_model_set_pwl(CnfModel* m, int mode) {
   return CNF_OK;
 }
 
+/* Internal knob: which kernel builds the dim-2 tables -- 0 = by table count (default; build_tables in cnf_flow.hip),
+ * 1 = the reference builder (pwl_build_kernel), 2 = the lean builder (pwl_build_lean_kernel<64>).  Both write the same
+ * bytes. */
+extern "C" int cnf_model_set_pwl_builder(CnfModel* m, int mode) {
+  if (!m || mode < 0 || mode > 2) return CNF_ERR_INVALID;
+  m->pwl_builder = mode;
+  return CNF_OK;
+}
+
+/* The builder the most recent table build ran (1 / 2); 0 before the first build.  A plain field, like last_path:
+ * meaningful only while one host thread calls into the model. */
+extern "C" int cnf_model_last_pwl_builder(const CnfModel* m) { return m ? m->last_pwl_builder : CNF_ERR_INVALID; }
+
 /* 1 (default): cnf_log_prob / cnf_inverse_logdet (data -> base) carry the knot positions, the offset in the
  * bin and the base term in float64 (cnf_device.h "precise position path"); 0: plain fp32 throughout. */
 extern "C" int cnf_model_set_precise(CnfModel* m, int on) {

@@ -250,6 +250,31 @@ class FlowEngine:
     _capi.check(self.lib.cnf_model_set_pwl(self._h, int(mode)), "cnf_model_set_pwl")
     self._pwl_mode = int(mode)
 
+  def set_pwl_builder(self, mode: int) -> None:
+    """Which kernel builds the tables: 0 = by table count (default), 1 = the
+    reference builder, 2 = the lean one (one wave per table)."""
+    _capi.check(self.lib.cnf_model_set_pwl_builder(self._h, int(mode)), "cnf_model_set_pwl_builder")
+
+  def last_pwl_builder(self) -> int:
+    """The builder the most recent table build ran (0: none yet)."""
+    return self.lib.cnf_model_last_pwl_builder(self._h)
+
+  def build_tables(self, c: torch.Tensor, c_offset: float = 0.0, out: torch.Tensor = None) -> torch.Tensor:
+    """The table sets of the conditions `c + c_offset`, built by the selected
+    builder: float32 [n, L, PWL_TBL] (tests and measurements only).  `out`: a
+    contiguous float32 buffer of that shape to build into (rows past a table's
+    last piece are not written)."""
+    c = c.to(self.device, torch.float32).contiguous().reshape(-1)
+    per = self.lib.cnf_model_table_bytes(self._h) // (4 * self.cfg.num_layers)
+    shape = (c.numel(), self.cfg.num_layers, per)
+    if out is None:
+      out = torch.empty(shape, dtype=torch.float32, device=self.device)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+      raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.device}")
+    _capi.check(self.lib.cnf_internal_build_tables_into(self._h, _stream_ptr(self.device), c.data_ptr(), float(c_offset),
+                                                        c.numel(), out.data_ptr()), "cnf_internal_build_tables_into")
+    return out
+
   def set_dpar(self, mode: int) -> None:
     """Wave-per-dimension kernel for base -> data at dim >= 3: 1 = chosen by
     batch size (default), 2 = always, 0 = never."""

@@ -27,6 +27,18 @@ int cnf_model_set_mfma(CnfModel *m, int mode);
 /* dim-2 conditioner tables: 1 (default) for large launches, 2 whenever they apply, 0 never. */
 int cnf_model_set_pwl(CnfModel *m, int mode);
 
+/* which kernel builds the dim-2 conditioner tables: 0 (default) by table count, 1 the reference builder (512 threads per
+ * table), 2 the lean builder (one wave per table).  Both write the same table bytes.  cnf_model_last_pwl_builder: what
+ * the most recent build ran (1 / 2; 0 before the first) -- an unsynchronised field like cnf_model_last_path, only
+ * meaningful while a single host thread calls into the model. */
+int cnf_model_set_pwl_builder(CnfModel *m, int mode);
+int cnf_model_last_pwl_builder(const CnfModel *m);
+
+/* Builds the table sets of the n conditions c[0 .. n) + c_offset (device) with the selected builder into the
+ * caller's device buffer out[n, L, PWL_TBL] (cnf_model_table_bytes per condition; 16-byte aligned), on `stream`.
+ * Nothing else shows table bytes: the builder tests compare them. */
+int cnf_internal_build_tables_into(CnfModel *m, void *stream, const float *c, float c_offset, int64_t n, float *out);
+
 /* wave-per-dimension kernel (base -> data, dim >= 3): 1 (default) by batch size, 2 always, 0 never. */
 int cnf_model_set_dpar(CnfModel *m, int mode);
 
