@@ -81,6 +81,9 @@ __device__ __forceinline__ Potential<float> potential(v2f x, int subtype, float 
 
 // The reverse-KL target log(N(y;0,vs I) ws + N(y;0,vt I) wt) at condition t as a log-sum-exp (applications.py:136-163),
 // and g = -(d/dy_e) of it / y_e.  FAST folds -1/(2 v) into one constant; otherwise the exponent divides by v.
+// The weights enter the exponents as log |w| and their signs multiply afterwards, so the maximum is over the WEIGHTED
+// exponents and the larger term is exp(0): a zero weight (ws at t == T, wt at t == 0) is -inf, and its component drops
+// out of the maximum and of the sum however far its exponent lies above the other's.
 template <class T> struct RklMix { T logmix, g; };
 
 template <bool FAST, class T, class X>
@@ -89,7 +92,9 @@ __device__ __forceinline__ RklMix<T> rkl_mixture(X y, int D, float t, float Tt, 
   const T s2 = sq_norm<T>(y, D);
   const float vs = 2.0f / beta * (Tt + 1.0f), vt = 2.0f / beta;
   const float ws = (Tt - t) / Tt, wt = t / Tt;
-  const float ls = -0.5f * D * logf(6.283185307179586f * vs), lt = -0.5f * D * logf(6.283185307179586f * vt);
+  const float ss = copysignf(1.0f, ws), st = copysignf(1.0f, wt);
+  const float ls = -0.5f * D * logf(6.283185307179586f * vs) + logf(fabsf(ws));
+  const float lt = -0.5f * D * logf(6.283185307179586f * vt) + logf(fabsf(wt));
   T as, at;
   if constexpr (FAST) {
     as = vfma(s2, splat<T>(-0.5f / vs), splat<T>(ls));
@@ -99,7 +104,7 @@ __device__ __forceinline__ RklMix<T> rkl_mixture(X y, int D, float t, float Tt, 
     at = s2 * -0.5f / vt + lt;
   }
   const T mx = vmax(as, at);
-  const T es = M::exp(as - mx) * ws, et = M::exp(at - mx) * wt;
+  const T es = M::exp(as - mx) * ss, et = M::exp(at - mx) * st;
   return RklMix<T>{mx + M::log(es + et), (es / vs + et / vt) / (es + et)};
 }
 

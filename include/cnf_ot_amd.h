@@ -484,7 +484,10 @@ int cnf_score_fd_vjp(CnfModel *m, const float *r, const float *c, int64_t count,
  *
  * cnf_rkl_residual: y [n, D], lp [n] from cnf_sample_logprob;
  * sum = sum_i lp_i - log(mixture(y_i)) of reverse_kl_loss_fn
- * (applications.py:129-163), adjoints ybar / lpbar likewise. */
+ * (applications.py:129-163), adjoints ybar / lpbar likewise.  The mixture is
+ * a log-sum-exp over the WEIGHTED exponents: at t == 0 and t == T the
+ * component of weight zero drops out, and sum, ybar stay finite wherever the
+ * remaining density is representable as a float32 logarithm. */
 /* cnf_term_residual: value and adjoints of the kinetic / potential / density-fit terms composed from separate flow
  * launches (kinetic_loss_fn applications.py:220-242: r = [r1 | r2], 2 n points, p0 = dt; potential_loss_fn :176-205:
  * r = n points, subtype = CnfPotential (else CNF_ERR_INVALID), p0 = a; kl_loss_fn :11-86: r = the recovered base
