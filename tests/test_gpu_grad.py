@@ -13,6 +13,7 @@ Tolerance: |g_gpu - g_fd|_inf <= 5e-3 * |g_fd|_inf for the finite-difference
 terms (their per-sample velocities are fp32 differences divided by dt = 0.01,
 and the gradient is a difference of two such Jacobian products), 1e-3 for the
 direct terms.  Measured values are printed.
+Every parameter of every tensor, at more shapes and at float32-noise bounds: test_gpu_flow_adjoint.py (analytic float64 adjoint).
 """
 import os
 import sys
