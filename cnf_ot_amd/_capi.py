@@ -46,6 +46,21 @@ class CnfLossSpec(ctypes.Structure):
   ]
 
 
+TARGET_MAX_COMP, TARGET_MAX_DIM = 8, 14
+
+
+class CnfTargetSpec(ctypes.Structure):
+  """A Gaussian mixture with a shared covariance shape (include/cnf_ot_amd.h); applications.GaussianMixtureTarget packs it."""
+  _fields_ = [
+    ("n_comp", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ("mean", (ctypes.c_double * TARGET_MAX_DIM) * TARGET_MAX_COMP),
+    ("log_weight", ctypes.c_double * TARGET_MAX_COMP),
+    ("W", (ctypes.c_double * TARGET_MAX_DIM) * TARGET_MAX_DIM),
+    ("log_det_W", ctypes.c_double),
+    ("scale", ctypes.c_void_p),
+  ]
+
+
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
 TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
@@ -135,6 +150,12 @@ SYMBOLS = {
                                       ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _I64, _P]),
   "cnf_point_stats": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CnfFieldGrid), _P, _P, _P,
                                      _I64, _P]),
+  # importance-sampling diagnostics against a closed-form density: stats [n_slices, 5] doubles (m, s1, s2, c, n)
+  "cnf_importance_workspace": (ctypes.c_int, [_I64, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_importance_stats": (ctypes.c_int, [_P, ctypes.POINTER(CnfTargetSpec), _P, ctypes.c_int, _P, _I64, _I64, _P, _P, _I64,
+                                          _P]),
+  "cnf_importance_stats_seeded": (ctypes.c_int, [_P, ctypes.POINTER(CnfTargetSpec), _U64, _I64, _I64, _P, _I64, _I64, _P, _P,
+                                                 _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),
@@ -154,7 +175,7 @@ _INTERNAL = {
                                             ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
 }
 PATH_NAMES = {0: "none", 1: "mlp1", 2: "mlp2", 3: "mfma", 4: "tables", 5: "loss_mlp", 6: "loss_tables", 7: "f64", 8: "detect", 9: "dpar", 10: "fields",
-              11: "score"}
+              11: "score", 12: "importance"}
 
 _lib = None
 

@@ -950,6 +950,160 @@ def fp_reference_particles(dim, T, a, sigma, subtype, times, n_particles=1 << 20
   return out
 
 
+# ---- importance-sampling diagnostics against the densities known in closed form -------------------------------------
+# The reference's kl_ess (tests/test_fit_prob.py:50-56, "metrics used in the tori paper"): draw y from the flow, weight
+# w = p_target(y) / q_flow(y), report Z = mean w, KL = mean(log q - log p) + log Z, ESS = (sum w)^2 / sum w^2.  It
+# divides in linear space, where sum w underflows to 0 as soon as the flow is far from its target; here one fused
+# launch (cnf_importance_stats) returns, per time, the raw state of the LOG-weights l = log p - log q,
+#   (m, s1, s2, c, n) = (max l, sum exp(l - m), sum exp(2 (l - m)), sum l, count),
+# which merges exactly across ranks and calls (merge_importance_stats) and gives the three numbers in log space.
+
+class GaussianMixtureTarget:
+  """The packer of CnfTargetSpec: sum_m weights[m] N(means[m], scale * cov), up to 8 components and dim 14.  means
+  [n_comp, D] (or [D]: one component); cov: None = I, a scalar v = v I, or a symmetric positive definite [D, D]
+  matrix; weights: None = uniform, else positive numbers (normalised here).  `scale` is a per-time factor of the
+  covariance given with the call, not part of the target.  ValueError for a covariance that is not positive definite,
+  more than 8 components or dim > 14."""
+
+  def __init__(self, means, cov=None, weights=None):
+    mu = np.atleast_2d(np.asarray(means, dtype=np.float64))
+    if mu.ndim != 2 or mu.shape[0] < 1 or mu.shape[1] < 1:
+      raise ValueError(f"GaussianMixtureTarget: means must be [n_comp, D], got {np.shape(means)}")
+    n, D = mu.shape
+    if n > _capi.TARGET_MAX_COMP:
+      raise ValueError(f"GaussianMixtureTarget: {n} components, at most {_capi.TARGET_MAX_COMP}")
+    if D > _capi.TARGET_MAX_DIM:
+      raise ValueError(f"GaussianMixtureTarget: dim {D}, at most {_capi.TARGET_MAX_DIM}")
+    if cov is None:
+      A = np.eye(D)
+    elif np.ndim(cov) == 0:
+      A = float(cov) * np.eye(D)
+    else:
+      A = np.asarray(cov, dtype=np.float64)
+      if A.shape != (D, D) or not np.allclose(A, A.T, rtol=1e-12, atol=0.0):
+        raise ValueError(f"GaussianMixtureTarget: cov must be a symmetric [{D}, {D}] matrix")
+    if not np.all(np.isfinite(A)) or not np.all(np.isfinite(mu)):
+      raise ValueError("GaussianMixtureTarget: means and cov must be finite")
+    try:
+      L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+      raise ValueError("GaussianMixtureTarget: cov is not positive definite") from None
+    # cov = L L^T, so cov^-1 = W^T W with the lower-triangular W = L^-1
+    W = np.tril(np.linalg.solve(L, np.eye(D)))
+    w = np.full(n, 1.0 / n) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (n,) or not np.all(np.isfinite(w)) or not np.all(w > 0.0):
+      raise ValueError(f"GaussianMixtureTarget: weights must be {n} positive numbers")
+    self.dim, self.n_comp = D, n
+    self.means, self.cov, self.W = mu, A, W
+    self.log_weights = np.log(w / w.sum())
+    self.log_det_W = -float(np.log(np.diag(L)).sum())
+    s = self.spec = _capi.CnfTargetSpec()
+    s.n_comp = n
+    for i in range(n):
+      s.log_weight[i] = self.log_weights[i]
+      for d in range(D):
+        s.mean[i][d] = mu[i, d]
+    for i in range(n, _capi.TARGET_MAX_COMP):
+      s.log_weight[i] = -math.inf
+    for i in range(_capi.TARGET_MAX_DIM):      # (identity past D: the struct is valid at any dimension's checks)
+      s.W[i][i] = 1.0
+    for i in range(D):
+      for j in range(i + 1):
+        s.W[i][j] = W[i, j]
+    s.log_det_W = self.log_det_W
+    s.scale = None
+
+
+# the times of the fp figure (solvers.FIGURE_SETTINGS[("fp", None, 2)]): where fp / ou reports its fit along the path
+FP_FIT_TIMES = (0.0, 0.05, 0.1, 0.3, 1.0)
+
+
+def known_densities(config):
+  """[(t, target, scale)]: every density of `config`'s problem that is known in closed form, as a target of
+  `importance_stats` at condition t (scale: the variance factor of the target's covariance at that time, or None).
+    ot:   the configured source (ot.source, default "mixture": the 8-mode mixture of applications.py:34-71, or
+          "gaussian": N(-3 1, A); both dim 2) at 0 and N(0, I) at T = 1
+    rwpo: the initial condition N(0, 2 (T + 1) / beta I) at 0
+    fp:   the initial condition N(0, (T + 1) / 2 I) at 0; with the OU drift the exact density
+          N(0, ou_variance(t) I) at the figure's times (one unit-covariance target, the variances as scales)"""
+  g = config["general"]
+  _type, dim = g["type"], g["dim"]
+  zero = np.zeros((1, dim))
+  if _type == "ot":
+    out = []
+    source = config["ot"].get("source", "mixture")
+    if dim == 2 and source == "mixture":
+      out.append((0.0, GaussianMixtureTarget(MIXTURE_CENTERS.astype(np.float64)), None))
+    elif dim == 2 and source == "gaussian":
+      out.append((0.0, GaussianMixtureTarget([[-3.0, -3.0]], np.array([[5.0, 1.0], [1.0, 0.5]])), None))
+    return out + [(1.0, GaussianMixtureTarget(zero), None)]
+  if _type == "rwpo":
+    r = config["rwpo"]
+    return [(0.0, GaussianMixtureTarget(zero, rwpo_initial_variance(r["T"], r["beta"])), None)]
+  if _type == "fp":
+    f = config["fp"]
+    T, var0 = float(f["T"]), fp_initial_variance(f["T"])
+    if f["velocity_field_type"] != "ou":
+      return [(0.0, GaussianMixtureTarget(zero, var0), None)]
+    unit = GaussianMixtureTarget(zero)
+    times = sorted({t for t in FP_FIT_TIMES if t < T} | {T})
+    return [(t, unit, ou_variance(t, f["a"], var0, f["sigma"])) for t in times]
+  raise Exception(f"Unknown problem type: {_type}...")
+
+
+def merge_importance_stats(parts) -> torch.Tensor:
+  """Merges raw [S, 5] blocks (m, s1, s2, c, n) of disjoint sample sets into the block of their union, in float64, part
+  by part in the order given: the scaled sums are brought to the common maximum, c and n add.  An empty block
+  (m = -inf, zeros) is a no-op; a slice that is NaN in one block stays NaN."""
+  parts = [torch.as_tensor(p, dtype=torch.float64) for p in parts]
+  if not parts:
+    raise ValueError("merge_importance_stats: nothing to merge")
+  out = parts[0].clone()
+  for p in parts[1:]:
+    p = p.to(out.device)
+    m = torch.maximum(out[:, 0], p[:, 0])
+    empty = m == -math.inf
+    ea = torch.where(empty, torch.zeros_like(m), torch.exp(out[:, 0] - m))
+    eb = torch.where(empty, torch.zeros_like(m), torch.exp(p[:, 0] - m))
+    out = torch.stack([m, out[:, 1] * ea + p[:, 1] * eb, out[:, 2] * ea * ea + p[:, 2] * eb * eb, out[:, 3] + p[:, 3],
+                       out[:, 4] + p[:, 4]], 1)
+  return out
+
+
+def importance_summary(raw: torch.Tensor):
+  """The numbers of a raw [S, 5] block, each a float64 [S] tensor: log_Z = log mean w, KL = mean(log q - log p) + log_Z,
+  ess = (sum w)^2 / sum w^2 (in [1, n]), ess_pct = 100 ess / n, max_log_w; and the block itself as `raw`."""
+  raw = torch.as_tensor(raw, dtype=torch.float64)
+  m, s1, s2, c, n = raw.unbind(1)
+  log_Z = torch.log(s1) + m - torch.log(n)
+  ess = torch.exp(2.0 * torch.log(s1) - torch.log(s2))
+  return {"log_Z": log_Z, "KL": -c / n + log_Z, "ess": ess, "ess_pct": 100.0 * ess / n, "max_log_w": m, "n": n, "raw": raw}
+
+
+def importance_stats(model, params, target, conds, rng, batch_size, scale=None, shard=None):
+  """The importance-sampling fit of the flow at the times `conds` against `target` (GaussianMixtureTarget; scale: the
+  covariance factor per time, or None): `importance_summary` of batch_size samples per time, time s drawing samples
+  [s batch_size, (s + 1) batch_size) of the stream of `rng` inside the kernel -- ONE fused launch, nothing but 5
+  doubles per time returned.  Sharded (shard, default: the torch.distributed world): a rank takes its shard_range of
+  every time's samples, the raw blocks are all-gathered and merged in rank order, so every rank returns the same
+  numbers, independent of the rank count beyond rounding.  A shard given without an initialised process group cannot
+  gather: the rank's own block comes back, to be merged by the caller (merge_importance_stats on `raw`)."""
+  if target.dim != model.cfg.dim:
+    raise ValueError(f"importance_stats: a target of dim {target.dim} for a flow of dim {model.cfg.dim}")
+  shard = shard if shard is not None else current_shard()
+  be = model.terms_backend(params)
+  start, count = shard_range(batch_size, shard)
+  raw = be.importance_stats(target, t=_conds(conds), B=count, seed=rng, first_sample=start, slice_stride=int(batch_size),
+                            scale=scale)
+  if shard.world > 1:
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+      blocks = [torch.empty_like(raw) for _ in range(shard.world)]
+      dist.all_gather(blocks, raw, group=shard.group)
+      raw = merge_importance_stats(blocks)
+  return importance_summary(raw)
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

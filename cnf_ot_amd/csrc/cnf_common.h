@@ -1,6 +1,7 @@
 // cnf_common.h -- structs shared by the translation units of libcnf_ot_amd.so that work on a CnfModel (cnf_model.hip,
-// cnf_rng.hip, cnf_flow.hip, cnf_grad.hip): the model object, the kernels' view of it, the dim-2 table route, the
-// list of compiled shapes and the argument checks.  The declarations of functions that cross units: cnf_host.h.
+// cnf_rng.hip, cnf_flow.hip, cnf_grad.hip, cnf_importance.hip): the model object, the kernels' view of it, the dim-2
+// table route, the list of compiled shapes, the argument checks and the launch tail.  The declarations of functions
+// that cross units: cnf_host.h.
 #pragma once
 #include <mutex>
 #include <map>
@@ -96,6 +97,7 @@ enum CnfPath {
   CNF_PATH_DETECT = 8,      // per-sample condition: uniformity check + table kernels + MLP kernel, gated on the device
   CNF_PATH_FIELDS = 10,     // fields_kernel (cnf_eulerian_fields, cnf_trajectories)
   CNF_PATH_SCORE = 11,      // score_kernel (cnf_score)
+  CNF_PATH_IMPORTANCE = 12, // importance_kernel + importance_finish_kernel (cnf_importance_stats)
 };
 
 // ---- The dim-2 conditioner-table route, stated once (host code; no HIP call anywhere below) -------------------------
@@ -170,6 +172,36 @@ static inline bool ensure_lds(K kernel, size_t bytes) {
   const bool ok = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
   done[key] = ok;
   return ok;
+}
+
+// profiling helpers: a record is opened before the (optional) build kernel and closed after the flow kernel
+// (samples < 0: a launch that is not recorded)
+struct ProfScope {
+  CnfModel* m; hipStream_t s; CnfModel::ProfRec r; bool on;
+  ProfScope(CnfModel* m_, hipStream_t s_, bool with_build, int64_t samples, int path) : m(m_), s(s_), on(false) {
+    r.e0 = r.e1 = r.e2 = nullptr; r.samples = samples; r.path = path;
+    if (!m->profiling || samples < 0 || m->prof.size() >= 4096) return;
+    if (hipEventCreate(&r.e1) != hipSuccess || hipEventCreate(&r.e2) != hipSuccess) return;
+    if (with_build) { if (hipEventCreate(&r.e0) != hipSuccess) return; (void)hipEventRecord(r.e0, s); }
+    else (void)hipEventRecord(r.e1, s);
+    on = true;
+  }
+  void built() { if (on && r.e0) (void)hipEventRecord(r.e1, s); }
+  void done() { if (on) { (void)hipEventRecord(r.e2, s); m->prof.push_back(r); on = false; } }
+};
+
+// The one tail of every kernel family's launch: report `path` (cnf_model_last_path) -- unless the launch is gated on
+// the device: its call has reported CNF_PATH_DETECT --, opt in to the LDS, launch `threads` per workgroup and map the
+// launch error.  prof_samples >= 0: a kernel of the flow entry points, timed under cnf_model_set_profiling.
+template <class K, class A>
+static int launch(CnfModel* m, K kernel, int64_t grid, int threads, size_t lds, hipStream_t stream, const A& a, int path,
+                  bool gated = false, int64_t prof_samples = -1) {
+  if (!gated) m->last_path = path;
+  if (!ensure_lds(kernel, lds)) return CNF_ERR_UNSUPPORTED;
+  ProfScope ps(m, stream, false, prof_samples, path);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
+  ps.done();
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 
 // Workgroups of `kernel` (threads, dynamic LDS bytes) that fit on one CU at a time (registers, LDS, waves), cached.

@@ -950,22 +950,6 @@ extern "C" int cnf_model_set_params(CnfModel* m, const float* params, void* stre
 }
 
 
-// profiling helpers: a record is opened before the (optional) build kernel and closed after the flow kernel
-// (samples < 0: a launch that is not recorded)
-struct ProfScope {
-  CnfModel* m; hipStream_t s; CnfModel::ProfRec r; bool on;
-  ProfScope(CnfModel* m_, hipStream_t s_, bool with_build, int64_t samples, int path) : m(m_), s(s_), on(false) {
-    r.e0 = r.e1 = r.e2 = nullptr; r.samples = samples; r.path = path;
-    if (!m->profiling || samples < 0 || m->prof.size() >= 4096) return;
-    if (hipEventCreate(&r.e1) != hipSuccess || hipEventCreate(&r.e2) != hipSuccess) return;
-    if (with_build) { if (hipEventCreate(&r.e0) != hipSuccess) return; (void)hipEventRecord(r.e0, s); }
-    else (void)hipEventRecord(r.e1, s);
-    on = true;
-  }
-  void built() { if (on && r.e0) (void)hipEventRecord(r.e1, s); }
-  void done() { if (on) { (void)hipEventRecord(r.e2, s); m->prof.push_back(r); on = false; } }
-};
-
 constexpr int CNF_MFMA_SMALL_WAVES = 4;        // waves of single-lane work per SIMD up to which use_mfma = 2 picks MFMA
 
 // Two samples per lane (packed fp32) once the batch fills every SIMD with at
@@ -978,20 +962,7 @@ static int samples_per_lane(const CnfModel* m, int64_t B) {
   return (m->fast_math && B >= (int64_t)m->num_cus * 4 * 64 * 2) ? 2 : 1;
 }
 
-// The one tail of every kernel family's launch: report `path` (cnf_model_last_path) -- unless the launch is gated on
-// the device: its call has reported CNF_PATH_DETECT --, opt in to the LDS, launch `threads` per workgroup and map the
-// launch error.  prof_samples >= 0: a kernel of the flow entry points, timed under cnf_model_set_profiling.
-template <class K, class A>
-static int launch(CnfModel* m, K kernel, int64_t grid, int threads, size_t lds, hipStream_t stream, const A& a, int path,
-                  bool gated = false, int64_t prof_samples = -1) {
-  if (!gated) m->last_path = path;
-  if (!ensure_lds(kernel, lds)) return CNF_ERR_UNSUPPORTED;
-  ProfScope ps(m, stream, false, prof_samples, path);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a);
-  ps.done();
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
+// (the one tail of every kernel family's launch, `launch`, and its profiling scope: cnf_common.h)
 typedef void (*FlowKernel)(const FlowArgs);
 
 // flow_dpar_kernel: D >= 3, base -> data, packed-VALU conditioner, hardware transcendentals.  Chosen (use_dpar

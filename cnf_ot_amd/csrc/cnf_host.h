@@ -18,3 +18,9 @@ int cnf_internal_build_tables(CnfModel* m, hipStream_t stream, const float* c, i
 // already built in the stream's workspace (cnf_kinetic_potential_vjp)
 int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, const float* c, int64_t slice_len,
                              int64_t n_slices, const float* tables, float* out);
+
+// ---- cnf_importance.hip ---------------------------------------------------------------------------------------------
+// importance_kernel and importance_finish_kernel behind cnf_importance_workspace / cnf_importance_stats(_seeded)
+// (include/cnf_ot_amd.h).  The unit calls into no other and none calls into it: it shares the headers -- the tile
+// helpers and flow_pass (cnf_flow_tile.h), target_logprob (cnf_terms.h), with_shape and launch (cnf_common.h) -- and
+// stands apart so that the kernels of cnf_flow.hip keep their generated code.

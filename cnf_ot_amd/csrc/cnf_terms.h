@@ -1,5 +1,6 @@
 // cnf_terms.h -- the per-sample math of the loss terms (applications.py), one definition each: the forward loss
-// kernels (cnf_flow.hip), the fused backward and the term epilogues (cnf_grad.hip) all call these.
+// kernels (cnf_flow.hip), the fused backward and the term epilogues (cnf_grad.hip) all call these; and of the
+// importance-sampling target (cnf_importance.hip).
 //
 // Coordinates are read through an accessor `x(d)` (an LDS column, a GROW-strided tile column, a row-major point,
 // or a sample pair held in registers); T is the lane type (float, v2f, double).  Formulas that call a transcendental
@@ -106,6 +107,38 @@ __device__ __forceinline__ RklMix<T> rkl_mixture(X y, int D, float t, float Tt, 
   const T mx = vmax(as, at);
   const T es = M::exp(as - mx) * ss, et = M::exp(at - mx) * st;
   return RklMix<T>{mx + M::log(es + et), (es / vs + et / vt) / (es + et)};
+}
+
+// The importance-sampling target (CnfTargetSpec: a Gaussian mixture with a shared covariance shape, Sigma^-1 = W^T W,
+// W lower triangular) at the point y, for a slice whose covariance is scale * Sigma:
+//   log p(y) = logsumexp_m(log_weight_m - |W (y - mean_m)|^2 / (2 scale)) - D/2 log(2 pi scale) + log|det W|,
+// a log-sum-exp with the maximum taken first (a component of weight 0 is -inf and drops out), in float64 whatever the
+// type of the point: the log-weights it enters reach thousands, where fp32 holds no more than 1e-4.  A non-finite
+// point gives a non-finite result.
+template <class X>
+__device__ __forceinline__ double target_logprob(const CnfTargetSpec& tg, X y, int D, double scale) {
+  const double half_inv = 0.5 / scale;
+  double e[CNF_TARGET_MAX_COMP];
+  double mx = -__builtin_huge_val();
+#pragma unroll
+  for (int m = 0; m < CNF_TARGET_MAX_COMP; ++m) {
+    e[m] = -__builtin_huge_val();
+    if (m < tg.n_comp) {
+      double q = 0.0;
+      for (int i = 0; i < D; ++i) {
+        double r = 0.0;
+        for (int j = 0; j <= i; ++j) r = fma(tg.W[i][j], (double)y(j) - tg.mean[m][j], r);
+        q = fma(r, r, q);
+      }
+      e[m] = tg.log_weight[m] - q * half_inv;
+      mx = fmax(mx, e[m]);
+    }
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int m = 0; m < CNF_TARGET_MAX_COMP; ++m)
+    if (m < tg.n_comp) s += exp(e[m] - mx);
+  return mx + log(s) - D * (HALF_LOG_2PI + 0.5 * log(scale)) + tg.log_det_W;
 }
 
 // The density-error target of rmse_mc_loss_fn / rmse_grid_loss_fn (solvers.py:239-305) at condition t:

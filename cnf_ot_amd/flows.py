@@ -470,6 +470,68 @@ class FlowEngine:
                                                    _stream_ptr(self.device)), "cnf_loss_terms_seeded")
     return sums
 
+  def importance_stats(self, target, noise=None, t=(0.0,), B: Optional[int] = None, *, seed=None, shared: bool = False,
+                       scale=None, first_sample: int = 0, slice_stride: Optional[int] = None) -> torch.Tensor:
+    """cnf_importance_stats(_seeded): the raw importance-sampling state of the flow's samples against `target` (a
+    _capi.CnfTargetSpec, or anything with a `.spec` of that type: applications.GaussianMixtureTarget), per time of t
+    [S]: float64 [S, 5] = (max l, sum exp(l - max), sum exp(2 (l - max)), sum l, n) of the log-weights
+    l = log p_target(y) - log q_flow(y) over B samples per time.  noise: base noise [S * B, D] ([B, D] with
+    shared=True) -- or seed=: drawn in the kernel, sample i of slice s = stream sample first_sample + s * slice_stride
+    + i (slice_stride default: B, each slice its own draw; 0: the same draw).  scale: [S] variance scales of the
+    target's covariance (None: 1); a float64 tensor on the device is passed as it is, anything else is uploaded here
+    (a synchronous copy: give the device tensor where the call must stay asynchronous or capturable).  Blocks merge
+    with applications.merge_importance_stats."""
+    spec = getattr(target, "spec", target)
+    if not isinstance(spec, _capi.CnfTargetSpec):
+      raise TypeError("importance_stats: target must be a CnfTargetSpec or carry one as .spec")
+    if getattr(target, "dim", self.cfg.dim) != self.cfg.dim:
+      raise ValueError(f"importance_stats: a target of dim {target.dim} for a flow of dim {self.cfg.dim}")
+    if (noise is None) == (seed is None):
+      raise ValueError("importance_stats: give base noise or a seed, not both")
+    tt = self.slice_conds(t)
+    S = tt.numel()
+    if noise is not None:
+      noise = self._points(noise, "importance_stats")
+      rows = noise.shape[0]
+      if B is None:
+        if not shared and S > 0 and rows % S:
+          raise ValueError(f"importance_stats: {rows} noise rows do not tile {S} times")
+        B = rows if shared or S == 0 else rows // S
+      need = B if shared else S * B
+      if rows != need:
+        raise ValueError(f"importance_stats: noise has {rows} rows, expected {need}")
+    elif B is None:
+      raise ValueError("importance_stats: B is needed with a seed")
+    B = int(B)
+    spec = _capi.CnfTargetSpec.from_buffer_copy(spec)       # (the scale pointer is this call's own)
+    sc = None
+    if scale is not None:
+      sc = torch.as_tensor(scale, dtype=torch.float64).reshape(-1).to(self.device).contiguous()
+      if sc.numel() != S:
+        raise ValueError(f"importance_stats: scale has {sc.numel()} values for {S} times")
+    spec.scale = sc.data_ptr() if sc is not None and S > 0 else None
+    stats = torch.empty(S, 5, dtype=torch.float64, device=self.device)
+    if S == 0 or B == 0:      # (the library launches nothing: the empty state, which merges as a no-op)
+      stats.zero_()
+      stats[:, 0] = -math.inf
+      return stats
+    nbytes = _capi.ctypes.c_int64(0)
+    _capi.check(self.lib.cnf_importance_workspace(S, B, self.cfg.dim, _capi.ctypes.byref(nbytes)), "cnf_importance_workspace")
+    work = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=self.device)
+    with _OnDevice(self.device):
+      if noise is not None:
+        rc = self.lib.cnf_importance_stats(self._h, _capi.ctypes.byref(spec), noise.data_ptr(), 1 if shared else 0,
+                                           tt.data_ptr(), S, B, stats.data_ptr(), work.data_ptr(), nbytes.value,
+                                           _stream_ptr(self.device))
+      else:
+        sd, off = seed_to_u64(seed)
+        rc = self.lib.cnf_importance_stats_seeded(self._h, _capi.ctypes.byref(spec), sd, off + int(first_sample),
+                                                  B if slice_stride is None else int(slice_stride), tt.data_ptr(), S, B,
+                                                  stats.data_ptr(), work.data_ptr(), nbytes.value,
+                                                  _stream_ptr(self.device))
+    _capi.check(rc, "cnf_importance_stats")
+    return stats
+
   def loss_terms_grad(self, spec, pts, t, B: int, shared: bool, scale: float, grad: torch.Tensor, sums=None) -> torch.Tensor:
     """cnf_loss_terms_grad: like `loss_terms`, and accumulates
     scale * d(sum of the term)/d(params) into `grad` (flat float32 [n_params])."""

@@ -9,6 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
+                               [--path-errors] [--fit]
 """
 import argparse
 import sys
@@ -430,6 +431,38 @@ def print_fp_path_errors(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.4f} | {:.4f} | {:.3e} | {:.0f}".format(*row))
 
 
+# ---- the fit to the densities known in closed form (the reference's kl_ess, tests/test_fit_prob.py:50-56) -----------
+
+def evaluate_fit(config, model: FlowModel, params: Params, rng, batch_size: int = 1 << 20) -> Dict[str, Any]:
+  """The importance-sampling fit of the trained flow to every closed-form density of the problem
+  (applications.known_densities: the boundary densities, and for fp / ou the exact density along the path): lists of
+  floats, one entry per time -- times, log_Z, KL, ess, ess_pct, max_log_w -- from batch_size samples per time.  One
+  fused launch per target (applications.importance_stats).  A perfect fit has log_Z = KL = 0 and ess_pct = 100."""
+  entries = applications.known_densities(config)
+  keys = ("log_Z", "KL", "ess", "ess_pct", "max_log_w")
+  out: Dict[str, Any] = {"times": [], "batch_size": int(batch_size), **{k: [] for k in keys}}
+  i = 0
+  while i < len(entries):                       # consecutive times of one target: one call
+    j = i
+    while j < len(entries) and entries[j][1] is entries[i][1]:
+      j += 1
+    grp = entries[i:j]
+    scale = None if all(e[2] is None for e in grp) else [1.0 if e[2] is None else float(e[2]) for e in grp]
+    res = applications.importance_stats(model, params, grp[0][1], [float(e[0]) for e in grp], rng, batch_size, scale=scale)
+    out["times"] += [float(e[0]) for e in grp]
+    for k in keys:
+      out[k] += [float(v) for v in res[k].cpu()]
+    i = j
+  return out
+
+
+def print_fit(res: Dict[str, Any]) -> None:
+  """evaluate_fit's table, one line per time"""
+  print(f"fit to the known densities ({res['batch_size']} samples per time):  t | log Z | KL | ESS % | max log w")
+  for row in zip(res["times"], res["log_Z"], res["KL"], res["ess_pct"], res["max_log_w"]):
+    print("  {:.4f} | {:+.4e} | {:.4e} | {:.2f} | {:.3f}".format(*row))
+
+
 # ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
 # The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
 # by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
@@ -517,10 +550,11 @@ def _eval_rng(seed, step):
 
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
-         fields: Optional[str] = None, path_errors: bool = False) -> Dict[str, Any]:
+         fields: Optional[str] = None, path_errors: bool = False, fit: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
-  evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp)."""
+  evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
+  returned dict is `evaluate`'s either way)."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -572,6 +606,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_path_errors(evaluate_fp_path(config, model, params))
   elif path_errors:
     print_path_errors(evaluate_path(config, model, params))
+  if fit:
+    print_fit(evaluate_fit(config, model, params, _eval_rng(seed, -2)))
   return res
 
 
@@ -586,10 +622,13 @@ def _parse(argv):
   p.add_argument("--path-errors", action="store_true",
                  help="print the density and velocity errors against the exact solution at 9 times (rwpo at dim 2), or the "
                       "errors against the particle reference at the figure's times (fp)")
+  p.add_argument("--fit", action="store_true",
+                 help="print log Z, KL and the effective sample size of the flow against every density of the problem that "
+                      "is known in closed form (1 M samples per time)")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
-       path_errors=args.path_errors)
+       path_errors=args.path_errors, fit=args.fit)

@@ -150,7 +150,7 @@ int cnf_model_set_precise(CnfModel *m, int on);
 /* Which kernels the most recent compute call on this model ran: 1/2 = MLP flow
  * kernel with one / two samples per lane, 3 = MFMA conditioner, 4 = conditioner
  * tables, 5/6 = fused loss kernel on the MLP / on tables, 7 = float64, 10 = the fused field kernel,
- * 11 = the exact-score kernel (cnf_score). */
+ * 11 = the exact-score kernel (cnf_score), 12 = the importance-sampling kernel (cnf_importance_stats). */
 int cnf_model_last_path(const CnfModel *m);
 
 /* Replaces: model.apply.forward(params, x, c) = flow.bijector.forward, and
@@ -698,6 +698,64 @@ int cnf_fp_particles(int32_t drift, int32_t D, float a, double sigma, double h,
 int cnf_point_stats(const float *pts, int64_t N, int32_t D, int32_t S,
                     const CnfFieldGrid *grid, double *sums, uint32_t *hist,
                     void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- importance-sampling diagnostics against a density known in closed form ----------------------------------------
+ * The reference's kl_ess (tests/test_fit_prob.py:50-56, "metrics used in the tori paper"): draw y_i from the flow,
+ * weight w_i = p_target(y_i) / q_flow(y_i), and report Z = mean w, KL = mean(log q - log p) + log Z and the effective
+ * sample size ESS = (sum w)^2 / sum w^2.  It forms target_prob / exp(log_model_prob) in linear space: with the flow
+ * far from its target (early in training, high dimension) sum w underflows to 0, Z = 0 and ESS = NaN.  Here the
+ * statistic is carried in log space, as a state that merges exactly over lanes, waves, workgroups, calls and ranks.
+ *
+ * The target family, CnfTargetSpec: a Gaussian mixture whose components share one covariance shape,
+ *   log p_s(y) = logsumexp_m(log_weight[m] - |W (y - mean[m])|^2 / (2 scale_s)) - D/2 log(2 pi scale_s) + log_det_W,
+ * W lower triangular with Sigma^-1 = W^T W (rows and columns < D are read; the diagonal must be positive and
+ * finite), log_det_W = log|det W|, log_weight normalised by the host (logsumexp = 0; -inf: a component of weight 0),
+ * scale [n_slices] an optional DEVICE array of per-slice variance factors (slice s has covariance scale[s] Sigma;
+ * NULL: 1).  It holds every closed-form density of the reference's problems: N(0, v I), the Gaussian source N(-3 1, A)
+ * and the 8-mode mixture source (applications.py:28-71), and the OU solution N(0, v(t) I) at all times through scale.
+ * The struct is a HOST argument, passed to the kernel by value.
+ *
+ * cnf_importance_stats: n_slices times t [n_slices] (device), B samples per time from base noise [n_slices * B, D]
+ * ([B, D] with noise_shared != 0: every slice the same draw); one base -> data pass per sample gives y and
+ * log q = log N(noise; 0, I) - log|det J|; the target is evaluated in float64 at the fp32 sample.  With
+ * l_i = log p_s(y_i) - log q(y_i), stats [n_slices, 5] (device, double, overwritten) is the raw, mergeable state
+ *   m = max_i l_i,  s1 = sum exp(l_i - m),  s2 = sum exp(2 (l_i - m)),  c = sum l_i,  n = the sample count,
+ * from which log Z = log s1 + m - log n, KL = -c / n + log Z, ESS = s1^2 / s2.  Two states merge by bringing s1
+ * and s2 to the common maximum and adding; the empty state (-inf, 0, 0, 0, 0) is the identity.  A slice with any
+ * non-finite l_i has NaN in its first four columns: nothing is hidden.  All sums are float64 in a fixed order that
+ * depends on B alone -- not on the device, nor on the other slices of the call; no atomics: repeated calls are
+ * bit-identical on any device, and a slice's row is the same whatever else the call holds.
+ * cnf_importance_stats_seeded: the same with the noise drawn in the kernel, by the convention of
+ * cnf_loss_terms_seeded: sample i of slice s is sample first_sample + s * slice_stride + i of the cnf_fill_normal
+ * stream of `seed` -- bit for bit cnf_fill_normal followed by cnf_importance_stats.
+ * cnf_importance_workspace: the bytes of device workspace a call with these sizes needs (> 0); no HIP call.  The
+ * workspace is the caller's: the compute calls neither allocate nor synchronise (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL model, target, noise, t, stats or workspace; a
+ * negative size, first_sample or slice_stride; n_comp outside 1..8; a diagonal entry of W (below the model's dim)
+ * that is not positive and finite; a model of dim > 14; a workspace smaller than cnf_importance_workspace says;
+ * parameters not set.  CNF_ERR_UNSUPPORTED: a periodized model, as for the loss terms.  n_slices == 0 or B == 0:
+ * CNF_OK, nothing launched, stats untouched.  Runs the conditioner MLP at every dimension (the dim-2 tables pay from
+ * launches far larger than an evaluation's). */
+#define CNF_TARGET_MAX_COMP 8
+#define CNF_TARGET_MAX_DIM 14
+typedef struct CnfTargetSpec {
+  int32_t n_comp;                                       /* 1 .. CNF_TARGET_MAX_COMP                      */
+  int32_t reserved;
+  double mean[CNF_TARGET_MAX_COMP][CNF_TARGET_MAX_DIM];
+  double log_weight[CNF_TARGET_MAX_COMP];
+  double W[CNF_TARGET_MAX_DIM][CNF_TARGET_MAX_DIM];     /* lower triangular: Sigma^-1 = W^T W            */
+  double log_det_W;
+  const double *scale;                                  /* device [n_slices], or NULL                    */
+} CnfTargetSpec;
+int cnf_importance_workspace(int64_t n_slices, int64_t B, int32_t D, int64_t *bytes);
+int cnf_importance_stats(CnfModel *m, const CnfTargetSpec *target, const float *noise,
+                         int noise_shared, const float *t, int64_t n_slices, int64_t B,
+                         double *stats, void *workspace, int64_t workspace_bytes,
+                         void *stream);
+int cnf_importance_stats_seeded(CnfModel *m, const CnfTargetSpec *target, uint64_t seed,
+                                int64_t first_sample, int64_t slice_stride, const float *t,
+                                int64_t n_slices, int64_t B, double *stats, void *workspace,
+                                int64_t workspace_bytes, void *stream);
 
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
