@@ -61,6 +61,15 @@ class CnfTargetSpec(ctypes.Structure):
   ]
 
 
+MMD_MAX_BW, MMD_MAX_DIM, MMD_MAX_SETS = 8, 14, 64
+MMD_KINDS = {"gaussian": 0, "energy": 1}
+
+
+class CnfMmdSpec(ctypes.Structure):
+  """The kernel of cnf_mmd2 (include/cnf_ot_amd.h): kind 0 = a sum of Gaussians of n_bw bandwidths, 1 = energy."""
+  _fields_ = [("kind", ctypes.c_int32), ("n_bw", ctypes.c_int32), ("bw", ctypes.c_float * MMD_MAX_BW)]
+
+
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
 TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
@@ -156,6 +165,11 @@ SYMBOLS = {
                                           _P]),
   "cnf_importance_stats_seeded": (ctypes.c_int, [_P, ctypes.POINTER(CnfTargetSpec), _U64, _I64, _I64, _P, _I64, _I64, _P, _P,
                                                  _I64, _P]),
+  # kernel two-sample statistics of point clouds x [S, N, D], y [S, M, D]: raw sums [S, 3] doubles, xgrad [S, N, D]
+  "cnf_mmd_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_mmd_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_mmd2": (ctypes.c_int, [ctypes.POINTER(CnfMmdSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, _P, _P,
+                              _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

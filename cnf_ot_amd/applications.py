@@ -1104,6 +1104,48 @@ def importance_stats(model, params, target, conds, rng, batch_size, scale=None, 
   return importance_summary(raw)
 
 
+# ---- a sample-only fitting term: MMD^2 / energy distance between the flow's samples and given target samples --------
+
+def mmd_loss_fn(model, dim, params, target, cond, rng, batch_size, bandwidths=None, kind="gaussian", shard=None,
+                grad=None):
+  """The mean over the times of `cond` of the unbiased MMD^2 (kind="gaussian"; bandwidths=None:
+  utils.median_bandwidths(target)) or energy distance (kind="energy") between batch_size flow samples at that time --
+  the same base draw of `rng` for every time, as the other terms -- and the samples `target`: [M, D], or [S, M, D] with
+  one set per time.  A fitting term for a target known by its samples alone.  With `grad` (the convention of the
+  other term functions; `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_mmd2 call
+  (value and d / d samples) and ONE cnf_pass_vjp call.  Single rank: the pairs across ranks would need an all-gather of
+  the samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
+  from . import utils
+  shard = shard if shard is not None else current_shard()
+  if shard.world > 1:
+    raise ValueError("mmd_loss_fn: single rank only (pairs across ranks need an all-gather of the samples)")
+  conds = _conds(cond)
+  S = _n_conds(conds)
+  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+  if tgt.dim() == 2:
+    tgt = tgt[None].expand(S, -1, -1)
+  if tgt.dim() != 3 or tgt.shape[0] != S:
+    raise ValueError(f"mmd_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
+  utils.mmd_check_shapes((S, int(batch_size), int(dim)), tgt.shape)
+  if kind == "gaussian" and bandwidths is not None:
+    utils.mmd_spec(bandwidths, kind)
+  elif kind not in _capi.MMD_KINDS:
+    raise ValueError(f"mmd_loss_fn: kind is 'gaussian' or 'energy', not {kind!r}")
+  ctx = _Ctx(model, params, rng, shard, grad)
+  be = ctx.be
+  z, _, count = ctx.noise(batch_size)
+  zs = z.repeat(S, 1)                                         # the same draw for every time
+  c = be.slice_conds(conds)
+  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
+  tgt = tgt.to(device=samples.device, dtype=torch.float32)
+  if kind == "gaussian" and bandwidths is None:
+    bandwidths = utils.median_bandwidths(tgt)
+  res = utils.mmd2(samples.view(S, count, -1), tgt, bandwidths, kind, want_grad=grad is not None)
+  if grad is not None:
+    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
+  return res["mmd2"].sum() / S
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

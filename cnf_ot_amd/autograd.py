@@ -90,3 +90,32 @@ def _cond_tensor(engine, c):
   if not torch.is_tensor(c):
     c = torch.as_tensor(c, dtype=torch.float32)
   return c.to(device=engine.device, dtype=torch.float32).reshape(-1)
+
+
+class _Mmd2(torch.autograd.Function):
+  """utils.mmd2 with its gradient: in x from the same cnf_mmd2 call (xgrad), in y from a second call with the roles
+  swapped (MMD^2 is symmetric)."""
+
+  @staticmethod
+  def forward(ctx, x, y, bandwidths, kind):
+    from .utils import mmd2 as _mmd2
+    need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    res = _mmd2(x.detach(), y.detach(), bandwidths, kind, want_grad=need_x)
+    gy = _mmd2(y.detach(), x.detach(), bandwidths, kind, want_grad=True)["grad"] if need_y else None
+    ctx.save_for_backward(res.get("grad"), gy)
+    return res["mmd2"]
+
+  @staticmethod
+  def backward(ctx, gbar):
+    gx, gy = ctx.saved_tensors
+    w = gbar.to(torch.float32)
+    scale = lambda g: None if g is None else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
+    return scale(gx), scale(gy), None, None
+
+
+def mmd2(x: torch.Tensor, y: torch.Tensor, bandwidths, kind: str = "gaussian"):
+  """The unbiased MMD^2 (kind="gaussian", up to 8 bandwidths) or energy distance (kind="energy") between the sample
+  sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D], [S] float64 ([1] for 2-D inputs), differentiable in x and y:
+  with `flow_forward` a flow trains on samples through ordinary autograd (applications.mmd_loss_fn is the hand-written
+  fast path).  The bandwidths are constants (utils.median_bandwidths(y) gives the usual choice)."""
+  return _Mmd2.apply(x, y, bandwidths, kind)

@@ -24,3 +24,7 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
 // (include/cnf_ot_amd.h).  The unit calls into no other and none calls into it: it shares the headers -- the tile
 // helpers and flow_pass (cnf_flow_tile.h), target_logprob (cnf_terms.h), with_shape and launch (cnf_common.h) -- and
 // stands apart so that the kernels of cnf_flow.hip keep their generated code.
+
+// ---- cnf_mmd.hip ----------------------------------------------------------------------------------------------------
+// mmd_kernel and mmd_finish_kernel behind cnf_mmd_workspace / cnf_mmd_splits / cnf_mmd2 (include/cnf_ot_amd.h).
+// Model-free, like cnf_fp_particles.hip: the unit calls into no other and none calls into it.

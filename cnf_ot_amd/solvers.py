@@ -431,6 +431,60 @@ def print_fp_path_errors(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.4f} | {:.4f} | {:.3e} | {:.0f}".format(*row))
 
 
+def evaluate_fp_two_sample(config, model: FlowModel, params: Params, times=None, n_particles=65536, h=1e-3, seed=0,
+                           bandwidths=None) -> Dict[str, Any]:
+  """How far, in the FULL dimension, the flow's samples are from the Euler-Maruyama ensemble of an fp configuration
+  (evaluate_fp_path's histograms are a marginal over axes (0, 1) beyond dim 2): kernel two-sample statistics per time
+  of `times` (default and refusals as evaluate_fp_path: fp only, a configuration with figure settings, an even
+  n_particles, times that are multiples of h).  The ensemble is run as its two halves
+  (fp_reference_particles(positions=True, shard=Shard(r, 2), all_reduce=False)); n_particles / 2 flow samples
+  (model.apply.sample of `seed`) are compared with half 0, and half 1 with half 0 -- the same sample sizes and the same
+  bandwidths (None: utils.median_bandwidths of half 0's first time).  Lists of floats, one per time:
+    times
+    mmd2, mmd2_floor      the unbiased Gaussian MMD^2 of flow against half 0, and of half 1 against half 0: the
+                          Monte-Carlo level that makes mmd2 readable, as tv_floor does for tv
+    energy, energy_floor  the same for the energy distance 2 E|x - y| - E|x - x'| - E|y - y'|
+    bandwidths            the bandwidths used
+  Two cnf_mmd2 calls per kind over all times (utils.mmd2).  Single process."""
+  g = config["general"]
+  if g["type"] != "fp":
+    raise ValueError(f"evaluate_fp_two_sample: defined for fp only, not {g['type']}")
+  st = figure_settings(config)
+  if st is None:
+    raise ValueError(f"evaluate_fp_two_sample: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
+  n_particles = int(n_particles)
+  if n_particles < 4 or n_particles % 2:
+    raise ValueError(f"evaluate_fp_two_sample: n_particles must be even and >= 4 (two halves are compared), not {n_particles}")
+  if bandwidths is not None:
+    utils.mmd_spec(bandwidths, "gaussian")
+  from .distributed import Shard
+  f, dim = config["fp"], g["dim"]
+  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
+  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
+  applications.fp_step_indices(ts, float(h), T)
+  n = n_particles // 2
+  flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n,)) for t in ts])
+  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
+                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  bws = utils.median_bandwidths(h0) if bandwidths is None else bandwidths
+  out: Dict[str, Any] = {"times": [float(t) for t in ts]}
+  for kind, key in (("gaussian", "mmd2"), ("energy", "energy")):
+    res = utils.mmd2(flow, h0, bws, kind)
+    out[key] = res["mmd2"].tolist()
+    out[key + "_floor"] = utils.mmd2(h1, h0, bws, kind)["mmd2"].tolist()
+    if kind == "gaussian":
+      out["bandwidths"] = res["bandwidths"]
+  return out
+
+
+def print_fp_two_sample(res: Dict[str, Any]) -> None:
+  """evaluate_fp_two_sample's table, one line per time"""
+  print("two-sample distances to the particle reference (bandwidths " + " ".join(f"{b:.3g}" for b in res["bandwidths"])
+        + "):  t | mmd2 | mmd2 floor | energy | energy floor")
+  for row in zip(res["times"], res["mmd2"], res["mmd2_floor"], res["energy"], res["energy_floor"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row))
+
+
 # ---- the fit to the densities known in closed form (the reference's kl_ess, tests/test_fit_prob.py:50-56) -----------
 
 def evaluate_fit(config, model: FlowModel, params: Params, rng, batch_size: int = 1 << 20) -> Dict[str, Any]:
@@ -550,15 +604,18 @@ def _eval_rng(seed, step):
 
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
-         fields: Optional[str] = None, path_errors: bool = False, fit: bool = False) -> Dict[str, Any]:
+         fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
+         two_sample: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
-  returned dict is `evaluate`'s either way)."""
+  returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
     raise Exception(f"Unknown problem type: {_type}...")
+  if two_sample and _type != "fp":      # (before the training run, not after it)
+    raise ValueError(f"--two-sample compares the flow with the fp particle reference: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
 
   def log(step, loss):
@@ -608,6 +665,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_path_errors(evaluate_path(config, model, params))
   if fit:
     print_fit(evaluate_fit(config, model, params, _eval_rng(seed, -2)))
+  if two_sample:
+    print_fp_two_sample(evaluate_fp_two_sample(config, model, params))
   return res
 
 
@@ -625,10 +684,13 @@ def _parse(argv):
   p.add_argument("--fit", action="store_true",
                  help="print log Z, KL and the effective sample size of the flow against every density of the problem that "
                       "is known in closed form (1 M samples per time)")
+  p.add_argument("--two-sample", action="store_true",
+                 help="print MMD^2 and the energy distance, in the full dimension, between the flow's samples and the "
+                      "particle reference at the figure's times, each beside its Monte-Carlo floor (fp)")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
-       path_errors=args.path_errors, fit=args.fit)
+       path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample)

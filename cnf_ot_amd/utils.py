@@ -335,3 +335,109 @@ def point_stats(pts, grid=None, axes=(0, 1)) -> dict:
                                             sums.data_ptr(), None if hist is None else hist.data_ptr(), ws.data_ptr(),
                                             ws.numel() * 8, _stream_ptr(dev)), "cnf_point_stats")
   return stats_from_sums(sums, hist, N, g, D)
+
+
+# ---- kernel two-sample statistics: what compares a flow with a target that exists only as samples -------------------
+# The reference: with samples of the target alone KL cannot be computed and "we need to shift to other integral
+# probability metric, e.g. MMD" (tests/test_wasserstein_geodesic.py:165-169).  One fused launch over all sets
+# (cnf_mmd2); composed in torch the same statistic materialises three N x M matrices.
+
+MEDIAN_BANDWIDTH_FACTORS = (0.25, 0.5, 1.0, 2.0, 4.0)
+
+
+def median_bandwidths(y, max_rows: int = 1024):
+  """The median heuristic: the median pair distance of the first <= 1 024 rows of y ([M, D], or the first set of
+  [S, M, D]) times (1/4, 1/2, 1, 2, 4), computed in torch (float64); a list of 5 floats."""
+  y = torch.as_tensor(y)
+  if y.dim() == 3:
+    y = y[0]
+  if y.dim() != 2 or y.shape[0] < 2:
+    raise ValueError(f"median_bandwidths: expected [M >= 2, D] points, got {tuple(y.shape)}")
+  med = float(torch.pdist(y[:max_rows].double()).median())
+  if not (med > 0.0 and np.isfinite(med)):
+    raise ValueError(f"median_bandwidths: the median pair distance is {med}")
+  return [f * med for f in MEDIAN_BANDWIDTH_FACTORS]
+
+
+def _mmd_sets(t, name):
+  t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+  if t.dim() == 2:
+    t = t[None]
+  if t.dim() != 3:
+    raise ValueError(f"mmd2: {name} must be [N, D] or [S, N, D], not {tuple(t.shape)}")
+  return t
+
+
+def mmd_spec(bandwidths, kind="gaussian"):
+  """(CnfMmdSpec, the bandwidths as a list) -- ValueError for what cnf_mmd2 refuses in a spec."""
+  if kind not in _capi.MMD_KINDS:
+    raise ValueError(f"mmd2: kind is 'gaussian' or 'energy', not {kind!r}")
+  spec = _capi.CnfMmdSpec()
+  spec.kind = _capi.MMD_KINDS[kind]
+  if kind == "energy":
+    return spec, []
+  bws = [float(b) for b in np.asarray(bandwidths.cpu() if torch.is_tensor(bandwidths) else bandwidths,
+                                      dtype=np.float64).reshape(-1)]
+  if not 1 <= len(bws) <= _capi.MMD_MAX_BW:
+    raise ValueError(f"mmd2: between 1 and {_capi.MMD_MAX_BW} bandwidths, not {len(bws)}")
+  for b in bws:
+    b32 = float(np.float32(b))      # (as the kernel sees it; 1 / bw^2 must stay in float32's range)
+    if not (b32 > 0.0 and np.isfinite(b32) and 1.0 / (b32 * b32) <= 3.0e38):
+      raise ValueError(f"mmd2: every bandwidth must be positive and finite (in float32, with 1 / bw^2): {bws}")
+  spec.n_bw = len(bws)
+  for i, b in enumerate(bws):
+    spec.bw[i] = b
+  return spec, [float(spec.bw[i]) for i in range(len(bws))]
+
+
+def mmd_check_shapes(x_shape, y_shape):
+  """ValueError for sets cnf_mmd2 refuses: ([S, N, D], [S, M, D]) with S in 1..64, N, M >= 2, D in 1..14."""
+  (S, N, D), (Sy, M, Dy) = x_shape, y_shape
+  if S != Sy or D != Dy:
+    raise ValueError(f"mmd2: x {tuple(x_shape)} and y {tuple(y_shape)} differ in the number of sets or in the dimension")
+  if not 1 <= S <= _capi.MMD_MAX_SETS or not 1 <= D <= _capi.MMD_MAX_DIM or N < 2 or M < 2 or max(N, M) > 1 << 24:
+    raise ValueError(f"mmd2: needs 1..{_capi.MMD_MAX_SETS} sets of 2..2^24 points of dimension 1..{_capi.MMD_MAX_DIM}, "
+                     f"not x {tuple(x_shape)}, y {tuple(y_shape)}")
+
+
+def mmd2_from_sums(sums, N, M):
+  """The unbiased MMD^2 [S] from raw sums [S, 3] = (sxx, syy, sxy)."""
+  return sums[:, 0] / (N * (N - 1.0)) + sums[:, 1] / (M * (M - 1.0)) - 2.0 * sums[:, 2] / (float(N) * M)
+
+
+def mmd2(x, y, bandwidths=None, kind="gaussian", want_grad=False) -> dict:
+  """The unbiased kernel two-sample statistic between the point sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D]
+  (set s of x against set s of y), ONE fused launch over all sets and all three pair blocks (cnf_mmd2):
+    kind="gaussian": k(x, y) = sum_b exp(-|x - y|^2 / (2 bw_b^2)) over up to 8 `bandwidths` (None:
+                     median_bandwidths(y)) -- MMD^2
+    kind="energy":   k(x, y) = -|x - y| -- the energy distance 2 E|x - y| - E|x - x'| - E|y - y'|
+  float32 on the device (float64 inputs are rounded; host inputs are uploaded).  Returns a dict: mmd2 [S] (float64),
+  sums [S, 3] (the raw sxx, syy, sxy: diagonal left out), bandwidths (a list; empty for energy) and, with want_grad,
+  grad [S, N, D] (float32; [N, D] for 2-D x) = d mmd2 / d x.  Two calls give the same bits.  ValueError before any
+  device work for what the C ABI refuses (D outside 1..14, N or M < 2, more than 64 sets or 8 bandwidths, a bandwidth
+  that is not positive and finite, an unknown kind) and for x and y that differ in S or D."""
+  from .applications import _OnDevice, _stream_ptr
+  x3, y3 = _mmd_sets(x, "x"), _mmd_sets(y, "y")
+  mmd_check_shapes(x3.shape, y3.shape)
+  if kind == "gaussian" and bandwidths is None:
+    bandwidths = median_bandwidths(y3)
+  spec, bws = mmd_spec(bandwidths, kind)
+  S, N, D = x3.shape
+  M = y3.shape[1]
+  dev = x3.device if x3.is_cuda else (y3.device if y3.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+  x3 = x3.to(device=dev, dtype=torch.float32).contiguous()
+  y3 = y3.to(device=dev, dtype=torch.float32).contiguous()
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_mmd_workspace(S, N, M, D, 1 if want_grad else 0, C.byref(nbytes)), "cnf_mmd_workspace")
+  ws = torch.empty(-(-nbytes.value // 8), dtype=torch.float64, device=dev)
+  sums = torch.empty(S, 3, dtype=torch.float64, device=dev)
+  grad = torch.empty(S, N, D, dtype=torch.float32, device=dev) if want_grad else None
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_mmd2(C.byref(spec), S, x3.data_ptr(), N, y3.data_ptr(), M, D, sums.data_ptr(),
+                             None if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+                "cnf_mmd2")
+  out = {"mmd2": mmd2_from_sums(sums, N, M), "sums": sums, "bandwidths": bws}
+  if want_grad:
+    out["grad"] = grad if np.ndim(x) == 3 else grad[0]
+  return out

@@ -757,6 +757,42 @@ int cnf_importance_stats_seeded(CnfModel *m, const CnfTargetSpec *target, uint64
                                 int64_t n_slices, int64_t B, double *stats, void *workspace,
                                 int64_t workspace_bytes, void *stream);
 
+/* ---- kernel two-sample statistics between point clouds: MMD^2 and the energy distance, with gradients ---------------
+ * What compares a flow with a target that exists only as SAMPLES (the reference: with samples of the target alone "we
+ * need to shift to other integral probability metric, e.g. MMD", tests/test_wasserstein_geodesic.py:165-169).
+ * Model-free.  For S independent sets, x [S, N, D] against y [S, M, D] (device, float32), and the kernel
+ *   kind CNF_MMD_GAUSSIAN:  k(x, y) = sum_b exp(-|x - y|^2 / (2 bw_b^2)),  b < n_bw <= 8
+ *   kind CNF_MMD_ENERGY:    k(x, y) = -|x - y|                             (n_bw and bw are ignored)
+ * cnf_mmd2 writes sums [S, 3] (device, double, overwritten), the RAW sums
+ *   sxx = sum_{i != j} k(x_i, x_j),   syy = sum_{i != j} k(y_i, y_j),   sxy = sum_{i, j} k(x_i, y_j);
+ * the caller forms the unbiased MMD^2 = sxx / (N (N - 1)) + syy / (M (M - 1)) - 2 sxy / (N M), which with the energy
+ * kernel is the energy distance 2 E|x - y| - E|x - x'| - E|y - y'|.  With xgrad [S, N, D] (device, float32, optional,
+ * overwritten) it also writes d MMD^2 / d x_i; the derivative of k in its first argument is -(x - y) / bw_b^2 k_b
+ * per bandwidth and -(x - y) / |x - y| for the energy kernel (0 for coincident points).  The diagonal i == j of the xx
+ * and yy sums is left out by index.  Distances are formed from coordinate differences in float32; no float32
+ * accumulator holds more than 64 pair terms before it is added into a double.  One launch computes the three blocks
+ * of all sets, the columns of a block split over cnf_mmd_splits(S, N, M, D) workgroups (a function of the sizes
+ * alone); a second adds the splits and the rows in a fixed order: no atomics, two calls are bit-identical, and the
+ * result does not depend on what the workspace held.  The spec is a HOST argument.
+ * cnf_mmd_workspace: the bytes of device workspace (8-byte aligned) such a call needs; no HIP call.  The workspace is
+ * the caller's: cnf_mmd2 neither allocates nor synchronises (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x, y, sums or workspace; D outside 1..14; N or
+ * M < 2 (or above 2^24); S outside 1..64; an unknown kind; n_bw outside 1..8 or a bandwidth that is not positive and
+ * finite (or whose square leaves float32's range); a workspace smaller than cnf_mmd_workspace says. */
+#define CNF_MMD_MAX_BW 8
+typedef enum { CNF_MMD_GAUSSIAN = 0, CNF_MMD_ENERGY = 1 } CnfMmdKind;
+typedef struct CnfMmdSpec {
+  int32_t kind;                 /* CnfMmdKind                                   */
+  int32_t n_bw;                 /* Gaussian: 1 .. CNF_MMD_MAX_BW; energy: ignored */
+  float bw[CNF_MMD_MAX_BW];
+} CnfMmdSpec;
+int cnf_mmd_workspace(int32_t S, int64_t N, int64_t M, int32_t D, int32_t want_grad, int64_t *bytes);
+/* the column splits of a block at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_mmd_splits(int32_t S, int64_t N, int64_t M, int32_t D);
+int cnf_mmd2(const CnfMmdSpec *spec, int32_t S, const float *x, int64_t N, const float *y,
+             int64_t M, int32_t D, double *sums, float *xgrad, void *workspace,
+             int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
