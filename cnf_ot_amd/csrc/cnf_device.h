@@ -515,7 +515,9 @@ __device__ __forceinline__ void cond_spline_masked(const v2f (&th)[3 * K + 1], v
 // the 0/1 masks) addresses the row a second time and `slopes(ka, kb, ta, tb)` returns (t_k, t_k+1) of each sample
 // from one packed FMA.  Same values bit for bit as cond_spline_masked on the same rows.
 // LEAN (flow_pwl_kernel's sampling direction): in shift-free cells the root without its Newton step (rqs_bin_eval
-// NEWTON=false); the linear tails guarded by the caller's wave-uniform `tails` instead of this spline's own test.
+// NEWTON=false) and the bin selected on the unnormalised softmax sums (x0, y0, bw, bh within rounding of the values
+// above, not bit for bit); the linear tails guarded by the caller's wave-uniform `tails` instead of this spline's
+// own test.
 template <int K, bool INV, bool FAST, bool SHIFT_FREE, bool ARG = false, bool LEAN = false, class SlopeFetch>
 __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (&qb)[K], SlopeFetch&& slopes, v2f v,
                                                  const SplineConsts sc, v2f& out, v2f& ld, bool tails = true) {
@@ -523,8 +525,10 @@ __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (
   typedef v2f T;
   auto la = [&](int j) { return qa[j >> 1][j & 1]; };
   auto lb = [&](int j) { return qb[j >> 1][j & 1]; };
+  constexpr bool UNNORM = LEAN && SHIFT_FREE && INV;   // bin selection on the unnormalised sums (below)
   T ew[K], eh[K];
   T aw, ah;
+  [[maybe_unused]] T ch[K + 1];                             // UNNORM: ch[k] = eh[0] + ... + eh[k-1]
   if constexpr (SHIFT_FREE) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -532,8 +536,12 @@ __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (
       eh[k] = v2f{__builtin_amdgcn_exp2f(la(K + k)), __builtin_amdgcn_exp2f(lb(K + k))};
     }
     T sw = ew[0] + ew[1], sh = eh[0] + eh[1];
+    if constexpr (UNNORM) { ch[1] = eh[0]; ch[2] = sh; }
 #pragma unroll
-    for (int k = 2; k < K; ++k) { sw += ew[k]; sh += eh[k]; }
+    for (int k = 2; k < K; ++k) {
+      sw += ew[k]; sh += eh[k];                             // (left to right: the prefix sums are the sum's own terms)
+      if constexpr (UNNORM) ch[k + 1] = sh;
+    }
     const T r = M::rcp(sw * sh) * sc.span_eff;
     aw = r * sh; ah = r * sw;
   } else {
@@ -554,27 +562,58 @@ __device__ __forceinline__ void cond_spline_rows(const v2f (&qa)[K], const v2f (
     aw = M::rcp(sw) * sc.span_eff; ah = M::rcp(sh) * sc.span_eff;
   }
   const T big = splat<T>(1.152921504606846976e18f);       // 2^60
-  T px = splat<T>(sc.lo), py = splat<T>(sc.lo);            // running knot k
-  T wp = vfma(ew[0], aw, splat<T>(sc.min_bin)), hp = vfma(eh[0], ah, splat<T>(sc.min_bin));   // bin k-1
-  T x0 = px, y0 = py;
-  T mprev = splat<T>(1.0f), bw = splat<T>(0.0f), bh = splat<T>(0.0f), kf = splat<T>(0.0f);
+  T x0, y0, bw, bh, kf;
+  if constexpr (UNNORM) {
+    // The sampling direction needs the masks and four values of ONE bin, so nothing but those four is normalised:
+    // knot k sits at lo + k min_bin + ah ch[k] with ah = span_eff / sh, hence
+    //   m_k = [v > knot_k] = [(v - lo - k min_bin) sh / span_eff > ch[k]]
+    // -- on the raw exponentials, not behind the reciprocal -- and with the one-hot o_k = m_k - m_(k+1)
+    //   x0 = lo + kf min_bin + aw sum m_k ew[k-1],  bw = min_bin + aw sum o_k ew[k]      (y0, bh alike)
+    // (sums of products with 0 or 1: the selected terms bit for bit, scaled once).  No running knot is formed, so
+    // x0 + bw of the last bin is hi only to rounding (4.8e-6; scripts/numerics/exp_binsel_unnormalised.py).
+    const T t = ch[K] * (1.0f / sc.span_eff);
+    T m[K];
 #pragma unroll
-  for (int k = 1; k < K; ++k) {
-    px += wp;
-    py += hp;
-    const T m = step_mask(v - (INV ? py : px), big);
-    const T o = mprev - m;                                  // one-hot of bin k-1
-    bw = k == 1 ? o * wp : vfma(o, wp, bw);
-    bh = k == 1 ? o * hp : vfma(o, hp, bh);
-    kf = k == 1 ? m : kf + m;                               // masks are monotone: their sum is the bin index
-    x0 = vfma(m, wp, x0);
-    y0 = vfma(m, hp, y0);
-    if (k == K - 1) { wp = sc.hi - px; hp = sc.hi - py; }   // last knot is exactly hi
-    else { wp = vfma(ew[k], aw, splat<T>(sc.min_bin)); hp = vfma(eh[k], ah, splat<T>(sc.min_bin)); }
-    mprev = m;
+    for (int k = 1; k < K; ++k) m[k] = step_mask(vfma(v - (sc.lo + (float)k * sc.min_bin), t, -ch[k]), big);
+    T xs = m[1] * ew[0], ys = m[1] * eh[0];
+    T ws = ew[0] - xs, hs = eh[0] - ys;                     // o_0 e[0] with o_0 = 1 - m_1: exact, m_1 is 0 or 1
+    kf = m[1];                                              // masks are monotone: their sum is the bin index
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      const T o = k == K - 1 ? m[k] : m[k] - m[k + 1];
+      ws = vfma(o, ew[k], ws);
+      hs = vfma(o, eh[k], hs);
+      if (k > 1) { xs = vfma(m[k], ew[k - 1], xs); ys = vfma(m[k], eh[k - 1], ys); kf += m[k]; }
+    }
+    const T base = vfma(kf, splat<T>(sc.min_bin), splat<T>(sc.lo));
+    x0 = vfma(xs, aw, base);
+    y0 = vfma(ys, ah, base);
+    bw = vfma(ws, aw, splat<T>(sc.min_bin));
+    bh = vfma(hs, ah, splat<T>(sc.min_bin));
+  } else {
+    T px = splat<T>(sc.lo), py = splat<T>(sc.lo);            // running knot k
+    T wp = vfma(ew[0], aw, splat<T>(sc.min_bin)), hp = vfma(eh[0], ah, splat<T>(sc.min_bin));   // bin k-1
+    x0 = px; y0 = py;
+    T mprev = splat<T>(1.0f);
+    bw = splat<T>(0.0f); bh = splat<T>(0.0f); kf = splat<T>(0.0f);
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      px += wp;
+      py += hp;
+      const T m = step_mask(v - (INV ? py : px), big);
+      const T o = mprev - m;                                  // one-hot of bin k-1
+      bw = k == 1 ? o * wp : vfma(o, wp, bw);
+      bh = k == 1 ? o * hp : vfma(o, hp, bh);
+      kf = k == 1 ? m : kf + m;                               // masks are monotone: their sum is the bin index
+      x0 = vfma(m, wp, x0);
+      y0 = vfma(m, hp, y0);
+      if (k == K - 1) { wp = sc.hi - px; hp = sc.hi - py; }   // last knot is exactly hi
+      else { wp = vfma(ew[k], aw, splat<T>(sc.min_bin)); hp = vfma(eh[k], ah, splat<T>(sc.min_bin)); }
+      mprev = m;
+    }
+    bw = vfma(mprev, wp, bw);
+    bh = vfma(mprev, hp, bh);
   }
-  bw = vfma(mprev, wp, bw);
-  bh = vfma(mprev, hp, bh);
   v2f ta, tb;                                               // (t_k, t_k+1) of sample a, of sample b
   slopes((int)kf.x, (int)kf.y, ta, tb);
   T d0, d1;
