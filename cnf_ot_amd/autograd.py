@@ -3,8 +3,8 @@
 `flow_forward(engine, flat_params, x, c)` / `flow_inverse(...)` return
 (points, log|det J|) and are differentiable w.r.t. the parameters and the input
 points: forward = the fused HIP flow kernel, backward = `cnf_pass_vjp` (the
-backward kernels of cnf_grad.hip).  Any loss composed from these on the host
-gets the gradients jax.value_and_grad gives the reference
+backward kernels of cnf_grad.hip and cnf_grad_pwl.hip).  Any loss composed
+from these on the host gets the gradients jax.value_and_grad gives the reference
 (cnf_ot/mfc/solvers.py:94) -- the fused loss kernels of
 `cnf_ot_amd.applications` are the fast path for the reference's own losses,
 this is the general one (and the one that parallelises the 2*dim log_prob

@@ -12,6 +12,9 @@
 
 namespace cnf {
 
+constexpr int GK = 5;              // bins
+constexpr int GP = 3 * GK + 1;     // 16 spline parameters
+
 // ---------------------------------------------------------------------------
 // Partials of the forward spline map f(x; bin) and of its log-derivative
 // ld(x; bin) = log f'(x) with respect to x and the bin's six quantities

@@ -1,7 +1,7 @@
 // cnf_common.h -- structs shared by the translation units of libcnf_ot_amd.so that work on a CnfModel (cnf_model.hip,
-// cnf_rng.hip, cnf_flow.hip, cnf_grad.hip, cnf_importance.hip): the model object, the kernels' view of it, the dim-2
-// table route, the list of compiled shapes, the argument checks and the launch tail.  The declarations of functions
-// that cross units: cnf_host.h.
+// cnf_rng.hip, cnf_flow.hip, cnf_grad.hip, cnf_grad_pwl.hip, cnf_importance.hip): the model object, the kernels' view
+// of it, the dim-2 table route, the list of compiled shapes, the argument checks and the launch tails (the model-free
+// cnf_step.hip uses those too).  The declarations of functions that cross units: cnf_host.h.
 #pragma once
 #include <mutex>
 #include <map>
@@ -67,7 +67,7 @@ struct CnfModel {
   int last_pwl_builder;   // the builder (1 / 2) of the most recent table build, 0 before the first
   // table workspaces [sets][L][PWL_TBL], one per stream (calls on different streams never share one).
   // Allocated ONLY by cnf_model_reserve; the compute entry points look theirs up and never allocate.
-  // cnf_grad_enable: per-piece gradient statistics of the table backward (cnf_grad.hip), PWL_STAT_SLICES slices
+  // cnf_grad_enable: per-piece gradient statistics of the table backward (cnf_grad_pwl.hip), PWL_STAT_SLICES slices
   float* pwl_stats;
   // retired: blocks of this stream outgrown by a later reservation, kept alive for graphs captured on them
   struct PwlWorkspace { float* tables; int64_t sets; uint32_t epoch; std::vector<float*> retired; };
@@ -204,6 +204,14 @@ static int launch(CnfModel* m, K kernel, int64_t grid, int threads, size_t lds, 
   return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 
+// ... and its sibling for the kernels that report no path (the backward's, whose entry points set theirs themselves, and
+// the step's, which have no model): the launch and the mapped error.  ensure_lds, where needed, is the caller's.
+template <class K, class... A>
+static int launch_plain(K kernel, int64_t grid, int threads, size_t lds, hipStream_t stream, const A&... a) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, a...);
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
 // Workgroups of `kernel` (threads, dynamic LDS bytes) that fit on one CU at a time (registers, LDS, waves), cached.
 template <class K>
 static inline int resident_blocks_per_cu(K kernel, int threads, size_t lds) {
@@ -278,6 +286,25 @@ static inline int wait_for_params(CnfModel* m, hipStream_t stream) {
   if (m->prep_event && m->prep_stream != (void*)stream)
     if (hipStreamWaitEvent(stream, m->prep_event, 0) != hipSuccess) return CNF_ERR_HIP;
   return CNF_OK;
+}
+
+// The checks of a backward entry point on its model, in this order for those asked for in `what`: CHECK_MODEL -- the
+// parameters are set and the backward serves the config; CHECK_SLABS -- cnf_grad_enable has made room for gradient
+// slabs; CHECK_WAIT -- wait_for_params.  An entry point asks CHECK_MODEL before and the rest after its own return for
+// an empty call; where one keeps another order, that check is written out there.
+enum { CHECK_MODEL = 1, CHECK_SLABS = 2, CHECK_WAIT = 4 };
+static inline int backward_check(CnfModel* m, int what, hipStream_t stream) {
+  if ((what & CHECK_MODEL) && !m->params_set) return CNF_ERR_INVALID;
+  if ((what & CHECK_MODEL) && !cnf_grad_supported(&m->cfg)) return CNF_ERR_UNSUPPORTED;
+  if ((what & CHECK_SLABS) && !m->grad_slabs) return CNF_ERR_INVALID;
+  return (what & CHECK_WAIT) ? wait_for_params(m, stream) : CNF_OK;
+}
+
+// Zeroes a call's n_sums sums on its stream: CNF_ERR_HIP (< 0), 1 when the call has work to launch, or 0 -- no sum
+// or no point: what an empty call returns (CNF_OK).
+static inline int zero_sums(double* sums, int64_t n_sums, int64_t n_points, hipStream_t stream) {
+  if (n_sums > 0 && hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_sums, stream) != hipSuccess) return CNF_ERR_HIP;
+  return n_sums > 0 && n_points > 0;
 }
 
 static inline cnf::ModelArgs model_args(const CnfModel* m) {

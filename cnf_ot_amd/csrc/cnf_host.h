@@ -9,7 +9,28 @@
 void pwl_workspace(CnfModel* m, hipStream_t stream, float** tables, int64_t* sets, uint32_t** flag = nullptr,
                    uint32_t* epoch = nullptr);
 
-// ---- cnf_flow.hip (called by cnf_grad.hip) --------------------------------------------------------------------------
+// ---- cnf_grad.hip (called by cnf_grad_pwl.hip) ----------------------------------------------------------------------
+// grad_finish_kernel: grad += the sum of the first n_slabs gradient slabs (amax != null: the table backward's, whose
+// adjoint maximum it clears)
+int grad_finish(const CnfModel* m, int64_t n_slabs, const float* params, float* grad, uint32_t* amax, hipStream_t stream);
+
+// ---- cnf_grad_pwl.hip (called by cnf_grad.hip) ----------------------------------------------------------------------
+// bytes of CnfModel::pwl_stats for a flow of L layers (cnf_grad_enable allocates and clears them)
+size_t pwl_stats_bytes(int L);
+// The table form of cnf_pass_vjp (its conditions: with the definition).  CNF_ERR_UNSUPPORTED: the caller runs the MLP
+// backward.  seed_sums != null: the density-fit form; built != null: on tables already built (cnf_kinetic_potential_vjp).
+int pass_vjp_pwl(CnfModel* m, int to_base, const float* pts, const float* c, int64_t c_block, const float* ybar,
+                 const float* ldbar, float* xbar, float* grad, const float* params, int64_t B, hipStream_t stream,
+                 float seed_coef = 0.0f, double* seed_sums = nullptr, const float* built = nullptr);
+
+// ---- cnf_step.hip (called by cnf_grad_pwl.hip) ----------------------------------------------------------------------
+// term_residual_kernel over n checked rows, the arguments of cnf_term_residual (its sums already zeroed); amax != null:
+// the kernel also leaves the largest |rbar| and the non-finite flag there, as adjoint_max_kernel would
+int term_residual_launch(int32_t kind, const float* r, const float* aux, int64_t n, int64_t count, int32_t D,
+                         int32_t subtype, float p0, float loss_coef, double* sums, float* rbar, float* auxbar,
+                         uint32_t* amax, hipStream_t stream);
+
+// ---- cnf_flow.hip (called by cnf_grad_pwl.hip) ----------------------------------------------------------------------
 // builds the dim-2 conditioner tables (cnf_pwl.h) of n slices -- conditions c[0 .. n) on the device --
 // into the stream's reserved workspace and returns them; CNF_ERR_UNSUPPORTED if the configuration has no table path
 // or the stream's reservation (cnf_model_reserve) is smaller than n.  Used by the table form of cnf_pass_vjp.

@@ -1,6 +1,6 @@
 // cnf_terms.h -- the per-sample math of the loss terms (applications.py), one definition each: the forward loss
-// kernels (cnf_flow.hip), the fused backward and the term epilogues (cnf_grad.hip) all call these; and of the
-// importance-sampling target (cnf_importance.hip).
+// kernels (cnf_flow.hip), the fused backward (cnf_grad.hip) and the term epilogues (cnf_step.hip) all call these; and
+// of the importance-sampling target (cnf_importance.hip).
 //
 // Coordinates are read through an accessor `x(d)` (an LDS column, a GROW-strided tile column, a row-major point,
 // or a sample pair held in registers); T is the lane type (float, v2f, double).  Formulas that call a transcendental

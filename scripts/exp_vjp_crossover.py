@@ -1,5 +1,5 @@
-"""Where the table form of cnf_pass_vjp starts to pay: both forms over pass sizes around the thresholds of cnf_grad.hip
-(slices >= 8 192 points, >= 524 288 points per pass)."""
+"""Where the table form of cnf_pass_vjp starts to pay: both forms over pass sizes around the thresholds of cnf_common.h
+(slices >= 8 192 points, >= 262 144 points per pass)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of every kernel of a HIP source (hipcc -S --cuda-device-only):
   python scripts/kernel_resources.py cnf_ot_amd/csrc/UNIT.hip [--full]     (one translation unit: cnf_flow.hip,
-  cnf_rng.hip, cnf_grad.hip, ...)"""
+  cnf_rng.hip, cnf_grad.hip, cnf_grad_pwl.hip, cnf_step.hip, ...)"""
 import os, re, subprocess, sys, tempfile
 src = sys.argv[1]
 flags = ([] if "--full" in sys.argv else ["-DCNF_MINIMAL_CONFIGS"]) + os.environ.get("CNF_EXTRA_FLAGS", "").split()
