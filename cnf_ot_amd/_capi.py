@@ -170,6 +170,12 @@ SYMBOLS = {
   "cnf_mmd_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_mmd2": (ctypes.c_int, [ctypes.POINTER(CnfMmdSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, _P, _P,
                               _I64, _P]),
+  # the Sinkhorn divergence of point clouds (eps: a host array of doubles): sums [S, 6] doubles, potentials
+  # [S, 2 N + 2 M], xgrad and xmap [S, N, D]
+  "cnf_sinkhorn_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_sinkhorn_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_sinkhorn": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
+                                  ctypes.c_int32, _P, _P, _P, _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

@@ -1146,6 +1146,46 @@ def mmd_loss_fn(model, dim, params, target, cond, rng, batch_size, bandwidths=No
   return res["mmd2"].sum() / S
 
 
+# ---- the same in transport units: the Sinkhorn divergence between the flow's samples and given target samples --------
+
+def sinkhorn_loss_fn(model, dim, params, target, cond, rng, batch_size, eps=0.05, schedule=None, shard=None, grad=None):
+  """The mean over the times of `cond` of the Sinkhorn divergence S_eps (utils.sinkhorn: cost |x - y|^2 / 2, an
+  estimate of W2^2 / 2) between batch_size flow samples at that time -- the same base draw of `rng` for every time, as
+  the other terms -- and the samples `target`: [M, D], or [S, M, D] with one set per time.  schedule: the eps of every
+  iteration (None: utils.sinkhorn_schedule of the samples and the target at `eps`, which reads the samples' bounding
+  box back from the device; a fixed schedule does not).  With `grad` (the convention of the other term functions;
+  `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_sinkhorn call (value and the envelope
+  gradient d / d samples) and ONE cnf_pass_vjp call.  Single rank: the pairs across ranks would need an all-gather of the
+  samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
+  from . import utils
+  shard = shard if shard is not None else current_shard()
+  if shard.world > 1:
+    raise ValueError("sinkhorn_loss_fn: single rank only (pairs across ranks need an all-gather of the samples)")
+  conds = _conds(cond)
+  S = _n_conds(conds)
+  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+  if tgt.dim() == 2:
+    tgt = tgt[None].expand(S, -1, -1)
+  if tgt.dim() != 3 or tgt.shape[0] != S:
+    raise ValueError(f"sinkhorn_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
+  utils.sinkhorn_check_shapes((S, int(batch_size), int(dim)), tgt.shape)
+  if schedule is not None:
+    schedule = utils.sinkhorn_check_schedule(schedule)
+  elif not (float(eps) > 0.0 and np.isfinite(float(eps))):
+    raise ValueError(f"sinkhorn_loss_fn: eps must be positive and finite, not {eps}")
+  ctx = _Ctx(model, params, rng, shard, grad)
+  be = ctx.be
+  z, _, count = ctx.noise(batch_size)
+  zs = z.repeat(S, 1)                                         # the same draw for every time
+  c = be.slice_conds(conds)
+  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
+  tgt = tgt.to(device=samples.device, dtype=torch.float32)
+  res = utils.sinkhorn(samples.view(S, count, -1), tgt, eps, schedule, want_grad=grad is not None)
+  if grad is not None:
+    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
+  return res["divergence"].sum() / S
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

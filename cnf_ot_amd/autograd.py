@@ -119,3 +119,34 @@ def mmd2(x: torch.Tensor, y: torch.Tensor, bandwidths, kind: str = "gaussian"):
   with `flow_forward` a flow trains on samples through ordinary autograd (applications.mmd_loss_fn is the hand-written
   fast path).  The bandwidths are constants (utils.median_bandwidths(y) gives the usual choice)."""
   return _Mmd2.apply(x, y, bandwidths, kind)
+
+
+class _Sinkhorn(torch.autograd.Function):
+  """utils.sinkhorn with its envelope gradient: in x from the same cnf_sinkhorn call (xgrad), in y from a second call
+  with the roles swapped (the divergence is symmetric)."""
+
+  @staticmethod
+  def forward(ctx, x, y, eps, schedule):
+    from .utils import sinkhorn as _sinkhorn
+    need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    res = _sinkhorn(x.detach(), y.detach(), eps, schedule, want_grad=need_x)
+    gy = _sinkhorn(y.detach(), x.detach(), eps, res["schedule"], want_grad=True)["grad"] if need_y else None
+    ctx.save_for_backward(res["grad"], gy)
+    return res["divergence"]
+
+  @staticmethod
+  def backward(ctx, gbar):
+    gx, gy = ctx.saved_tensors
+    w = gbar.to(torch.float32)
+    scale = lambda g: None if g is None else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
+    return scale(gx), scale(gy), None, None
+
+
+def sinkhorn_divergence(x: torch.Tensor, y: torch.Tensor, eps: float = 0.05, schedule=None):
+  """The Sinkhorn divergence S_eps (cost |x - y|^2 / 2, uniform weights) between the sample sets x [N, D] or [S, N, D]
+  and y [M, D] or [S, M, D], [S] float64 ([1] for 2-D inputs), differentiable in x (and in y, by a second call) through
+  the ENVELOPE gradient of cnf_sinkhorn: the potentials are held fixed, which is exact at the fixed point of the
+  recursion (utils.sinkhorn's `change` says how far the schedule stopped from it).  The schedule is a constant
+  (None: utils.sinkhorn_schedule(x, y, eps)).  With `flow_forward` a flow trains on target samples in transport units
+  through ordinary autograd (applications.sinkhorn_loss_fn is the hand-written fast path)."""
+  return _Sinkhorn.apply(x, y, eps, schedule)

@@ -49,3 +49,7 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
 // ---- cnf_mmd.hip ----------------------------------------------------------------------------------------------------
 // mmd_kernel and mmd_finish_kernel behind cnf_mmd_workspace / cnf_mmd_splits / cnf_mmd2 (include/cnf_ot_amd.h).
 // Model-free, like cnf_fp_particles.hip: the unit calls into no other and none calls into it.
+
+// ---- cnf_sinkhorn.hip -----------------------------------------------------------------------------------------------
+// sinkhorn_pair_kernel, sinkhorn_merge_kernel and sinkhorn_finish_kernel behind cnf_sinkhorn_workspace /
+// cnf_sinkhorn_splits / cnf_sinkhorn (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).

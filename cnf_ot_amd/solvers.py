@@ -485,6 +485,86 @@ def print_fp_two_sample(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row))
 
 
+# ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------
+
+OT_REFERENCE_KEYS = ("coupling_cost", "kinetic_energy", "w2_flow", "gap_flow", "map_rmse", "map_blur", "w2_problem",
+                     "w2_closed_form", "fit_0", "fit_T", "floor", "change", "eps", "n", "iterations")
+
+
+def evaluate_ot_reference(config, model: FlowModel, params: Params, n=8192, eps=0.05, seed=0) -> Dict[str, Any]:
+  """What an ot flow is judged against: at the optimum the kinetic energy E|v|^2 / 2 over [0, 1] equals
+  W2^2(source, target) / 2, and the flow's own map from t = 0 to t = T is the Monge map between its endpoints.  From
+  one base draw z of `seed`: x0 = flow(z, 0) and xT = flow(z, T), the flow's own coupling; src: n draws of the
+  configured source (ot.source, the training's own draw), tgt and a second, independent draw: n samples of N(0, I).
+  Five Sinkhorn divergences S_eps (utils.sinkhorn: cost |x - y|^2 / 2, so every number is in the units of W2^2 / 2) in
+  ONE cnf_sinkhorn call, on one schedule (utils.sinkhorn_schedule over all sets).  Floats:
+    coupling_cost   mean |xT - x0|^2 / 2: >= W2^2 / 2 of the flow's own endpoints, <= its kinetic energy
+    kinetic_energy  utils.calc_kinetic_energy at batch n, 1 000 slices
+    w2_flow         S_eps(x0, xT);  gap_flow = coupling_cost - w2_flow: what the flow's map pays above the optimal one
+    map_rmse        the rms of |xT - T_eps(x0)|, T_eps the barycentric map of (x0, xT); beside it
+    map_blur        the rms of |x0 - Txx(x0)|, the barycentric map of x0 onto itself: what eps alone smears
+    w2_problem      S_eps(src, tgt): the value training aims for
+    w2_closed_form  (|m|^2 + tr(A + I - 2 A^(1/2))) / 2 for the Gaussian source N(m, A); None for the mixture
+    fit_0, fit_T    S_eps(x0, src) and S_eps(xT, tgt): the boundary fits in transport units
+    floor           S_eps between the two target draws: the Monte-Carlo level of n points
+    change          [5, 2], cnf_sinkhorn's convergence diagnostic per set (utils.sinkhorn), as lists
+    eps, n, iterations
+  ValueError before any device work: a problem type other than ot, a dimension other than the sources' 2, n outside
+  2..2^20, an eps that is not positive and finite.  Single process."""
+  g = config["general"]
+  if g["type"] != "ot":
+    raise ValueError(f"evaluate_ot_reference: defined for ot only, not {g['type']}")
+  dim, source = g["dim"], config["ot"].get("source", "mixture")
+  if dim != 2 or source not in ("mixture", "gaussian"):
+    raise ValueError(f"evaluate_ot_reference: the ot sources are 2-D ('mixture' or 'gaussian'), not {source!r} at dim {dim}")
+  n, eps, seed = int(n), float(eps), int(seed)
+  utils.sinkhorn_check_shapes((5, n, dim), (5, n, dim))
+  if not (eps > 0.0 and np.isfinite(eps)):
+    raise ValueError(f"evaluate_ot_reference: eps must be positive and finite, not {eps}")
+  from .distributed import Shard
+  T = 1.0
+  ctx = applications._Ctx(model, params, seed + 1, Shard(0, 1))
+  be = ctx.be
+  z = be.normal(seed, n)
+  ends, _ = be.forward_logdet(z.repeat(2, 1), be.slice_conds(np.array([0.0, T], dtype=np.float32)), want_logdet=False)
+  x0, xT = ends[:n], ends[n:]
+  zs, start, count = ctx.noise(n)
+  src = applications._source_samples(ctx, zs, start, count, n, source)
+  tgt, tgt2 = be.normal(seed + 2, n), be.normal(seed + 3, n)
+  x = torch.stack([x0, src, x0, xT, tgt2])
+  y = torch.stack([xT, tgt, src, tgt, tgt])
+  res = utils.sinkhorn(x, y, eps, want_grad=True, want_map=True)
+  div = res["divergence"].tolist()
+  tmap, txx = res["map"][0].double(), res["map"][0].double() + n * res["grad"][0].double()
+  coupling = float(0.5 * ((xT - x0).double() ** 2).sum(1).mean())
+  closed = None
+  if source == "gaussian":
+    m, A = np.array([-3.0, -3.0]), np.array([[5.0, 1.0], [1.0, 0.5]])
+    w, _ = np.linalg.eigh(A)
+    closed = float(0.5 * (m @ m + np.trace(A) + dim - 2.0 * np.sqrt(w).sum()))
+  return {"coupling_cost": coupling,
+          "kinetic_energy": float(utils.calc_kinetic_energy(model.apply.sample, params, seed, batch_size=n, t_size=1000,
+                                                            dim=dim)),
+          "w2_flow": div[0], "gap_flow": coupling - div[0],
+          "map_rmse": float(((xT.double() - tmap) ** 2).sum(1).mean().sqrt()),
+          "map_blur": float(((x0.double() - txx) ** 2).sum(1).mean().sqrt()),
+          "w2_problem": div[1], "w2_closed_form": closed, "fit_0": div[2], "fit_T": div[3], "floor": div[4],
+          "change": res["change"].tolist(), "eps": eps, "n": n, "iterations": len(res["schedule"])}
+
+
+def print_ot_reference(res: Dict[str, Any]) -> None:
+  """evaluate_ot_reference's lines"""
+  print("optimal-transport reference (Sinkhorn divergence, eps {:.3g}, {} points, {} iterations; units of W2^2 / 2):".format(
+    res["eps"], res["n"], res["iterations"]))
+  closed = "n/a" if res["w2_closed_form"] is None else "{:.4f}".format(res["w2_closed_form"])
+  print("  problem: S(source, target) {:.4f} | closed form {} | floor {:.3e}".format(res["w2_problem"], closed, res["floor"]))
+  print("  flow: kinetic energy {:.4f} | coupling cost {:.4f} | S(x0, xT) {:.4f} | gap {:.3e}".format(
+    res["kinetic_energy"], res["coupling_cost"], res["w2_flow"], res["gap_flow"]))
+  print("  map: rms |xT - T(x0)| {:.3e} | blur of eps alone {:.3e}".format(res["map_rmse"], res["map_blur"]))
+  print("  boundary fits: S(x0, source) {:.3e} | S(xT, target) {:.3e}".format(res["fit_0"], res["fit_T"]))
+  print("  largest change of the final pass: {:.2e}".format(max(max(c) for c in res["change"])))
+
+
 # ---- the fit to the densities known in closed form (the reference's kl_ess, tests/test_fit_prob.py:50-56) -----------
 
 def evaluate_fit(config, model: FlowModel, params: Params, rng, batch_size: int = 1 << 20) -> Dict[str, Any]:
@@ -605,17 +685,20 @@ def _eval_rng(seed, step):
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
-         two_sample: bool = False) -> Dict[str, Any]:
+         two_sample: bool = False, ot_reference: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
-  returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table."""
+  returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
+  print evaluate_ot_reference's lines."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
     raise Exception(f"Unknown problem type: {_type}...")
   if two_sample and _type != "fp":      # (before the training run, not after it)
     raise ValueError(f"--two-sample compares the flow with the fp particle reference: not defined for {_type}")
+  if ot_reference and _type != "ot":
+    raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
 
   def log(step, loss):
@@ -667,6 +750,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fit(evaluate_fit(config, model, params, _eval_rng(seed, -2)))
   if two_sample:
     print_fp_two_sample(evaluate_fp_two_sample(config, model, params))
+  if ot_reference:
+    print_ot_reference(evaluate_ot_reference(config, model, params))
   return res
 
 
@@ -687,10 +772,13 @@ def _parse(argv):
   p.add_argument("--two-sample", action="store_true",
                  help="print MMD^2 and the energy distance, in the full dimension, between the flow's samples and the "
                       "particle reference at the figure's times, each beside its Monte-Carlo floor (fp)")
+  p.add_argument("--ot-reference", action="store_true",
+                 help="print the Sinkhorn divergence between source and target samples, the flow's coupling cost and "
+                      "kinetic energy beside it, and the distance of the flow's map from the barycentric map (ot)")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
-       path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample)
+       path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference)

@@ -441,3 +441,117 @@ def mmd2(x, y, bandwidths=None, kind="gaussian", want_grad=False) -> dict:
   if want_grad:
     out["grad"] = grad if np.ndim(x) == 3 else grad[0]
   return out
+
+
+# ---- the Sinkhorn divergence: an optimal-transport estimate between point clouds, in transport units -----------------
+# Log-domain Sinkhorn on C(x, y) = |x - y|^2 / 2, debiased: S_eps(x, y) = OT_eps(x, y) - OT_eps(x, x) / 2 - OT_eps(y, y) / 2,
+# with the dual potentials, the barycentric map (an estimate of the Monge map) and the gradient in x.  The iteration
+# count and the eps of every iteration are inputs of the kernel (cnf_sinkhorn): the schedule below is
+# the usual annealing, and `change` in the result says how far from its fixed point the recursion stopped.
+
+SINKHORN_MAX_ITERS, SINKHORN_MAX_POINTS = 512, 1 << 20
+
+
+def _sinkhorn_sets(t, name):
+  t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+  if t.dim() == 2:
+    t = t[None]
+  if t.dim() != 3:
+    raise ValueError(f"sinkhorn: {name} must be [N, D] or [S, N, D], not {tuple(t.shape)}")
+  return t
+
+
+def sinkhorn_check_shapes(x_shape, y_shape):
+  """ValueError for sets cnf_sinkhorn refuses: ([S, N, D], [S, M, D]) with S in 1..64, N, M in 2..2^20, D in 1..14."""
+  (S, N, D), (Sy, M, Dy) = x_shape, y_shape
+  if S != Sy or D != Dy:
+    raise ValueError(f"sinkhorn: x {tuple(x_shape)} and y {tuple(y_shape)} differ in the number of sets or in the dimension")
+  if (not 1 <= S <= _capi.MMD_MAX_SETS or not 1 <= D <= _capi.MMD_MAX_DIM or min(N, M) < 2
+      or max(N, M) > SINKHORN_MAX_POINTS):
+    raise ValueError(f"sinkhorn: needs 1..{_capi.MMD_MAX_SETS} sets of 2..2^20 points of dimension 1..{_capi.MMD_MAX_DIM}, "
+                     f"not x {tuple(x_shape)}, y {tuple(y_shape)}")
+
+
+def sinkhorn_check_schedule(schedule):
+  """The schedule as a list of floats -- ValueError for what cnf_sinkhorn refuses in one: no entry or more than 512, an
+  eps that is not positive and finite or whose inverse leaves float32's range."""
+  eps = [float(e) for e in np.asarray(schedule.cpu() if torch.is_tensor(schedule) else schedule, dtype=np.float64).reshape(-1)]
+  if not 1 <= len(eps) <= SINKHORN_MAX_ITERS:
+    raise ValueError(f"sinkhorn: a schedule has 1..{SINKHORN_MAX_ITERS} entries, not {len(eps)}")
+  for e in eps:
+    if not (e > 0.0 and np.isfinite(e) and 1.2e-38 <= 1.0 / e <= 2.0e38):
+      raise ValueError(f"sinkhorn: every eps must be positive and finite, with 1 / eps in float32's range: {e}")
+  return eps
+
+
+def sinkhorn_schedule(x, y, eps, ratio=0.8, extra=10):
+  """The annealing schedule of `sinkhorn`, a list of floats: the squared diagonal of the joint bounding box of x and y
+  (all sets), times ratio^k for k = 0, 1, ... while that is > eps, then `extra` entries at eps.  ValueError for an eps
+  that is not positive and finite, a ratio outside (0, 1), extra < 0, an empty schedule or more than 512 entries."""
+  eps, ratio, extra = float(eps), float(ratio), int(extra)
+  if not (eps > 0.0 and np.isfinite(eps)) or not 0.0 < ratio < 1.0 or extra < 0:
+    raise ValueError(f"sinkhorn_schedule: needs eps > 0, 0 < ratio < 1 and extra >= 0, not {eps}, {ratio}, {extra}")
+  pts = [t.detach().reshape(-1, t.shape[-1]).double() for t in (_sinkhorn_sets(x, "x"), _sinkhorn_sets(y, "y"))]
+  lo = torch.minimum(pts[0].min(0).values.cpu(), pts[1].min(0).values.cpu())
+  hi = torch.maximum(pts[0].max(0).values.cpu(), pts[1].max(0).values.cpu())
+  v = float(((hi - lo) ** 2).sum())
+  if not np.isfinite(v):
+    raise ValueError("sinkhorn_schedule: the points are not finite")
+  out = []
+  while v > eps and len(out) + extra <= SINKHORN_MAX_ITERS:
+    out.append(v)
+    v *= ratio
+  out += [eps] * extra
+  if len(out) > SINKHORN_MAX_ITERS:
+    raise ValueError(f"sinkhorn_schedule: more than {SINKHORN_MAX_ITERS} iterations (diagonal^2 {out[0]:.3g}, eps {eps}, "
+                     f"ratio {ratio}, extra {extra})")
+  if not out:
+    raise ValueError("sinkhorn_schedule: an empty schedule (the bounding box is within eps and extra = 0)")
+  return out
+
+
+def sinkhorn(x, y, eps=0.05, schedule=None, want_grad=False, want_map=False, want_potentials=False) -> dict:
+  """The Sinkhorn divergence S_eps between the point sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D] (set s of x
+  against set s of y; uniform weights, cost |x - y|^2 / 2), ONE cnf_sinkhorn call over all sets: len(schedule)
+  averaged Jacobi iterations of the four potentials f, g (x against y), p (x against x), q (y against y) and a final
+  pass at the last eps (the recursion: include/cnf_ot_amd.h).  schedule: the eps of every iteration (None:
+  sinkhorn_schedule(x, y, eps); with a schedule `eps` is not used).  float32 on the device (float64 inputs are rounded;
+  host inputs are uploaded).  Returns a dict:
+    divergence [S]  (sum f* - sum p*) / N + (sum g* - sum q*) / M (float64): an estimate of W2^2 / 2
+    ot_xy [S]       sum f* / N + sum g* / M, the entropic cost of x against y alone
+    change [S, 2]   the largest |f* - f|, |g* - g| and |p* - p|, |q* - q| of the final pass: 0 at the fixed point
+    grad            want_grad: [S, N, D] float32 ([N, D] for 2-D x), the envelope gradient of the divergence in x (the
+                    potentials held fixed: exact at the fixed point); else None
+    map             want_map: the barycentric map T(x_i) = sum_j pi_ij y_j / sum_j pi_ij, shaped like grad; else None
+    f, g, p, q      want_potentials: [S, N], [S, M], [S, N], [S, M] float32; else None
+    schedule        the list of eps used
+  Two calls give the same bits, and the numbers do not depend on the want_ flags.  ValueError before any device work
+  for what the C ABI refuses and for x and y that differ in S or D."""
+  from .applications import _OnDevice, _stream_ptr
+  x3, y3 = _sinkhorn_sets(x, "x"), _sinkhorn_sets(y, "y")
+  sinkhorn_check_shapes(x3.shape, y3.shape)
+  sched = sinkhorn_check_schedule(sinkhorn_schedule(x3, y3, eps) if schedule is None else schedule)
+  S, N, D = x3.shape
+  M = y3.shape[1]
+  dev = x3.device if x3.is_cuda else (y3.device if y3.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+  x3 = x3.detach().to(device=dev, dtype=torch.float32).contiguous()
+  y3 = y3.detach().to(device=dev, dtype=torch.float32).contiguous()
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_sinkhorn_workspace(S, N, M, D, C.byref(nbytes)), "cnf_sinkhorn_workspace")
+  ws = torch.empty(-(-nbytes.value // 8), dtype=torch.float64, device=dev)
+  sums = torch.empty(S, 6, dtype=torch.float64, device=dev)
+  grad = torch.empty(S, N, D, dtype=torch.float32, device=dev) if want_grad else None
+  tmap = torch.empty(S, N, D, dtype=torch.float32, device=dev) if want_map else None
+  pot = torch.empty(S, 2 * (N + M), dtype=torch.float32, device=dev) if want_potentials else None
+  ptr = lambda t: None if t is None else t.data_ptr()
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_sinkhorn(S, x3.data_ptr(), N, y3.data_ptr(), M, D, (C.c_double * len(sched))(*sched), len(sched),
+                                 sums.data_ptr(), ptr(pot), ptr(grad), ptr(tmap), ws.data_ptr(), ws.numel() * 8,
+                                 _stream_ptr(dev)), "cnf_sinkhorn")
+  one = np.ndim(x) != 3
+  f, g, p, q = (None,) * 4 if pot is None else pot.split([N, M, N, M], dim=1)
+  return {"divergence": (sums[:, 0] - sums[:, 2]) / N + (sums[:, 1] - sums[:, 3]) / M,
+          "ot_xy": sums[:, 0] / N + sums[:, 1] / M, "change": sums[:, 4:6],
+          "grad": grad if grad is None or not one else grad[0], "map": tmap if tmap is None or not one else tmap[0],
+          "f": f, "g": g, "p": p, "q": q, "schedule": sched}

@@ -793,6 +793,43 @@ int cnf_mmd2(const CnfMmdSpec *spec, int32_t S, const float *x, int64_t N, const
              int64_t M, int32_t D, double *sums, float *xgrad, void *workspace,
              int64_t workspace_bytes, void *stream);
 
+/* ---- the Sinkhorn divergence between point clouds: the optimal-transport reference of the ot problems ---------------
+ * Debiased entropic optimal transport with the cost C(x, y) = |x - y|^2 / 2 and uniform weights, in the log domain.
+ * Model-free.  For S independent sets, x [S, N, D] against y [S, M, D] (device, float32) and a HOST array
+ * eps[n_iters], four potentials per set, all 0 at the start: f [N], g [M] (x against y), p [N] (x against x), q [M]
+ * (y against y).  With T(h; rows, cols, e)_i = -e log((1 / n_cols) sum_j exp((h_j - C(row_i, col_j)) / e)), iteration
+ * k = 0 .. n_iters - 1 updates the four simultaneously from the old state,
+ *   f <- (f + T(g; x, y, eps_k)) / 2,  g <- (g + T(f; y, x, eps_k)) / 2,
+ *   p <- (p + T(p; x, x, eps_k)) / 2,  q <- (q + T(q; y, y, eps_k)) / 2,
+ * and a final pass at eps[n_iters - 1] takes f* = T(g), g* = T(f), p* = T(p), q* = T(q) without averaging.  The
+ * iteration count and every eps are the caller's: the call decides nothing about convergence.
+ * cnf_sinkhorn writes
+ *   sums [S, 6] (device, double, overwritten): sum f*, sum g*, sum p*, sum q*, max(|f* - f|, |g* - g|) and
+ *     max(|p* - p|, |q* - q|) over the final pass (the convergence diagnostic).  The caller forms
+ *     OT_eps(x, y) = sum f* / N + sum g* / M and S_eps(x, y) = (sum f* - sum p*) / N + (sum g* - sum q*) / M;
+ *   potentials [S, 2 N + 2 M] (device, float32, or NULL): per set f* [N], g* [M], p* [N], q* [M];
+ *   xmap [S, N, D] (device, float32, or NULL): the barycentric map Txy(x_i) = sum_j w_ij y_j of the final pass,
+ *     w_ij = exp((g_j - C_ij) / eps) normalised over j;
+ *   xgrad [S, N, D] (device, float32, or NULL): (Txx(x_i) - Txy(x_i)) / N, Txx the same map of x onto itself under p.
+ *     It is the ENVELOPE gradient of S_eps in x_i (potentials held fixed): exact at the fixed point of the recursion,
+ *     approximate before it.
+ * Every iteration is one pair launch over the four blocks of all sets, the columns of a block split over
+ * cnf_sinkhorn_splits(S, N, M, D) workgroups (a function of the sizes alone), and one merge launch; every eps goes to
+ * its launches by value.  No atomics: two calls are bit-identical, the sums do not depend on which optional outputs
+ * are asked for, and the result does not depend on what the workspace held.
+ * cnf_sinkhorn_workspace: the bytes of device workspace (8-byte aligned) a call needs; no HIP call.  The workspace
+ * is the caller's: cnf_sinkhorn neither allocates, synchronises nor reads the device (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL x, y, eps, sums or workspace; S outside 1..64; D
+ * outside 1..14; N or M outside 2..2^20; n_iters outside 1..512; an eps that is not finite and > 0, or for which 1 / eps
+ * or log2(e) / eps is not a finite normal float32; a workspace smaller than cnf_sinkhorn_workspace says. */
+int cnf_sinkhorn_workspace(int32_t S, int64_t N, int64_t M, int32_t D, int64_t *bytes);
+/* the column splits of a block at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_sinkhorn_splits(int32_t S, int64_t N, int64_t M, int32_t D);
+int cnf_sinkhorn(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int32_t D,
+                 const double *eps, int32_t n_iters, double *sums, float *potentials,
+                 float *xgrad, float *xmap, void *workspace, int64_t workspace_bytes,
+                 void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
