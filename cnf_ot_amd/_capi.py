@@ -176,6 +176,13 @@ SYMBOLS = {
   "cnf_sinkhorn_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_sinkhorn": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
                                   ctypes.c_int32, _P, _P, _P, _P, _P, _I64, _P]),
+  # the sliced Wasserstein distance of point clouds for given directions theta [P, D], G projections at a time: sums
+  # [S, P + 2] doubles (the P values, their mean, their maximum), grad [S, N, D]
+  "cnf_sliced_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.POINTER(_I64)]),
+  "cnf_sliced_tile": (ctypes.c_int, []),
+  "cnf_sliced_w2": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P,
+                                   _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

@@ -1186,6 +1186,46 @@ def sinkhorn_loss_fn(model, dim, params, target, cond, rng, batch_size, eps=0.05
   return res["divergence"].sum() / S
 
 
+# ---- the same at any batch size: the sliced Wasserstein distance between the flow's samples and target samples ------
+
+def sliced_loss_fn(model, dim, params, target, cond, rng, batch_size, directions=None, n_proj=64, seed=0, shard=None,
+                   grad=None):
+  """The mean over the times of `cond` of the sliced Wasserstein distance (utils.sliced_wasserstein: cost |.|^2 / 2)
+  between batch_size flow samples at that time -- the same base draw of `rng` for every time, as the other terms -- and
+  the samples `target`: [M, D], or [S, M, D] with one set per time.  directions: [P, dim], constants (None:
+  utils.sliced_directions(dim, n_proj, seed)).  N log N per projection, so the term is usable at the flow's own
+  training batch sizes, where the pair statistics are not.  With `grad` (the convention of the other term functions;
+  `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_sliced_w2 call (value and the
+  envelope gradient d / d samples) and ONE cnf_pass_vjp call.  Single rank: the sort would need an all-gather of the
+  samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
+  from . import utils
+  shard = shard if shard is not None else current_shard()
+  if shard.world > 1:
+    raise ValueError("sliced_loss_fn: single rank only (the sort across ranks needs an all-gather of the samples)")
+  conds = _conds(cond)
+  S = _n_conds(conds)
+  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+  if tgt.dim() == 2:
+    tgt = tgt[None].expand(S, -1, -1)
+  if tgt.dim() != 3 or tgt.shape[0] != S:
+    raise ValueError(f"sliced_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
+  if directions is None:
+    directions = utils.sliced_directions(int(dim), 1 if int(dim) == 1 else n_proj, seed)
+  th = directions if torch.is_tensor(directions) else torch.as_tensor(np.asarray(directions))
+  utils.sliced_check_shapes((S, int(batch_size), int(dim)), tgt.shape, tuple(th.shape))
+  ctx = _Ctx(model, params, rng, shard, grad)
+  be = ctx.be
+  z, _, count = ctx.noise(batch_size)
+  zs = z.repeat(S, 1)                                         # the same draw for every time
+  c = be.slice_conds(conds)
+  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
+  tgt = tgt.to(device=samples.device, dtype=torch.float32)
+  res = utils.sliced_wasserstein(samples.view(S, count, -1), tgt, th, want_grad=grad is not None)
+  if grad is not None:
+    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
+  return res["sw"].sum() / S
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,

@@ -150,3 +150,33 @@ def sinkhorn_divergence(x: torch.Tensor, y: torch.Tensor, eps: float = 0.05, sch
   (None: utils.sinkhorn_schedule(x, y, eps)).  With `flow_forward` a flow trains on target samples in transport units
   through ordinary autograd (applications.sinkhorn_loss_fn is the hand-written fast path)."""
   return _Sinkhorn.apply(x, y, eps, schedule)
+
+
+class _Sliced(torch.autograd.Function):
+  """utils.sliced_wasserstein with its envelope gradient: in x from the same cnf_sliced_w2 call, in y from a second call
+  with the roles swapped (the distance is symmetric)."""
+
+  @staticmethod
+  def forward(ctx, x, y, directions):
+    from .utils import sliced_wasserstein as _sw
+    need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    res = _sw(x.detach(), y.detach(), directions, want_grad=need_x)
+    gy = _sw(y.detach(), x.detach(), directions, want_grad=True)["grad"] if need_y else None
+    ctx.save_for_backward(res["grad"], gy)
+    return res["sw"]
+
+  @staticmethod
+  def backward(ctx, gbar):
+    gx, gy = ctx.saved_tensors
+    w = gbar.to(torch.float32)
+    scale = lambda g: None if g is None else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
+    return scale(gx), scale(gy), None
+
+
+def sliced_wasserstein(x: torch.Tensor, y: torch.Tensor, directions):
+  """The sliced Wasserstein distance (cost |.|^2 / 2, uniform weights) between the sample sets x [N, D] or [S, N, D] and
+  y [M, D] or [S, M, D] over the directions [P, D] (constants: utils.sliced_directions gives the usual choice), [S]
+  float64 ([1] for 2-D inputs), differentiable in x (and in y, by a second call): backward is the gradient cnf_sliced_w2
+  stored times the incoming scalar.  With `flow_forward` a flow trains on target samples through ordinary autograd
+  (applications.sliced_loss_fn is the hand-written fast path)."""
+  return _Sliced.apply(x, y, directions)

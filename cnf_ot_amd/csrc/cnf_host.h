@@ -53,3 +53,7 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
 // ---- cnf_sinkhorn.hip -----------------------------------------------------------------------------------------------
 // sinkhorn_pair_kernel, sinkhorn_merge_kernel and sinkhorn_finish_kernel behind cnf_sinkhorn_workspace /
 // cnf_sinkhorn_splits / cnf_sinkhorn (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).
+
+// ---- cnf_sliced.hip -------------------------------------------------------------------------------------------------
+// sliced_sort_kernel, sliced_merge_kernel, sliced_w2_kernel and the three finish kernels behind cnf_sliced_workspace /
+// cnf_sliced_tile / cnf_sliced_w2 (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).

@@ -485,6 +485,67 @@ def print_fp_two_sample(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row))
 
 
+# ---- the same comparison in transport units at the full ensemble size: the sliced Wasserstein distance ---------------
+
+FP_SLICED_KEYS = ("times", "sw", "sw_floor", "max_sliced", "max_sliced_floor", "w2_marginal", "w2_marginal_floor", "n",
+                  "n_proj")
+
+
+def evaluate_fp_sliced(config, model: FlowModel, params: Params, times=None, n_particles=1 << 20, h=1e-3, seed=0,
+                       n_proj=64) -> Dict[str, Any]:
+  """How far, in the FULL dimension and in transport units, the flow's samples are from the Euler-Maruyama ensemble of
+  an fp configuration, at the ensemble size of the other evaluators: the sliced Wasserstein distance
+  (utils.sliced_wasserstein: cost |.|^2 / 2, N log N per projection, where evaluate_fp_two_sample's pair statistics stop
+  at 65 536 particles).  `times`, and the refusals, as evaluate_fp_two_sample.  The ensemble is run as its two halves;
+  n_particles / 2 flow samples (model.apply.sample of `seed`) are compared with half 0, and half 1 with half 0 -- the
+  same sizes and the same directions, utils.sliced_directions(dim, n_proj, seed).  Per time, lists of floats:
+    times
+    sw, sw_floor                  the distance of flow against half 0, and of half 1 against half 0: its Monte-Carlo level
+    max_sliced, max_sliced_floor  the largest one-dimensional cost over the directions
+    w2_marginal, w2_marginal_floor  [D] each: sqrt(2 w) with the coordinate axes as directions, the exact W2 between
+                                  the two empirical marginals of every coordinate
+    n, n_proj                     the points per set and the directions used
+  All times, flow and floor, go into ONE cnf_sliced_w2 call per direction set (2 x len(times) <= 64 sets).  Single
+  process."""
+  g = config["general"]
+  if g["type"] != "fp":
+    raise ValueError(f"evaluate_fp_sliced: defined for fp only, not {g['type']}")
+  st = figure_settings(config)
+  if st is None:
+    raise ValueError(f"evaluate_fp_sliced: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
+  n_particles = int(n_particles)
+  if n_particles < 2 or n_particles % 2:
+    raise ValueError(f"evaluate_fp_sliced: n_particles must be even and >= 2 (two halves are compared), not {n_particles}")
+  from .distributed import Shard
+  f, dim = config["fp"], g["dim"]
+  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
+  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
+  applications.fp_step_indices(ts, float(h), T)
+  n, S = n_particles // 2, len(ts)
+  utils.sliced_check_shapes((2 * S, n, dim), (2 * S, n, dim))
+  theta = utils.sliced_directions(dim, 1 if dim == 1 else n_proj, seed)
+  axes = utils.sliced_directions(dim, dim, kind="axes")
+  flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n,)) for t in ts])
+  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
+                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  x, y = torch.cat([flow.float(), h1]), torch.cat([h0, h0])
+  rnd = utils.sliced_wasserstein(x, y, theta)
+  marg = (2.0 * utils.sliced_wasserstein(x, y, axes)["per_projection"]).sqrt()
+  return {"times": [float(t) for t in ts], "sw": rnd["sw"][:S].tolist(), "sw_floor": rnd["sw"][S:].tolist(),
+          "max_sliced": rnd["max_sliced"][:S].tolist(), "max_sliced_floor": rnd["max_sliced"][S:].tolist(),
+          "w2_marginal": marg[:S].tolist(), "w2_marginal_floor": marg[S:].tolist(), "n": n, "n_proj": int(theta.shape[0])}
+
+
+def print_fp_sliced(res: Dict[str, Any]) -> None:
+  """evaluate_fp_sliced's table, one line per time"""
+  print("sliced Wasserstein distance to the particle reference ({} points per set, {} directions; units of W2^2 / 2):  "
+        "t | sw | sw floor | max sliced | floor | W2 of each marginal (floor)".format(res["n"], res["n_proj"]))
+  for t, sw, fl, mx, mfl, wm, wfl in zip(res["times"], res["sw"], res["sw_floor"], res["max_sliced"], res["max_sliced_floor"],
+                                         res["w2_marginal"], res["w2_marginal_floor"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e} | ".format(t, sw, fl, mx, mfl)
+          + " ".join("{:.3e} ({:.1e})".format(u, v) for u, v in zip(wm, wfl)))
+
+
 # ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------
 
 OT_REFERENCE_KEYS = ("coupling_cost", "kinetic_energy", "w2_flow", "gap_flow", "map_rmse", "map_blur", "w2_problem",
@@ -685,18 +746,20 @@ def _eval_rng(seed, step):
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
-         two_sample: bool = False, ot_reference: bool = False) -> Dict[str, Any]:
+         two_sample: bool = False, ot_reference: bool = False, sliced: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
-  print evaluate_ot_reference's lines."""
+  print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
     raise Exception(f"Unknown problem type: {_type}...")
   if two_sample and _type != "fp":      # (before the training run, not after it)
     raise ValueError(f"--two-sample compares the flow with the fp particle reference: not defined for {_type}")
+  if sliced and _type != "fp":
+    raise ValueError(f"--sliced compares the flow with the fp particle reference: not defined for {_type}")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -752,6 +815,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_two_sample(evaluate_fp_two_sample(config, model, params))
   if ot_reference:
     print_ot_reference(evaluate_ot_reference(config, model, params))
+  if sliced:
+    print_fp_sliced(evaluate_fp_sliced(config, model, params))
   return res
 
 
@@ -775,10 +840,14 @@ def _parse(argv):
   p.add_argument("--ot-reference", action="store_true",
                  help="print the Sinkhorn divergence between source and target samples, the flow's coupling cost and "
                       "kinetic energy beside it, and the distance of the flow's map from the barycentric map (ot)")
+  p.add_argument("--sliced", action="store_true",
+                 help="print the sliced Wasserstein distance, in the full dimension and at the full ensemble size, between "
+                      "the flow's samples and the particle reference, and the exact W2 of every marginal (fp)")
   return p.parse_args(argv)
 
 
 if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
-       path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference)
+       path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
+       sliced=args.sliced)

@@ -555,3 +555,114 @@ def sinkhorn(x, y, eps=0.05, schedule=None, want_grad=False, want_map=False, wan
           "ot_xy": sums[:, 0] / N + sums[:, 1] / M, "change": sums[:, 4:6],
           "grad": grad if grad is None or not one else grad[0], "map": tmap if tmap is None or not one else tmap[0],
           "f": f, "g": g, "p": p, "q": q, "schedule": sched}
+
+
+# ---- the sliced Wasserstein distance: transport units between point clouds of any size, N log N per projection -------
+# Both clouds are projected on P directions; along a direction optimal transport is exact and is a sort.  No eps, no
+# iteration count, no debiasing; cost |.|^2 / 2 as `sinkhorn`, so for unit directions drawn uniformly SW <= W2^2 / (2 D),
+# and with the coordinate axes as directions sqrt(2 w) is the exact W2 of every marginal (cnf_sliced_w2).
+
+SLICED_MAX_PROJ, SLICED_MAX_POINTS, SLICED_WORKSPACE_BYTES = 1024, 1 << 20, 1 << 30
+_SLICED_WS = {}                                  # device -> the cached workspace (grown, never shrunk)
+
+
+def sliced_directions(D, P, seed=0, kind="random"):
+  """Directions for `sliced_wasserstein`, [P, D] float32 on the host.  kind="random": P unit vectors, Gaussian draws of
+  numpy's default_rng(seed) normalised in float64 -- a fixed function of (D, P, seed); for D = 1 the single direction
+  +1 (P must be 1: the other direction, -1, gives the same value).  kind="axes": the D coordinate axes (P must be D).
+  ValueError for D outside 1..14, P outside 1..1024, an unknown kind or a P the kind does not allow."""
+  D, P = int(D), int(P)
+  if not 1 <= D <= _capi.MMD_MAX_DIM or not 1 <= P <= SLICED_MAX_PROJ:
+    raise ValueError(f"sliced_directions: needs D in 1..{_capi.MMD_MAX_DIM} and P in 1..{SLICED_MAX_PROJ}, not {D}, {P}")
+  if kind == "axes":
+    if P != D:
+      raise ValueError(f"sliced_directions: the axes of dimension {D} are {D} directions, not {P}")
+    return torch.eye(D, dtype=torch.float32)
+  if kind != "random":
+    raise ValueError(f"sliced_directions: kind is 'random' or 'axes', not {kind!r}")
+  if D == 1:
+    if P != 1:
+      raise ValueError(f"sliced_directions: dimension 1 has the single direction +1, not {P}")
+    return torch.ones(1, 1, dtype=torch.float32)
+  g = np.random.default_rng(int(seed)).standard_normal((P, D))
+  return torch.from_numpy((g / np.sqrt((g * g).sum(1, keepdims=True))).astype(np.float32))
+
+
+def sliced_check_shapes(x_shape, y_shape, theta_shape=None):
+  """ValueError for what cnf_sliced_w2 refuses: ([S, N, D], [S, M, D], [P, D]) with S in 1..64, N, M in 1..2^20, D in
+  1..14, P in 1..1024."""
+  (S, N, D), (Sy, M, Dy) = x_shape, y_shape
+  if S != Sy or D != Dy:
+    raise ValueError(f"sliced: x {tuple(x_shape)} and y {tuple(y_shape)} differ in the number of sets or in the dimension")
+  if (not 1 <= S <= _capi.MMD_MAX_SETS or not 1 <= D <= _capi.MMD_MAX_DIM or min(N, M) < 1
+      or max(N, M) > SLICED_MAX_POINTS):
+    raise ValueError(f"sliced: needs 1..{_capi.MMD_MAX_SETS} sets of 1..2^20 points of dimension 1..{_capi.MMD_MAX_DIM}, "
+                     f"not x {tuple(x_shape)}, y {tuple(y_shape)}")
+  if theta_shape is not None and (len(theta_shape) != 2 or theta_shape[1] != D or not 1 <= theta_shape[0] <= SLICED_MAX_PROJ):
+    raise ValueError(f"sliced: directions must be [P, {D}] with P in 1..{SLICED_MAX_PROJ}, not {tuple(theta_shape)}")
+
+
+def _sliced_sets(t, name):
+  t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+  if t.dim() == 2:
+    t = t[None]
+  if t.dim() != 3:
+    raise ValueError(f"sliced: {name} must be [N, D] or [S, N, D], not {tuple(t.shape)}")
+  return t
+
+
+def sliced_group(S, N, M, D, P, want_grad, limit=SLICED_WORKSPACE_BYTES):
+  """(G, bytes): the largest group of projections whose workspace (cnf_sliced_workspace) is at most `limit` bytes -- 1
+  if even that is more -- and that workspace's size.  The size is linear in G, so two calls settle it."""
+  lib, C = _capi.lib(), _capi.ctypes
+
+  def size(G):
+    b = C.c_int64(0)
+    _capi.check(lib.cnf_sliced_workspace(S, N, M, D, G, int(want_grad), C.byref(b)), "cnf_sliced_workspace")
+    return b.value
+  b1 = size(1)
+  G = 1 if P == 1 or b1 >= limit else max(1, min(P, 1 + (limit - b1) // (size(2) - b1)))
+  return G, size(G)
+
+
+def sliced_wasserstein(x, y, directions=None, n_proj=64, seed=0, want_grad=False) -> dict:
+  """The sliced Wasserstein distance between the point sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D] (set s of x
+  against set s of y; uniform weights, cost |.|^2 / 2), ONE cnf_sliced_w2 call over all sets.  directions: [P, D]
+  (None: sliced_directions(D, n_proj, seed), or the single direction of D = 1); they are used as given, not
+  normalised.  float32 on the device (float64 inputs are rounded; host inputs are uploaded).  Returns a dict:
+    sw [S]               the mean over the directions of the one-dimensional transport cost (float64)
+    per_projection [S, P]  that cost per direction: the quantile-function integral, exact for any N and M
+    max_sliced [S]       its maximum over the given directions
+    directions [P, D]    the directions used, float32 on the device
+    grad                 want_grad: [S, N, D] float32 ([N, D] for 2-D x), the envelope gradient of sw in x (the sorting
+                         permutations held fixed: exact wherever the projected samples are distinct); else None
+  The projections are processed in the largest groups whose workspace stays within 1 GiB (sliced_group); the result
+  does not depend on the grouping, and two calls give the same bits.  The workspace is cached per device.  ValueError
+  before any device work for what the C ABI refuses and for x, y and directions that differ in S or D."""
+  from .applications import _OnDevice, _stream_ptr
+  x3, y3 = _sliced_sets(x, "x"), _sliced_sets(y, "y")
+  sliced_check_shapes(x3.shape, y3.shape)
+  S, N, D = x3.shape
+  M = y3.shape[1]
+  if directions is None:
+    directions = sliced_directions(D, 1 if D == 1 else n_proj, seed)
+  th = directions if torch.is_tensor(directions) else torch.as_tensor(np.asarray(directions))
+  sliced_check_shapes(x3.shape, y3.shape, tuple(th.shape))
+  P = th.shape[0]
+  dev = x3.device if x3.is_cuda else (y3.device if y3.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+  x3 = x3.detach().to(device=dev, dtype=torch.float32).contiguous()
+  y3 = y3.detach().to(device=dev, dtype=torch.float32).contiguous()
+  th = th.detach().to(device=dev, dtype=torch.float32).contiguous()
+  G, nbytes = sliced_group(S, N, M, D, P, want_grad)
+  ws = _SLICED_WS.get(dev)
+  if ws is None or ws.numel() * 8 < nbytes:
+    _SLICED_WS[dev] = None                       # (the old one is released before the new one is asked for)
+    ws = _SLICED_WS[dev] = torch.empty(-(-nbytes // 8), dtype=torch.float64, device=dev)
+  sums = torch.empty(S, P + 2, dtype=torch.float64, device=dev)
+  grad = torch.empty(S, N, D, dtype=torch.float32, device=dev) if want_grad else None
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_sliced_w2(S, x3.data_ptr(), N, y3.data_ptr(), M, D, th.data_ptr(), P, G, sums.data_ptr(),
+                                          None if grad is None else grad.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                          _stream_ptr(dev)), "cnf_sliced_w2")
+  return {"sw": sums[:, P], "per_projection": sums[:, :P], "max_sliced": sums[:, P + 1], "directions": th,
+          "grad": grad if grad is None or np.ndim(x) == 3 else grad[0]}

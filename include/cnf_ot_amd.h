@@ -830,6 +830,47 @@ int cnf_sinkhorn(int32_t S, const float *x, int64_t N, const float *y, int64_t M
                  float *xgrad, float *xmap, void *workspace, int64_t workspace_bytes,
                  void *stream);
 
+/* ---- the sliced Wasserstein distance between point clouds: transport units at N log N ------------------------------
+ * What the reference's tests/test_wasserstein_geodesic.py:165-169 leaves open for a target known only by its samples,
+ * in the units of cnf_sinkhorn (cost |.|^2 / 2) and without an eps, an iteration count or N x M pairs.  Model-free.
+ * For S independent sets, x [S, N, D] against y [S, M, D] (device, float32, uniform weights) and P directions
+ * theta [P, D] (device, float32) that the CALLER supplies: the library neither draws nor normalises them.
+ * Per set s and projection p:
+ *   keys   k_i = x[i, 0] theta[p, 0], then k_i = fmaf(x[i, d], theta[p, d], k_i) for d = 1 .. D - 1 in ascending d, in
+ *          float32, and last k_i = fmaf(k_i, 0, k_i): a finite key is unchanged by it, an infinite one becomes NaN.
+ *          l_j the same for y.
+ *   order  both key arrays ascending; TIES go by the sample's index.  (A NaN sorts by its bit pattern.)
+ *   value  w[s, p] = 1/2 sum_i sum_j o_ij (k_(i) - l_(j))^2 over the sorted keys, with
+ *          o_ij = max(0, min((i + 1) M, (j + 1) N) - max(i M, j N)) / (N M)
+ *          in 64-bit integers up to the division: the quantile-function integral of one-dimensional optimal
+ *          transport, for equal and for unequal sizes.  Differences and sums in double.
+ * cnf_sliced_w2 writes
+ *   sums [S, P + 2] (device, double, overwritten): the P values w[s, :], their mean SW[s] (summed in ascending p) and
+ *     their maximum, the max-sliced value over the given directions;
+ *   grad [S, N, D] (device, float32, or NULL): grad[s, i, :] = (1 / P) sum_p a[s, p, i] theta[p, :] + 0 SW[s], with
+ *     a = sum_j o_ij (k_i - l_j) at the rank sample i took: the ENVELOPE gradient of SW in x_i, the two permutations
+ *     held fixed (exact wherever the keys are distinct), accumulated in double in ascending p and rounded once.
+ * The cost convention is |.|^2 / 2: for unit directions drawn uniformly, SW <= W2^2 / (2 D), and with the D coordinate
+ * axes as directions sqrt(2 w[s, d]) is the exact W2 of marginal d.
+ * Non-finite input: a NaN or infinite coordinate of set s makes every key it enters NaN, hence every value of that
+ * set it reaches, and through the 0 SW[s] term every gradient row of that set; other sets are untouched.
+ * G projections are in flight at a time (the workspace grows with G).  The running gradient is carried between
+ * groups as DOUBLES in the workspace, so values and gradient are bit-identical for every G; no atomics: two calls are
+ * bit-identical, and the result does not depend on what the workspace held.
+ * cnf_sliced_workspace: the bytes of device workspace a call with this G needs (want_grad: grad != NULL); no HIP call.
+ * The workspace is the caller's: cnf_sliced_w2 neither allocates, synchronises nor reads the device (legal inside a
+ * stream capture).  cnf_sliced_tile: the keys per sorted tile (a build constant; clouds above it take merge passes).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL x, y, theta, sums or workspace; S outside 1..64; D
+ * outside 1..14; N or M outside 1..2^20; P outside 1..1024; G outside 1..P (cnf_sliced_workspace: 1..1024); a workspace
+ * smaller than cnf_sliced_workspace says.
+ * Out of scope: weights, more than one rank, N > 2^20, costs other than |.|^2 / 2, drawing directions on the device. */
+int cnf_sliced_workspace(int32_t S, int64_t N, int64_t M, int32_t D, int32_t G, int32_t want_grad,
+                         int64_t *bytes);
+int cnf_sliced_tile(void);
+int cnf_sliced_w2(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int32_t D,
+                  const float *theta, int32_t P, int32_t G, double *sums, float *grad,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
