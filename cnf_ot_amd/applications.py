@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, two_sample
 from .distributed import Shard, all_reduce_sums, current_shard, shard_range
 from .flows import DeviceRng, FlowEngine, _OnDevice, _stream_ptr, seed_to_u64
 
@@ -1104,7 +1104,41 @@ def importance_stats(model, params, target, conds, rng, batch_size, scale=None, 
   return importance_summary(raw)
 
 
-# ---- a sample-only fitting term: MMD^2 / energy distance between the flow's samples and given target samples --------
+# ---- sample-only fitting terms: a distance between the flow's samples and given target samples ----------------------
+
+def _sample_term(name, why, model, params, target, cond, rng, batch_size, shard, grad, refuse, stat):
+  """The mean over the times of `cond` of a point-set statistic (two_sample) between batch_size flow samples per time
+  -- the same base draw of `rng` for every time -- and `target`, [M, D] or one set per time; with `grad` its parameter
+  gradient, by ONE cnf_pass_vjp call seeded with the statistic's gradient in the samples / S.  The term supplies
+  refuse(S, target shape [S, M, D]): its own ValueErrors, returning what its checks resolved; and
+  stat(samples [S, B, D], target [S, M, D], what refuse returned, want_grad) -> (values [S], gradient [S, B, D] or
+  None).  Every refusal, the term's included, comes before the backend is touched.  `why`: the subject of the
+  single-rank refusal."""
+  shard = shard if shard is not None else current_shard()
+  if shard.world > 1:
+    raise ValueError(f"{name}: single rank only ({why} an all-gather of the samples)")
+  conds = _conds(cond)
+  S = _n_conds(conds)
+  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+  if tgt.dim() == 2:
+    tgt = tgt[None].expand(S, -1, -1)
+  if tgt.dim() != 3 or tgt.shape[0] != S:
+    raise ValueError(f"{name}: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
+  checked = refuse(S, tgt.shape)
+  ctx = _Ctx(model, params, rng, shard, grad)
+  be = ctx.be
+  z, _, count = ctx.noise(batch_size)
+  zs = z.repeat(S, 1)                                         # the same draw for every time
+  c = be.slice_conds(conds)
+  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
+  values, xgrad = stat(samples.view(S, count, -1), tgt.to(device=samples.device, dtype=torch.float32), checked,
+                       grad is not None)
+  if grad is not None:
+    be.pass_vjp(zs, c, (xgrad * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
+  return values.sum() / S
+
+
+# ---- MMD^2 / energy distance ------------------------------------------------------------------------------------------
 
 def mmd_loss_fn(model, dim, params, target, cond, rng, batch_size, bandwidths=None, kind="gaussian", shard=None,
                 grad=None):
@@ -1115,35 +1149,19 @@ def mmd_loss_fn(model, dim, params, target, cond, rng, batch_size, bandwidths=No
   other term functions; `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_mmd2 call
   (value and d / d samples) and ONE cnf_pass_vjp call.  Single rank: the pairs across ranks would need an all-gather of
   the samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
-  from . import utils
-  shard = shard if shard is not None else current_shard()
-  if shard.world > 1:
-    raise ValueError("mmd_loss_fn: single rank only (pairs across ranks need an all-gather of the samples)")
-  conds = _conds(cond)
-  S = _n_conds(conds)
-  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-  if tgt.dim() == 2:
-    tgt = tgt[None].expand(S, -1, -1)
-  if tgt.dim() != 3 or tgt.shape[0] != S:
-    raise ValueError(f"mmd_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
-  utils.mmd_check_shapes((S, int(batch_size), int(dim)), tgt.shape)
-  if kind == "gaussian" and bandwidths is not None:
-    utils.mmd_spec(bandwidths, kind)
-  elif kind not in _capi.MMD_KINDS:
-    raise ValueError(f"mmd_loss_fn: kind is 'gaussian' or 'energy', not {kind!r}")
-  ctx = _Ctx(model, params, rng, shard, grad)
-  be = ctx.be
-  z, _, count = ctx.noise(batch_size)
-  zs = z.repeat(S, 1)                                         # the same draw for every time
-  c = be.slice_conds(conds)
-  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
-  tgt = tgt.to(device=samples.device, dtype=torch.float32)
-  if kind == "gaussian" and bandwidths is None:
-    bandwidths = utils.median_bandwidths(tgt)
-  res = utils.mmd2(samples.view(S, count, -1), tgt, bandwidths, kind, want_grad=grad is not None)
-  if grad is not None:
-    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
-  return res["mmd2"].sum() / S
+  def refuse(S, tgt_shape):
+    two_sample.mmd_check_shapes((S, int(batch_size), int(dim)), tgt_shape)
+    if kind == "gaussian" and bandwidths is not None:
+      two_sample.mmd_spec(bandwidths, kind)
+    elif kind not in _capi.MMD_KINDS:
+      raise ValueError(f"mmd_loss_fn: kind is 'gaussian' or 'energy', not {kind!r}")
+
+  def stat(samples, tgt, checked, want_grad):      # (the median bandwidths: of the target where the samples are)
+    bws = two_sample.median_bandwidths(tgt) if kind == "gaussian" and bandwidths is None else bandwidths
+    res = two_sample.mmd2(samples, tgt, bws, kind, want_grad=want_grad)
+    return res["mmd2"], res.get("grad")
+  return _sample_term("mmd_loss_fn", "pairs across ranks need", model, params, target, cond, rng, batch_size, shard, grad,
+                      refuse, stat)
 
 
 # ---- the same in transport units: the Sinkhorn divergence between the flow's samples and given target samples --------
@@ -1157,33 +1175,18 @@ def sinkhorn_loss_fn(model, dim, params, target, cond, rng, batch_size, eps=0.05
   `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_sinkhorn call (value and the envelope
   gradient d / d samples) and ONE cnf_pass_vjp call.  Single rank: the pairs across ranks would need an all-gather of the
   samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
-  from . import utils
-  shard = shard if shard is not None else current_shard()
-  if shard.world > 1:
-    raise ValueError("sinkhorn_loss_fn: single rank only (pairs across ranks need an all-gather of the samples)")
-  conds = _conds(cond)
-  S = _n_conds(conds)
-  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-  if tgt.dim() == 2:
-    tgt = tgt[None].expand(S, -1, -1)
-  if tgt.dim() != 3 or tgt.shape[0] != S:
-    raise ValueError(f"sinkhorn_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
-  utils.sinkhorn_check_shapes((S, int(batch_size), int(dim)), tgt.shape)
-  if schedule is not None:
-    schedule = utils.sinkhorn_check_schedule(schedule)
-  elif not (float(eps) > 0.0 and np.isfinite(float(eps))):
-    raise ValueError(f"sinkhorn_loss_fn: eps must be positive and finite, not {eps}")
-  ctx = _Ctx(model, params, rng, shard, grad)
-  be = ctx.be
-  z, _, count = ctx.noise(batch_size)
-  zs = z.repeat(S, 1)                                         # the same draw for every time
-  c = be.slice_conds(conds)
-  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
-  tgt = tgt.to(device=samples.device, dtype=torch.float32)
-  res = utils.sinkhorn(samples.view(S, count, -1), tgt, eps, schedule, want_grad=grad is not None)
-  if grad is not None:
-    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
-  return res["divergence"].sum() / S
+  def refuse(S, tgt_shape):      # -> the checked schedule, or None
+    two_sample.sinkhorn_check_shapes((S, int(batch_size), int(dim)), tgt_shape)
+    if schedule is not None:
+      return two_sample.sinkhorn_check_schedule(schedule)
+    if not (float(eps) > 0.0 and np.isfinite(float(eps))):
+      raise ValueError(f"sinkhorn_loss_fn: eps must be positive and finite, not {eps}")
+
+  def stat(samples, tgt, sched, want_grad):
+    res = two_sample.sinkhorn(samples, tgt, eps, sched, want_grad=want_grad)
+    return res["divergence"], res["grad"]
+  return _sample_term("sinkhorn_loss_fn", "pairs across ranks need", model, params, target, cond, rng, batch_size, shard,
+                      grad, refuse, stat)
 
 
 # ---- the same at any batch size: the sliced Wasserstein distance between the flow's samples and target samples ------
@@ -1198,32 +1201,17 @@ def sliced_loss_fn(model, dim, params, target, cond, rng, batch_size, directions
   `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_sliced_w2 call (value and the
   envelope gradient d / d samples) and ONE cnf_pass_vjp call.  Single rank: the sort would need an all-gather of the
   samples, so a shard (or a torch.distributed world) of more than one rank raises ValueError."""
-  from . import utils
-  shard = shard if shard is not None else current_shard()
-  if shard.world > 1:
-    raise ValueError("sliced_loss_fn: single rank only (the sort across ranks needs an all-gather of the samples)")
-  conds = _conds(cond)
-  S = _n_conds(conds)
-  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-  if tgt.dim() == 2:
-    tgt = tgt[None].expand(S, -1, -1)
-  if tgt.dim() != 3 or tgt.shape[0] != S:
-    raise ValueError(f"sliced_loss_fn: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
-  if directions is None:
-    directions = utils.sliced_directions(int(dim), 1 if int(dim) == 1 else n_proj, seed)
-  th = directions if torch.is_tensor(directions) else torch.as_tensor(np.asarray(directions))
-  utils.sliced_check_shapes((S, int(batch_size), int(dim)), tgt.shape, tuple(th.shape))
-  ctx = _Ctx(model, params, rng, shard, grad)
-  be = ctx.be
-  z, _, count = ctx.noise(batch_size)
-  zs = z.repeat(S, 1)                                         # the same draw for every time
-  c = be.slice_conds(conds)
-  samples, _ = be.forward_logdet(zs, c, want_logdet=False)
-  tgt = tgt.to(device=samples.device, dtype=torch.float32)
-  res = utils.sliced_wasserstein(samples.view(S, count, -1), tgt, th, want_grad=grad is not None)
-  if grad is not None:
-    be.pass_vjp(zs, c, (res["grad"] * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
-  return res["sw"].sum() / S
+  def refuse(S, tgt_shape):      # -> the directions as a tensor
+    th = two_sample.sliced_directions(int(dim), 1 if int(dim) == 1 else n_proj, seed) if directions is None else directions
+    th = th if torch.is_tensor(th) else torch.as_tensor(np.asarray(th))
+    two_sample.sliced_check_shapes((S, int(batch_size), int(dim)), tgt_shape, tuple(th.shape))
+    return th
+
+  def stat(samples, tgt, th, want_grad):
+    res = two_sample.sliced_wasserstein(samples, tgt, th, want_grad=want_grad)
+    return res["sw"], res["grad"]
+  return _sample_term("sliced_loss_fn", "the sort across ranks needs", model, params, target, cond, rng, batch_size, shard,
+                      grad, refuse, stat)
 
 
 # ---- composite losses ---------------------------------------------------------

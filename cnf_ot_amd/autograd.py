@@ -15,7 +15,7 @@ the parameters only; its time derivatives are finite differences).
 """
 import torch
 
-from . import _capi
+from . import _capi, two_sample
 from .flows import FlowEngine, _stream_ptr
 
 
@@ -92,18 +92,20 @@ def _cond_tensor(engine, c):
   return c.to(device=engine.device, dtype=torch.float32).reshape(-1)
 
 
-class _Mmd2(torch.autograd.Function):
-  """utils.mmd2 with its gradient: in x from the same cnf_mmd2 call (xgrad), in y from a second call with the roles
-  swapped (MMD^2 is symmetric)."""
+
+class _PointSetStat(torch.autograd.Function):
+  """A symmetric statistic of two point sets whose call returns the value and its gradient in x (two_sample.mmd2,
+  sinkhorn, sliced_wasserstein): the gradient in x from the forward call, in y from a second call with the roles
+  swapped.  stat(x, y, want_grad, first) returns the statistic's dict; `first` is None in the forward call and the
+  forward call's dict in the swapped one.  key: the value's entry."""
 
   @staticmethod
-  def forward(ctx, x, y, bandwidths, kind):
-    from .utils import mmd2 as _mmd2
+  def forward(ctx, x, y, stat, key):
     need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    res = _mmd2(x.detach(), y.detach(), bandwidths, kind, want_grad=need_x)
-    gy = _mmd2(y.detach(), x.detach(), bandwidths, kind, want_grad=True)["grad"] if need_y else None
+    res = stat(x.detach(), y.detach(), need_x, None)
+    gy = stat(y.detach(), x.detach(), True, res)["grad"] if need_y else None
     ctx.save_for_backward(res.get("grad"), gy)
-    return res["mmd2"]
+    return res[key]
 
   @staticmethod
   def backward(ctx, gbar):
@@ -118,28 +120,8 @@ def mmd2(x: torch.Tensor, y: torch.Tensor, bandwidths, kind: str = "gaussian"):
   sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D], [S] float64 ([1] for 2-D inputs), differentiable in x and y:
   with `flow_forward` a flow trains on samples through ordinary autograd (applications.mmd_loss_fn is the hand-written
   fast path).  The bandwidths are constants (utils.median_bandwidths(y) gives the usual choice)."""
-  return _Mmd2.apply(x, y, bandwidths, kind)
-
-
-class _Sinkhorn(torch.autograd.Function):
-  """utils.sinkhorn with its envelope gradient: in x from the same cnf_sinkhorn call (xgrad), in y from a second call
-  with the roles swapped (the divergence is symmetric)."""
-
-  @staticmethod
-  def forward(ctx, x, y, eps, schedule):
-    from .utils import sinkhorn as _sinkhorn
-    need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    res = _sinkhorn(x.detach(), y.detach(), eps, schedule, want_grad=need_x)
-    gy = _sinkhorn(y.detach(), x.detach(), eps, res["schedule"], want_grad=True)["grad"] if need_y else None
-    ctx.save_for_backward(res["grad"], gy)
-    return res["divergence"]
-
-  @staticmethod
-  def backward(ctx, gbar):
-    gx, gy = ctx.saved_tensors
-    w = gbar.to(torch.float32)
-    scale = lambda g: None if g is None else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
-    return scale(gx), scale(gy), None, None
+  return _PointSetStat.apply(x, y, lambda a, b, want_grad, first: two_sample.mmd2(a, b, bandwidths, kind, want_grad),
+                             "mmd2")
 
 
 def sinkhorn_divergence(x: torch.Tensor, y: torch.Tensor, eps: float = 0.05, schedule=None):
@@ -149,28 +131,10 @@ def sinkhorn_divergence(x: torch.Tensor, y: torch.Tensor, eps: float = 0.05, sch
   recursion (utils.sinkhorn's `change` says how far the schedule stopped from it).  The schedule is a constant
   (None: utils.sinkhorn_schedule(x, y, eps)).  With `flow_forward` a flow trains on target samples in transport units
   through ordinary autograd (applications.sinkhorn_loss_fn is the hand-written fast path)."""
-  return _Sinkhorn.apply(x, y, eps, schedule)
-
-
-class _Sliced(torch.autograd.Function):
-  """utils.sliced_wasserstein with its envelope gradient: in x from the same cnf_sliced_w2 call, in y from a second call
-  with the roles swapped (the distance is symmetric)."""
-
-  @staticmethod
-  def forward(ctx, x, y, directions):
-    from .utils import sliced_wasserstein as _sw
-    need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    res = _sw(x.detach(), y.detach(), directions, want_grad=need_x)
-    gy = _sw(y.detach(), x.detach(), directions, want_grad=True)["grad"] if need_y else None
-    ctx.save_for_backward(res["grad"], gy)
-    return res["sw"]
-
-  @staticmethod
-  def backward(ctx, gbar):
-    gx, gy = ctx.saved_tensors
-    w = gbar.to(torch.float32)
-    scale = lambda g: None if g is None else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
-    return scale(gx), scale(gy), None
+  # (the swapped call runs on the schedule the forward call resolved)
+  stat = lambda a, b, want_grad, first: two_sample.sinkhorn(a, b, eps, schedule if first is None else first["schedule"],
+                                                            want_grad=want_grad)
+  return _PointSetStat.apply(x, y, stat, "divergence")
 
 
 def sliced_wasserstein(x: torch.Tensor, y: torch.Tensor, directions):
@@ -179,4 +143,5 @@ def sliced_wasserstein(x: torch.Tensor, y: torch.Tensor, directions):
   float64 ([1] for 2-D inputs), differentiable in x (and in y, by a second call): backward is the gradient cnf_sliced_w2
   stored times the incoming scalar.  With `flow_forward` a flow trains on target samples through ordinary autograd
   (applications.sliced_loss_fn is the hand-written fast path)."""
-  return _Sliced.apply(x, y, directions)
+  stat = lambda a, b, want_grad, first: two_sample.sliced_wasserstein(a, b, directions, want_grad=want_grad)
+  return _PointSetStat.apply(x, y, stat, "sw")

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _capi, applications, utils
+from .distributed import Shard
 from .flows import DeviceRng, RQSFlow, FlowModel, _OnDevice, _stream_ptr, mark_updated
 from .params import Params
 
@@ -362,6 +363,39 @@ def print_path_errors(res: Dict[str, Any]) -> None:
           + (" | {:.3e}".format(res["score_rel_err"][i]) if score else ""))
 
 
+def _fp_prelude(name, config, times, n_particles, h, min_particles, start="gaussian"):
+  """What the fp evaluators refuse, in `name`'s words, before any device work -- another problem type, (evaluate_fp_path:
+  an unknown `start`,) a configuration without figure settings, an n_particles that is odd or below min_particles,
+  times that are no multiples of h -- and what they go on with: (figure settings, times, n_particles, (dim, T, a,
+  sigma, drift type))."""
+  g = config["general"]
+  if g["type"] != "fp":
+    raise ValueError(f"{name}: defined for fp only, not {g['type']}")
+  if start not in ("gaussian", "flow"):
+    raise ValueError(f"{name}: start is 'gaussian' or 'flow', not {start!r}")
+  st = figure_settings(config)
+  if st is None:
+    raise ValueError(f"{name}: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
+  n_particles = int(n_particles)
+  if n_particles < min_particles or n_particles % 2:
+    raise ValueError(f"{name}: n_particles must be even and >= {min_particles} (two halves are compared), not {n_particles}")
+  f = config["fp"]
+  # (the figure's own times need not be multiples of h -- linspace(0, 1, 10) at dim 3: the default snaps them to it)
+  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
+  applications.fp_step_indices(ts, float(h), f["T"])
+  return st, ts, n_particles, (g["dim"], f["T"], f["a"], f["sigma"], f["velocity_field_type"])
+
+
+def _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed):
+  """(flow, half 0, half 1), [S, n_particles / 2, D] each: the flow's samples of `seed` at the times ts, stacked, and
+  the positions of the two halves of the Euler-Maruyama ensemble (fp: the problem, as _fp_prelude returns it)."""
+  dim, T, a, sigma, sub = fp
+  flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n_particles // 2,)) for t in ts])
+  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
+                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  return flow, h0, h1
+
+
 def evaluate_fp_path(config, model: FlowModel, params: Params, times=None, n_particles=1 << 20, h=1e-3, seed=0,
                      start="gaussian") -> Dict[str, Any]:
   """Where along [0, T] the flow of an fp configuration departs from the Fokker-Planck solution, for every drift and
@@ -381,23 +415,7 @@ def evaluate_fp_path(config, model: FlowModel, params: Params, times=None, n_par
     bad             particles that were not finite
   start="flow": the ensemble starts from the flow's own samples at t = 0 instead of N(0, (T + 1) / 2 I), which takes
   the initial-condition fit out of the path error.  Single process (the ensemble is run as its two halves)."""
-  g = config["general"]
-  if g["type"] != "fp":
-    raise ValueError(f"evaluate_fp_path: defined for fp only, not {g['type']}")
-  if start not in ("gaussian", "flow"):
-    raise ValueError(f"evaluate_fp_path: start is 'gaussian' or 'flow', not {start!r}")
-  st = figure_settings(config)
-  if st is None:
-    raise ValueError(f"evaluate_fp_path: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
-  n_particles = int(n_particles)
-  if n_particles < 2 or n_particles % 2:
-    raise ValueError(f"evaluate_fp_path: n_particles must be even (the noise floor compares two halves), not {n_particles}")
-  from .distributed import Shard
-  f, dim = config["fp"], g["dim"]
-  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
-  # (the figure's own times need not be multiples of h -- linspace(0, 1, 10) at dim 3: the default snaps them to it)
-  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
-  applications.fp_step_indices(ts, float(h), T)
+  st, ts, n_particles, (dim, T, a, sigma, sub) = _fp_prelude("evaluate_fp_path", config, times, n_particles, h, 2, start)
   S = len(ts)
   grid = utils.field_grid(st["domain_range"], FIGURE_GRID, axes=(0, 1))
   samples = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n_particles,)) for t in ts])
@@ -446,26 +464,10 @@ def evaluate_fp_two_sample(config, model: FlowModel, params: Params, times=None,
     energy, energy_floor  the same for the energy distance 2 E|x - y| - E|x - x'| - E|y - y'|
     bandwidths            the bandwidths used
   Two cnf_mmd2 calls per kind over all times (utils.mmd2).  Single process."""
-  g = config["general"]
-  if g["type"] != "fp":
-    raise ValueError(f"evaluate_fp_two_sample: defined for fp only, not {g['type']}")
-  st = figure_settings(config)
-  if st is None:
-    raise ValueError(f"evaluate_fp_two_sample: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
-  n_particles = int(n_particles)
-  if n_particles < 4 or n_particles % 2:
-    raise ValueError(f"evaluate_fp_two_sample: n_particles must be even and >= 4 (two halves are compared), not {n_particles}")
+  _, ts, n_particles, fp = _fp_prelude("evaluate_fp_two_sample", config, times, n_particles, h, 4)
   if bandwidths is not None:
     utils.mmd_spec(bandwidths, "gaussian")
-  from .distributed import Shard
-  f, dim = config["fp"], g["dim"]
-  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
-  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
-  applications.fp_step_indices(ts, float(h), T)
-  n = n_particles // 2
-  flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n,)) for t in ts])
-  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
-                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  flow, h0, h1 = _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed)
   bws = utils.median_bandwidths(h0) if bandwidths is None else bandwidths
   out: Dict[str, Any] = {"times": [float(t) for t in ts]}
   for kind, key in (("gaussian", "mmd2"), ("energy", "energy")):
@@ -507,27 +509,12 @@ def evaluate_fp_sliced(config, model: FlowModel, params: Params, times=None, n_p
     n, n_proj                     the points per set and the directions used
   All times, flow and floor, go into ONE cnf_sliced_w2 call per direction set (2 x len(times) <= 64 sets).  Single
   process."""
-  g = config["general"]
-  if g["type"] != "fp":
-    raise ValueError(f"evaluate_fp_sliced: defined for fp only, not {g['type']}")
-  st = figure_settings(config)
-  if st is None:
-    raise ValueError(f"evaluate_fp_sliced: no figure settings for fp / {config['fp']['velocity_field_type']} at dim {g['dim']}")
-  n_particles = int(n_particles)
-  if n_particles < 2 or n_particles % 2:
-    raise ValueError(f"evaluate_fp_sliced: n_particles must be even and >= 2 (two halves are compared), not {n_particles}")
-  from .distributed import Shard
-  f, dim = config["fp"], g["dim"]
-  T, a, sigma, sub = f["T"], f["a"], f["sigma"], f["velocity_field_type"]
-  ts = np.rint(st["t_array"] / float(h)) * float(h) if times is None else utils._times_of(times)
-  applications.fp_step_indices(ts, float(h), T)
-  n, S = n_particles // 2, len(ts)
+  _, ts, n_particles, fp = _fp_prelude("evaluate_fp_sliced", config, times, n_particles, h, 2)
+  n, S, dim = n_particles // 2, len(ts), fp[0]
   utils.sliced_check_shapes((2 * S, n, dim), (2 * S, n, dim))
   theta = utils.sliced_directions(dim, 1 if dim == 1 else n_proj, seed)
   axes = utils.sliced_directions(dim, dim, kind="axes")
-  flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n,)) for t in ts])
-  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
-                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  flow, h0, h1 = _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed)
   x, y = torch.cat([flow.float(), h1]), torch.cat([h0, h0])
   rnd = utils.sliced_wasserstein(x, y, theta)
   marg = (2.0 * utils.sliced_wasserstein(x, y, axes)["per_projection"]).sqrt()
@@ -582,7 +569,6 @@ def evaluate_ot_reference(config, model: FlowModel, params: Params, n=8192, eps=
   utils.sinkhorn_check_shapes((5, n, dim), (5, n, dim))
   if not (eps > 0.0 and np.isfinite(eps)):
     raise ValueError(f"evaluate_ot_reference: eps must be positive and finite, not {eps}")
-  from .distributed import Shard
   T = 1.0
   ctx = applications._Ctx(model, params, seed + 1, Shard(0, 1))
   be = ctx.be

@@ -262,60 +262,20 @@ def test_symmetry_and_the_python_surface(dev, kind, n_bw):
 @pytest.mark.parametrize("D", [2, 3])
 @pytest.mark.parametrize("kind", ["gaussian", "energy"])
 def test_training_term_against_the_float64_adjoint(dev, D, kind):
-  import flow_adjoint_f64 as fa
-  from cnf_ot_amd import FlowConfig, FlowModel, Params, applications as app, autograd
-  B, M, rng_seed = 96, 130, 77
-  cfg = FlowConfig(dim=D)
-  params = Params.random(cfg, 0.2, seed=3 + D, device=dev)
-  model = FlowModel(cfg)
+  import sample_term_check
+  from cnf_ot_amd import applications as app, autograd
+  B, M = 96, 130
   _, tgt = _inputs(D, 2, M, 46 + D)
-  conds = np.array([0.3, 0.8], dtype=np.float32)
-  S = len(conds)
   sp = _spec(kind, D, 3)
   bws = sp["bw"] if kind == "gaussian" else None
-  g = torch.zeros_like(params.flat)
-  loss = app.mmd_loss_fn(model, D, params, tgt, conds, rng_seed, B, bandwidths=bws, kind=kind, grad=g)
-  plain = app.mmd_loss_fn(model, D, params, tgt, conds, rng_seed, B, bandwidths=bws, kind=kind)
-  v, gt = app.value_and_grad(lambda p, *a, **kw: app.mmd_loss_fn(model, D, p, *a, **kw))(params, tgt, conds, rng_seed, B,
-                                                                                         bandwidths=bws, kind=kind)
-  torch.cuda.synchronize()
-  assert float(plain) == float(loss) == float(v) and torch.equal(gt.flat, g)
-  # the float64 reference: the analytic adjoint of the flow pass, seeded with the restatement's gradient
-  be = model.terms_backend(params)
-  z = be.normal(rng_seed, B).cpu().numpy()
-  zs, cs = np.tile(z, (S, 1)), np.repeat(conds, B)
-  flat = params.flat.cpu().numpy()
-
-  def ref(dt):
-    out = fa.pass_vjp(cfg, flat, zs, cs, None, None, False, dt)[0]
-    out = np.asarray(out, dtype=np.float64).reshape(S, B, D)
-    val = np.mean([mr.mmd2(out[s], tgt, sp) for s in range(S)])
-    ybar = np.concatenate([mr.xgrad(out[s], tgt, sp) for s in range(S)]) / S
-    return val, fa.pass_vjp(cfg, flat, zs, cs, ybar.astype(dt), None, False, dt)[3], out
-  v64, g64, out64 = ref(np.float64)
-  v32, g32, _ = ref(np.float32)
-  kmax = max(mr.k_max(out64[s], tgt, sp) for s in range(S))
-  e_v, e_g = abs(float(loss) - v64), float(np.abs(g.cpu().double().numpy() - g64).max())
-  bound = fa.bound(g32, g64)
-  print(f"\n[mmd_loss_fn D={D} {kind}] loss {v64:.6f}: error {e_v:.2e} (float32 restatement {abs(v32 - v64):.2e}, floor "
-        f"{4 * EPS * kmax:.2e}) | gradient |.| {np.abs(g64).max():.3e}: error {e_g:.2e}, bound {bound:.2e}")
-  assert e_v <= 2.0 * abs(v32 - v64) + 4.0 * EPS * kmax
-  assert e_g <= bound
-  # the same term through ordinary autograd: flow_forward + autograd.mmd2
-  flat_t = params.flat.clone().requires_grad_(True)
-  zt = torch.from_numpy(zs).to(dev)
-  samples, _ = autograd.flow_forward(be, flat_t, zt, torch.from_numpy(conds).to(dev))
-  val = autograd.mmd2(samples.view(S, B, D), torch.from_numpy(tgt).to(dev)[None].expand(S, -1, -1), bws, kind)
-  assert val.shape == (S,) and val.dtype == torch.float64
-  (val.sum() / S).backward()
-  e_auto = float((flat_t.grad - g).abs().max())
-  print(f"[mmd_loss_fn D={D} {kind}] autograd against the fast path: {e_auto:.2e}, values equal: {float(val.detach().sum() / S) == float(loss)}")
-  assert float(val.detach().sum() / S) == float(loss)
-  # float32 rounding of the final accumulation: two orders of a sum of S B per-sample terms differ by at most S B 2^-24
-  assert e_auto <= S * B * 2.0 ** -24 * float(g.abs().max())
+  samples = sample_term_check.check(
+      dev, f"mmd_loss_fn D={D} {kind}", D, B, tgt, app.mmd_loss_fn, dict(bandwidths=bws, kind=kind),
+      auto=lambda x, y: autograd.mmd2(x, y, bws, kind),
+      restate=lambda out: (mr.mmd2(out, tgt, sp), mr.xgrad(out, tgt, sp), None),
+      floor=lambda out64, runs: 4.0 * EPS * max(mr.k_max(o, tgt, sp) for o in out64))
   # ... and differentiable in y, by the call with the roles swapped
   yt = torch.from_numpy(tgt).to(dev).requires_grad_(True)
-  xs = samples.detach()[:B]
+  xs = samples[:B]
   autograd.mmd2(xs, yt, bws, kind).sum().backward()
   e_y = float(np.abs(yt.grad.cpu().double().numpy() - mr.xgrad(tgt, xs.cpu().numpy(), sp)).max()) * M
   assert e_y <= 4.0 * EPS * mr.tau(sp) + 2e-6 * float(np.abs(mr.xgrad(tgt, xs.cpu().numpy(), sp)).max()) * M

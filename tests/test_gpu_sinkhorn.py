@@ -289,59 +289,18 @@ def test_a_captured_call_replays_the_eager_bits(dev):
 
 @pytest.mark.parametrize("D", [2, 3])
 def test_training_term_against_the_float64_adjoint(dev, D):
-  import flow_adjoint_f64 as fa
-  from cnf_ot_amd import FlowConfig, FlowModel, Params, applications as app, autograd
-  B, M, rng_seed = 256, 130, 77
-  cfg = FlowConfig(dim=D)
-  params = Params.random(cfg, 0.2, seed=3 + D, device=dev)
-  model = FlowModel(cfg)
+  import sample_term_check
+  from cnf_ot_amd import applications as app, autograd
+  B, M = 256, 130
   _, tgt = _inputs(D, 2, M, 46 + D)
-  conds = np.array([0.3, 0.8], dtype=np.float32)
-  S = len(conds)
   sched = [16.0, 8.0, 4.0, 2.0, 1.0, 0.5, 0.25, 0.25, 0.25, 0.25]
-  g = torch.zeros_like(params.flat)
-  loss = app.sinkhorn_loss_fn(model, D, params, tgt, conds, rng_seed, B, schedule=sched, grad=g)
-  plain = app.sinkhorn_loss_fn(model, D, params, tgt, conds, rng_seed, B, schedule=sched)
-  v, gt = app.value_and_grad(lambda p, *a, **kw: app.sinkhorn_loss_fn(model, D, p, *a, **kw))(params, tgt, conds, rng_seed, B,
-                                                                                              schedule=sched)
-  torch.cuda.synchronize()
-  assert float(plain) == float(loss) == float(v) and torch.equal(gt.flat, g)
-  # the float64 reference: the analytic adjoint of the flow pass, seeded with the restatement's envelope gradient
-  be = model.terms_backend(params)
-  z = be.normal(rng_seed, B).cpu().numpy()
-  zs, cs = np.tile(z, (S, 1)), np.repeat(conds, B)
-  flat = params.flat.cpu().numpy()
 
-  def ref(dt):
-    out = fa.pass_vjp(cfg, flat, zs, cs, None, None, False, dt)[0]
-    out = np.asarray(out, dtype=np.float64).reshape(S, B, D)
-    runs = [sr.run(out[s], tgt, sched) for s in range(S)]
-    val = np.mean([r["divergence"] for r in runs])
-    ybar = np.concatenate([r["xgrad"] for r in runs]) / S
-    return val, fa.pass_vjp(cfg, flat, zs, cs, ybar.astype(dt), None, False, dt)[3], runs
-  v64, g64, runs = ref(np.float64)
-  v32, g32, _ = ref(np.float32)
-  floor = ULP8 * max(r["c_max"] + r["h_max"] for r in runs)
-  e_v, e_g = abs(float(loss) - v64), float(np.abs(g.cpu().double().numpy() - g64).max())
-  bound = fa.bound(g32, g64)
-  print(f"\n[sinkhorn_loss_fn D={D}] loss {v64:.6f}: error {e_v:.2e} (float32 restatement {abs(v32 - v64):.2e}, floor "
-        f"{floor:.2e}) | gradient |.| {np.abs(g64).max():.3e}: error {e_g:.2e}, bound {bound:.2e}")
-  assert e_v <= 2.0 * abs(v32 - v64) + floor
-  assert e_g <= bound
-  # the same term through ordinary autograd: flow_forward + autograd.sinkhorn_divergence
-  flat_t = params.flat.clone().requires_grad_(True)
-  zt = torch.from_numpy(zs).to(dev)
-  samples, _ = autograd.flow_forward(be, flat_t, zt, torch.from_numpy(conds).to(dev))
-  val = autograd.sinkhorn_divergence(samples.view(S, B, D), torch.from_numpy(tgt).to(dev)[None].expand(S, -1, -1),
-                                     schedule=sched)
-  assert val.shape == (S,) and val.dtype == torch.float64
-  (val.sum() / S).backward()
-  e_auto = float((flat_t.grad - g).abs().max())
-  print(f"[sinkhorn_loss_fn D={D}] autograd against the fast path: {e_auto:.2e}, values equal: "
-        f"{float(val.detach().sum() / S) == float(loss)}")
-  assert float(val.detach().sum() / S) == float(loss)
-  # float32 rounding of the final accumulation: two orders of a sum of S B per-sample terms differ by at most S B 2^-24
-  assert e_auto <= S * B * 2.0 ** -24 * float(g.abs().max())
+  def restate(out):      # (the envelope gradient)
+    r = sr.run(out, tgt, sched)
+    return r["divergence"], r["xgrad"], r
+  sample_term_check.check(dev, f"sinkhorn_loss_fn D={D}", D, B, tgt, app.sinkhorn_loss_fn, dict(schedule=sched),
+                          auto=lambda x, y: autograd.sinkhorn_divergence(x, y, schedule=sched), restate=restate,
+                          floor=lambda out64, runs: ULP8 * max(r["c_max"] + r["h_max"] for r in runs))
 
 
 @pytest.mark.parametrize("source", ["mixture", "gaussian"])

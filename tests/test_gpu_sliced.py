@@ -321,60 +321,27 @@ def test_a_captured_call_replays_the_eager_bits(dev):
 
 @pytest.mark.parametrize("D", [2, 3])
 def test_training_term_against_the_float64_adjoint(dev, D):
-  import flow_adjoint_f64 as fa
-  from cnf_ot_amd import FlowConfig, FlowModel, Params, applications as app, autograd, utils
-  B, M, P, rng_seed = 512, 384, 4, 77
-  cfg = FlowConfig(dim=D)
-  params = Params.random(cfg, 0.2, seed=3 + D, device=dev)
-  model = FlowModel(cfg)
+  import sample_term_check
+  from cnf_ot_amd import applications as app, autograd, utils
+  B, M, P = 512, 384, 4
   _, tgt = sl.clouds(D, 2, M, seed=800 + D)
   theta = utils.sliced_directions(D, P, seed=8)
-  conds = np.array([0.3, 0.8], dtype=np.float32)
-  S = len(conds)
-  g = torch.zeros_like(params.flat)
-  loss = app.sliced_loss_fn(model, D, params, tgt, conds, rng_seed, B, directions=theta, grad=g)
-  plain = app.sliced_loss_fn(model, D, params, tgt, conds, rng_seed, B, directions=theta)
-  v, gt = app.value_and_grad(lambda p, *a, **kw: app.sliced_loss_fn(model, D, p, *a, **kw))(params, tgt, conds, rng_seed, B,
-                                                                                            directions=theta)
-  torch.cuda.synchronize()
-  assert float(plain) == float(loss) == float(v) and torch.equal(gt.flat, g)
-  # the float64 reference: the analytic adjoint of the flow pass, seeded with the restatement's envelope gradient
-  be = model.terms_backend(params)
-  z = be.normal(rng_seed, B).cpu().numpy()
-  zs, cs = np.tile(z, (S, 1)), np.repeat(conds, B)
-  flat = params.flat.cpu().numpy()
 
-  def ref(dt):
-    out = fa.pass_vjp(cfg, flat, zs, cs, None, None, False, dt)[0]
-    out = np.asarray(out, dtype=np.float64).reshape(S, B, D)
-    runs = [sl.run(out[s], tgt, theta.numpy()) for s in range(S)]
-    val = np.mean([r["sw"] for r in runs])
-    ybar = np.concatenate([r["grad"] for r in runs]) / S
-    return val, fa.pass_vjp(cfg, flat, zs, cs, ybar.astype(dt), None, False, dt)[3], runs
-  v64, g64, runs = ref(np.float64)
-  v32, g32, runs32 = ref(np.float32)
-  k_max = max(float(max(np.abs(r["kx"]).max(), np.abs(r["ky"]).max())) for r in runs)
-  d_max = max(float(max(r["kx"].max() - r["ky"].min(), r["ky"].max() - r["kx"].min())) for r in runs)
-  floor = 8.0 * 2.0 ** -24 * k_max * d_max
-  swapped = sum(int((~sl.rows_that_agree(a["perm_x"], b["perm_x"])).sum()) for a, b in zip(runs, runs32))
-  e_v, e_g = abs(float(loss) - v64), float(np.abs(g.cpu().double().numpy() - g64).max())
-  bound = fa.bound(g32, g64)
-  print(f"\n[sliced_loss_fn D={D}] loss {v64:.6f}: error {e_v:.2e} (float32 restatement {abs(v32 - v64):.2e}, floor "
-        f"{floor:.2e}) | gradient |.| {np.abs(g64).max():.3e}: error {e_g:.2e}, bound {bound:.2e} | rows whose rank "
-        f"differs between the float32 and float64 flows: {swapped}")
-  assert e_v <= 2.0 * abs(v32 - v64) + floor
-  assert e_g <= bound
-  # the same term through ordinary autograd: flow_forward + autograd.sliced_wasserstein
-  flat_t = params.flat.clone().requires_grad_(True)
-  zt = torch.from_numpy(zs).to(dev)
-  samples, _ = autograd.flow_forward(be, flat_t, zt, torch.from_numpy(conds).to(dev))
-  val = autograd.sliced_wasserstein(samples.view(S, B, D), torch.from_numpy(tgt).to(dev)[None].expand(S, -1, -1), theta)
-  assert val.shape == (S,) and val.dtype == torch.float64
-  (val.sum() / S).backward()
-  assert float(val.detach().sum() / S) == float(loss)
-  e_auto = float((flat_t.grad - g).abs().max())
-  print(f"[sliced_loss_fn D={D}] autograd against the fast path: {e_auto:.2e}")
-  assert torch.equal(flat_t.grad, g)
+  def restate(out):      # (the envelope gradient)
+    r = sl.run(out, tgt, theta.numpy())
+    return r["sw"], r["grad"], r
+
+  def floor(out64, runs):
+    k_max = max(float(max(np.abs(r["kx"]).max(), np.abs(r["ky"]).max())) for r in runs)
+    d_max = max(float(max(r["kx"].max() - r["ky"].min(), r["ky"].max() - r["kx"].min())) for r in runs)
+    return 8.0 * 2.0 ** -24 * k_max * d_max
+
+  def note(runs, runs32):
+    swapped = sum(int((~sl.rows_that_agree(a["perm_x"], b["perm_x"])).sum()) for a, b in zip(runs, runs32))
+    return f" | rows whose rank differs between the float32 and float64 flows: {swapped}"
+  sample_term_check.check(dev, f"sliced_loss_fn D={D}", D, B, tgt, app.sliced_loss_fn, dict(directions=theta),
+                          auto=lambda x, y: autograd.sliced_wasserstein(x, y, theta), restate=restate, floor=floor,
+                          note=note, exact_autograd=True)
 
 
 def test_evaluate_fp_sliced(dev):
