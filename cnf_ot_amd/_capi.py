@@ -63,6 +63,7 @@ class CnfTargetSpec(ctypes.Structure):
 
 MMD_MAX_BW, MMD_MAX_DIM, MMD_MAX_SETS = 8, 14, 64
 MMD_KINDS = {"gaussian": 0, "energy": 1}
+KNN_MAX_K, KNN_MAX_POINTS = 16, 1 << 20          # CNF_KNN_MAX_K and the largest cloud of cnf_knn
 
 
 class CnfMmdSpec(ctypes.Structure):
@@ -183,6 +184,12 @@ SYMBOLS = {
   "cnf_sliced_tile": (ctypes.c_int, []),
   "cnf_sliced_w2": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P,
                                    _P, _P, _I64, _P]),
+  # the k nearest neighbours of x [S, N, D] in x (self) and in y [S, M, D] (cross): dist, idx [S, N, k] each or NULL,
+  # sums [S, 2, k, 2] doubles (block, rank, (sum of log dist over dist > 0, rows with dist == 0))
+  "cnf_knn_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_knn_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_knn": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _I64,
+                             _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

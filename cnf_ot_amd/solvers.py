@@ -533,6 +533,57 @@ def print_fp_sliced(res: Dict[str, Any]) -> None:
           + " ".join("{:.3e} ({:.1e})".format(u, v) for u, v in zip(wm, wfl)))
 
 
+# ---- the same comparison in the unit the flow was trained in: nearest-neighbour KL and entropy, in nats --------------
+
+FP_KNN_KEYS = ("times", "kl", "kl_floor", "kl_reverse", "entropy_knn", "entropy_model", "kl_ensemble_flow", "n", "k")
+
+
+def evaluate_fp_knn(config, model: FlowModel, params: Params, times=None, n_particles=65536, h=1e-3, seed=0,
+                    k=4) -> Dict[str, Any]:
+  """How far, in NATS and in the full dimension, the flow is from the Euler-Maruyama ensemble of an fp configuration,
+  whose law at t > 0 exists only as particles: the nearest-neighbour estimates of utils.knn_divergence at rank k.
+  `times`, and the refusals, as evaluate_fp_two_sample (and what utils.knn_check_shapes refuses).  The ensemble is run as
+  its two halves; n_particles / 2 flow samples (model.apply.sample of `seed`) stand beside them.  Per time, lists of floats:
+    times
+    kl                KL(flow || half 0)
+    kl_floor          KL(half 1 || half 0): two samples of one law, so the estimator's own bias and noise -- visibly
+                      non-zero at dim 10, and what makes kl readable
+    kl_reverse        KL(half 0 || flow samples); biased low where the flow's samples are the narrower cloud (the
+                      neighbours of the ensemble's tail points are far): read it beside kl_ensemble_flow
+    entropy_knn, entropy_model  the nearest-neighbour entropy of the flow's samples beside -mean log_prob of the same
+                      samples: a check of log_prob that never touches the flow's Jacobian
+    kl_ensemble_flow  -H_knn(half 0) - mean log_prob_flow(half 0): the forward KL with a single nearest-neighbour
+                      estimate in it
+    n, k              the points per set and the rank
+  The three comparisons of all times are the sets of as few cnf_knn calls as its 64-set limit allows (one for up to 21
+  times).  Single process."""
+  k = int(k)
+  _, ts, n_particles, fp = _fp_prelude("evaluate_fp_knn", config, times, n_particles, h, 4)
+  n, S, dim = n_particles // 2, len(ts), fp[0]
+  utils.knn_check_shapes((min(3 * S, _capi.MMD_MAX_SETS), n, dim), (min(3 * S, _capi.MMD_MAX_SETS), n, dim), k)
+  flow, h0, h1 = _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed)
+  flow = flow.float()
+  x, y = torch.cat([flow, h1, h0]), torch.cat([h0, h0, flow])
+  parts = [utils.knn_divergence(x[i:i + _capi.MMD_MAX_SETS], y[i:i + _capi.MMD_MAX_SETS], k)
+           for i in range(0, 3 * S, _capi.MMD_MAX_SETS)]
+  kl, ent = (torch.cat([p[key] for p in parts]) for key in ("kl", "entropy"))
+  lp_flow = [model.apply.sample_and_log_prob(params, cond=float(t), seed=seed, sample_shape=(n,))[1].double().mean().item()
+             for t in ts]
+  lp_h0 = [model.apply.log_prob(params, h0[i], cond=float(t)).double().mean().item() for i, t in enumerate(ts)]
+  return {"times": [float(t) for t in ts], "kl": kl[:S].tolist(), "kl_floor": kl[S:2 * S].tolist(),
+          "kl_reverse": kl[2 * S:].tolist(), "entropy_knn": ent[:S].tolist(), "entropy_model": [-v for v in lp_flow],
+          "kl_ensemble_flow": [-e - v for e, v in zip(ent[2 * S:].tolist(), lp_h0)], "n": n, "k": k}
+
+
+def print_fp_knn(res: Dict[str, Any]) -> None:
+  """evaluate_fp_knn's table, one line per time"""
+  print("nearest-neighbour estimates against the particle reference ({} points per set, k = {}; nats):  t | KL(flow||ens) | "
+        "floor | KL(ens||flow samples) | H knn | H model | KL(ens||flow), one estimate".format(res["n"], res["k"]))
+  for row in zip(res["times"], res["kl"], res["kl_floor"], res["kl_reverse"], res["entropy_knn"], res["entropy_model"],
+                 res["kl_ensemble_flow"]):
+    print("  {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f}".format(*row))
+
+
 # ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------
 
 OT_REFERENCE_KEYS = ("coupling_cost", "kinetic_energy", "w2_flow", "gap_flow", "map_rmse", "map_blur", "w2_problem",
@@ -732,12 +783,13 @@ def _eval_rng(seed, step):
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
-         two_sample: bool = False, ot_reference: bool = False, sliced: bool = False) -> Dict[str, Any]:
+         two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
-  print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table."""
+  print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
+  table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -746,6 +798,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     raise ValueError(f"--two-sample compares the flow with the fp particle reference: not defined for {_type}")
   if sliced and _type != "fp":
     raise ValueError(f"--sliced compares the flow with the fp particle reference: not defined for {_type}")
+  if knn and _type != "fp":
+    raise ValueError(f"--knn compares the flow with the fp particle reference: not defined for {_type}")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -803,6 +857,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_ot_reference(evaluate_ot_reference(config, model, params))
   if sliced:
     print_fp_sliced(evaluate_fp_sliced(config, model, params))
+  if knn:
+    print_fp_knn(evaluate_fp_knn(config, model, params))
   return res
 
 
@@ -829,6 +885,9 @@ def _parse(argv):
   p.add_argument("--sliced", action="store_true",
                  help="print the sliced Wasserstein distance, in the full dimension and at the full ensemble size, between "
                       "the flow's samples and the particle reference, and the exact W2 of every marginal (fp)")
+  p.add_argument("--knn", action="store_true",
+                 help="print the nearest-neighbour estimates of KL, in nats and in the full dimension, between the flow's "
+                      "samples and the particle reference, beside their floor, and the flow's entropy two ways (fp)")
   return p.parse_args(argv)
 
 
@@ -836,4 +895,4 @@ if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
-       sliced=args.sliced)
+       sliced=args.sliced, knn=args.knn)

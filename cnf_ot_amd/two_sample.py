@@ -1,6 +1,7 @@
 """Distances between two point clouds -- what compares a flow with a target that exists only as samples: the kernel
-two-sample statistics (cnf_mmd2), the Sinkhorn divergence (cnf_sinkhorn) and the sliced Wasserstein distance
-(cnf_sliced_w2).  The kernels are three units; what surrounds a call is stated once here: the sets
+two-sample statistics (cnf_mmd2), the Sinkhorn divergence (cnf_sinkhorn), the sliced Wasserstein distance
+(cnf_sliced_w2) and the nearest-neighbour estimates of entropy and KL (cnf_knn).  The kernels are four units
+(DESIGN.md 5.3h-j, 5.3l); what surrounds a call is stated once here: the sets
 as [S, N, D] (`_sets`), the shape check (`_check_shapes`), the staging on the device (`_stage`), the workspace
 (`_workspace`) and the result of a 2-D x (`_unstack`).  `utils` re-exports the public names.
 """
@@ -11,7 +12,7 @@ from . import _capi
 from .flows import _OnDevice, _stream_ptr
 
 
-# ---- what the three share ---------------------------------------------------------------------------------------------
+# ---- what the units share ----------------------------------------------------------------------------------------------
 
 def _sets(fn, t, name):
   """A point set, or S of them, as an [S, N, D] tensor where it is ([N, D]: S = 1)."""
@@ -328,3 +329,101 @@ def sliced_wasserstein(x, y, directions=None, n_proj=64, seed=0, want_grad=False
                                           _ptr(grad), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)), "cnf_sliced_w2")
   return {"sw": sums[:, P], "per_projection": sums[:, :P], "max_sliced": sums[:, P + 1], "directions": th,
           "grad": _unstack(grad, one)}
+
+
+# ---- nearest-neighbour estimates: entropy, cross entropy and KL in nats between point clouds -------------------------
+# The note quoted above holds for the plug-in formula; the nearest-neighbour estimators need samples alone.  One fused
+# call scans x against x and x against y over all sets (cnf_knn); composed in torch (cdist + topk) the
+# same scan materialises the N x M matrix.  No gradient and no training term: the estimator's gradient is too noisy to
+# train on, and no reference call site asks for one.
+
+KNN_MAX_K, KNN_MAX_POINTS = _capi.KNN_MAX_K, _capi.KNN_MAX_POINTS
+
+
+def knn_check_shapes(x_shape, y_shape=None, k=4):
+  """ValueError for what cnf_knn refuses: ([S, N, D], [S, M, D] or None, k) with S in 1..64, D in 1..14, k in 1..16, N in
+  k + 1..2^20, M in k..2^20."""
+  k = int(k)
+  if not 1 <= k <= KNN_MAX_K:
+    raise ValueError(f"knn: k must be in 1..{KNN_MAX_K}, not {k}")
+  _check_shapes("knn", x_shape, x_shape if y_shape is None else y_shape, k, KNN_MAX_POINTS)
+  if x_shape[1] < k + 1:
+    raise ValueError(f"knn: x needs at least k + 1 = {k + 1} points (a point is not its own neighbour), not {x_shape[1]}")
+
+
+def knn(x, y=None, k=4, want_indices=False) -> dict:
+  """The k nearest neighbours of every point of x [N, D] or [S, N, D] among the OTHER points of x and, with y [M, D] or
+  [S, M, D], among the points of y (set s of x against set s of y), ONE cnf_knn call over all sets.  Neighbours are
+  ascending by (squared distance as computed in float32 from coordinate differences, index): of two equal distances
+  the smaller index comes first, and a duplicate point at another index is a neighbour at distance 0.  float32 on the
+  device (float64 inputs are rounded; host inputs are uploaded).  Returns a dict:
+    dist_xx, dist_xy  [S, N, k] float32 ([N, k] for 2-D x), ranks 1..k; dist_xy is None without y
+    idx_xx, idx_xy    want_indices: the neighbours' rows, int32, shaped like the distances (idx_xy None without y)
+    sums              [S, 2, k, 2] float64: per block (self, cross) and rank, the sum of log dist over the rows whose
+                      dist is > 0 and the number of rows whose dist is 0 (the cross half: zeros without y) -- what
+                      knn_estimates reads
+  Rank j does not depend on k, two calls give the same bits, and the numbers do not depend on want_indices.  There is
+  no gradient: the estimators built on these distances are for evaluation, their gradient is too noisy to train on.
+  ValueError before any device work for what the C ABI refuses and for x and y that differ in S or D."""
+  x3 = _sets("knn", x, "x")
+  y3 = None if y is None else _sets("knn", y, "y")
+  knn_check_shapes(x3.shape, None if y3 is None else y3.shape, k)
+  k = int(k)
+  S, N, D = x3.shape
+  M = 0 if y3 is None else y3.shape[1]
+  dev, one, (x3, ys) = _stage(x, x3, x3 if y3 is None else y3)
+  y3 = None if y3 is None else ys
+  ws = _workspace(dev, _workspace_bytes("cnf_knn_workspace", S, N, M, D, k))
+  sums = torch.empty(S, 2, k, 2, dtype=torch.float64, device=dev)
+  new = lambda dtype: torch.empty(S, N, k, dtype=dtype, device=dev)
+  dxx, dxy = new(torch.float32), None if y3 is None else new(torch.float32)
+  ixx = new(torch.int32) if want_indices else None
+  ixy = new(torch.int32) if want_indices and y3 is not None else None
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_knn(S, x3.data_ptr(), N, _ptr(y3), M, D, k, _ptr(dxx), _ptr(ixx), _ptr(dxy), _ptr(ixy),
+                                    sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)), "cnf_knn")
+  out = {"dist_xx": _unstack(dxx, one), "dist_xy": _unstack(dxy, one), "sums": sums}
+  if want_indices:
+    out.update(idx_xx=_unstack(ixx, one), idx_xy=_unstack(ixy, one))
+  return out
+
+
+def knn_estimates(sums, N, M, D) -> dict:
+  """The nearest-neighbour estimators, in nats and in float64, for every rank j = 1..k of sums [S, 2, k, 2] (knn's): with
+  psi the digamma function, log V_D = (D / 2) log pi - lgamma(D / 2 + 1) the log volume of the unit ball, and the means
+  taken over the rows whose distance is not 0 (sums[..., 0] / (N - sums[..., 1])),
+    entropy [S, k]        psi(N) - psi(j) + log V_D + D mean_i log rho_j(i)   (Kozachenko-Leonenko)
+    cross_entropy [S, k]  log M  - psi(j) + log V_D + D mean_i log nu_j(i)    (Leonenko-Pronzato-Savani)
+    kl [S, k]             cross_entropy - entropy                              (Wang-Kulkarni-Verdu, psi-corrected)
+    zeros [S, 2, k]       the rows left out of each mean
+  rho_j(i): the distance from x_i to its j-th nearest other point of x; nu_j(i): to its j-th nearest point of the M
+  points of y.  M = 0 (no y): cross_entropy and kl are None.  This is the one place the estimators are written down."""
+  sums = torch.as_tensor(sums).double()
+  k, N, M, D = sums.shape[2], int(N), int(M), int(D)
+  psi = lambda v: torch.special.digamma(torch.as_tensor(v, dtype=torch.float64, device=sums.device))
+  psi_j = psi(list(range(1, k + 1)))
+  log_vd = 0.5 * D * float(np.log(np.pi)) - float(torch.lgamma(torch.tensor(0.5 * D + 1.0, dtype=torch.float64)))
+  zeros = sums[..., 1]
+  mean = sums[..., 0] / (N - zeros)
+  entropy = psi(float(N)) - psi_j + log_vd + D * mean[:, 0]
+  cross = None if M == 0 else float(np.log(M)) - psi_j + log_vd + D * mean[:, 1]
+  return {"entropy": entropy, "cross_entropy": cross, "kl": None if M == 0 else cross - entropy, "zeros": zeros}
+
+
+def knn_divergence(x, y, k=4) -> dict:
+  """KL(x || y) in nats between the point sets x [N, D] or [S, N, D] and y [M, D] or [S, M, D] from their samples alone
+  (knn, knn_estimates): kl, entropy (of x) and cross_entropy [S] (float64) at rank k, by_rank (knn_estimates' dict, every
+  rank 1..k), zeros [S, 2, k] and k.  The estimate carries a bias that grows with the dimension: read it beside the same
+  estimate between two samples of one law.  No gradient (see knn)."""
+  x3, y3 = _sets("knn", x, "x"), _sets("knn", y, "y")
+  est = knn_estimates(knn(x3, y3, k)["sums"], x3.shape[1], y3.shape[1], x3.shape[2])
+  return {"kl": est["kl"][:, -1], "entropy": est["entropy"][:, -1], "cross_entropy": est["cross_entropy"][:, -1],
+          "by_rank": est, "zeros": est["zeros"], "k": int(k)}
+
+
+def knn_entropy(x, k=4) -> dict:
+  """The Kozachenko-Leonenko entropy, in nats, of the point sets x [N, D] or [S, N, D] (the self block of knn alone):
+  entropy [S] (float64) at rank k, by_rank, zeros [S, 2, k] and k."""
+  x3 = _sets("knn", x, "x")
+  est = knn_estimates(knn(x3, None, k)["sums"], x3.shape[1], 0, x3.shape[2])
+  return {"entropy": est["entropy"][:, -1], "by_rank": est, "zeros": est["zeros"], "k": int(k)}

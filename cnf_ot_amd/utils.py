@@ -19,7 +19,8 @@ from .two_sample import (  # noqa: F401
     MEDIAN_BANDWIDTH_FACTORS, median_bandwidths, mmd_spec, mmd_check_shapes, mmd2_from_sums, mmd2,
     SINKHORN_MAX_ITERS, SINKHORN_MAX_POINTS, sinkhorn_check_shapes, sinkhorn_check_schedule, sinkhorn_schedule, sinkhorn,
     SLICED_MAX_PROJ, SLICED_MAX_POINTS, SLICED_WORKSPACE_BYTES, sliced_directions, sliced_check_shapes, sliced_group,
-    sliced_wasserstein)
+    sliced_wasserstein,
+    KNN_MAX_K, KNN_MAX_POINTS, knn_check_shapes, knn, knn_estimates, knn_divergence, knn_entropy)
 
 
 def _model_of(fn_or_model):

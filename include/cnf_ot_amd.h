@@ -871,6 +871,46 @@ int cnf_sliced_w2(int32_t S, const float *x, int64_t N, const float *y, int64_t 
                   const float *theta, int32_t P, int32_t G, double *sums, float *grad,
                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- k nearest neighbours between point clouds: entropy, cross entropy and KL in nats from samples alone ------------
+ * The reference's note (tests/test_wasserstein_geodesic.py:165-169), "with samples of the target alone KL cannot be
+ * computed", holds for the plug-in formula, not for the nearest-neighbour estimators.  Model-free.  For S independent
+ * sets, x [S, N, D] and optionally y [S, M, D] (device, float32), two blocks per set:
+ *   self   rho_j(i) = the distance from x_i to its j-th nearest OTHER point of x (the diagonal is left out by index; a
+ *          duplicate of x_i at another index is a neighbour at distance 0);
+ *   cross  nu_j(i)  = the distance from x_i to its j-th nearest point of y.
+ * Squared distances are formed from coordinate differences in float32: diff = x - c, d2 = diff_0^2, then
+ * d2 = fmaf(diff_d, diff_d, d2) in ascending d (the distance of cnf_mmd2).  ORDER: neighbours are ascending by (d2 as
+ * computed, index); of two equal d2 the smaller index comes first.  Rank j depends neither on k nor on what else is
+ * asked for.
+ * cnf_knn writes
+ *   dist_xx, dist_xy [S, N, k] (device, float32, each or NULL): (float)sqrt((double)d2), ranks 1..k;
+ *   idx_xx, idx_xy [S, N, k] (device, int32, each or NULL): the neighbour's row in x (self) or y (cross);
+ *   sums [S, 2, k, 2] (device, double, overwritten): per block (self, cross) and rank j,
+ *     sums[s, b, j, 0] = sum over the rows i with d2_j(i) > 0 of 0.5 log((double)d2_j(i)), and
+ *     sums[s, b, j, 1] = the number of rows with d2_j(i) == 0.
+ * From them, with psi the digamma function, log V_D = (D / 2) log pi - lgamma(D / 2 + 1) the log volume of the unit
+ * ball, and the means taken over the rows counted in the sum, the caller forms
+ *   the Kozachenko-Leonenko entropy           H(x)    ~ psi(N) - psi(j) + log V_D + D mean_i log rho_j(i),
+ *   the Leonenko-Pronzato-Savani cross entropy H(x, y) ~ log M  - psi(j) + log V_D + D mean_i log nu_j(i),
+ *   and KL(x || y) ~ H(x, y) - H(x), the Wang-Kulkarni-Verdu estimator with the psi corrections.
+ * With M == 0 and y == NULL the self block alone is computed and the cross half of sums is written as zeros.
+ * One launch scans both blocks of all sets, the columns of a block split over cnf_knn_splits(S, N, M, D) workgroups (a
+ * function of the sizes alone); a second merges a row's splits in ascending order, a third adds the rows in a fixed
+ * order: no atomics, two calls are bit-identical, the numbers do not depend on which optional outputs are asked for,
+ * and the result does not depend on what the workspace held.  There is no gradient.
+ * cnf_knn_workspace: the bytes of device workspace (8-byte aligned) such a call needs; no HIP call.  The workspace is
+ * the caller's: cnf_knn neither allocates nor synchronises (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL x, sums or workspace; y NULL with M != 0 or y given
+ * with M == 0; dist_xy or idx_xy given with M == 0; S outside 1..64; D outside 1..14; k outside 1..CNF_KNN_MAX_K; N
+ * outside k + 1..2^20; M outside k..2^20 and not 0; a workspace smaller than cnf_knn_workspace says. */
+#define CNF_KNN_MAX_K 16
+int cnf_knn_workspace(int32_t S, int64_t N, int64_t M, int32_t D, int32_t k, int64_t *bytes);
+/* the column splits of a block at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_knn_splits(int32_t S, int64_t N, int64_t M, int32_t D);
+int cnf_knn(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int32_t D, int32_t k,
+            float *dist_xx, int32_t *idx_xx, float *dist_xy, int32_t *idx_xy, double *sums,
+            void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);

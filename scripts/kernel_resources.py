@@ -12,8 +12,8 @@ txt = open(out).read()
 names = []
 for b in txt.split("  - .agpr_count:")[1:]:
   g = lambda k: re.search(r"\." + k + r":\s+(\S+)", b).group(1)
-  names.append((g("name"), g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("vgpr_spill_count")))
+  names.append((g("name"), g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("vgpr_spill_count"), g("sgpr_spill_count")))
 dem = subprocess.run(["c++filt"], input="\n".join(n[0] for n in names), capture_output=True, text=True).stdout.split("\n")
-for (n, v, s, p, sp), d in zip(names, dem):
-  print(f"{d[:110]:110s} vgpr {v:>4} sgpr {s:>4} scratch {p:>5} spills {sp:>3}")
+for (n, v, s, p, sp, ssp), d in zip(names, dem):
+  print(f"{d[:110]:110s} vgpr {v:>4} sgpr {s:>4} scratch {p:>5} spills {sp:>3} sgpr spills {ssp:>3}")
 print("asm:", out)
