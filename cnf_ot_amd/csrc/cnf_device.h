@@ -68,6 +68,8 @@ enum TabField {
   F_XKB2,    //   clamp-FMA that forms the bin masks of a sample pair (bin_of_pairs); two fields wide
   F_YKB,     // the same for the y knots
   F_YKB2,
+  F_D0BH,    // d0 bh (rounded once from float64) and 2 s (exactly twice F_S): the per-bin products of the sampling
+  F_2S,      //   direction's quadratic (rqs_bin_eval PRE)
   F_COUNT
 };
 enum { T_DLO = 0, T_DHI, T_LOG_DLO, T_LOG_DHI, T_INV_DLO, T_INV_DHI };
@@ -233,6 +235,19 @@ template <> struct Math<true> {
   }
 };
 
+// clip01(a b) of a sample pair as ONE v_pk_mul_f32 with the clamp modifier (clip01 on the product is a packed
+// multiply and two v_max_f32 ... clamp).  Same values bit for bit.
+// The operands come straight from v_rcp_f32: a vector instruction may not read a transcendental's result in the
+// very next issue slot, and the compiler, which spaces its own instructions, does not look inside an asm
+// statement -- hence the s_nop (without it the pair's second half reads the register's previous value).
+__device__ __forceinline__ v2f mul_clip01(v2f a, v2f b) {
+  v2f z;
+  asm("s_nop 0\n\tv_pk_mul_f32 %0, %1, %2 clamp" : "=v"(z) : "v"(a), "v"(b));
+  return z;
+}
+__device__ __forceinline__ float mul_clip01(float a, float b) { return clip01(a * b); }
+__device__ __forceinline__ double mul_clip01(double a, double b) { return clip01(a * b); }
+
 // softplus(t + offset) + m  (distrax _normalize_knot_slopes)
 template <bool FAST, class T, bool OFFSET_ADDED = false>
 __device__ __forceinline__ T knot_slope(T t, const SplineConstsT<typename Lanes<T>::real> sc) {
@@ -264,19 +279,34 @@ __device__ __forceinline__ T knot_slope(T t, const SplineConstsT<typename Lanes<
 // evaluates several splines multiplies the arguments and takes one logarithm.
 // NEWTON=false (the flow kernel's sampling direction): the root's quotient is one v_rcp_f32 product,
 // 1 ulp instead of 0.5 -- z in [0, 1] only enters x0 + bw z and the derivative's polynomial.
-template <bool INV, bool FAST, class T, bool L2S_GIVEN = true, bool ARG = false, bool NEWTON = true>
+// NEWTON=false forms the quadratic with no scaling by a literal: c2 = 2s dy with the 2s of the derivative's numerator,
+// -4 a c = a (c2 + c2), z = c2 / (b + sqrt(disc)) -- the parent form's values bit for bit (scalings by 2 are exact).
+// PRE (the `first` spline there): d0bh = d0 bh and s2 = 2 s come from the bin's prepared row (F_D0BH, F_2S), six
+// packed operations after dy; d0bh is rounded once from float64 instead of being the product of two rounded fields.
+template <bool INV, bool FAST, class T, bool L2S_GIVEN = true, bool ARG = false, bool NEWTON = true, bool PRE = false>
 __device__ __forceinline__ void rqs_bin_eval(T v, T x0, T y0, T bw, T bh, T ibw, T s, T st,
-                                             T d0, T d1, T l2s, T& out, T& ld) {
+                                             T d0, T d1, T l2s, T& out, T& ld, T d0bh = T{}, T s2 = T{}) {
   using M = Math<FAST>;
+  static_assert(!PRE || (INV && !NEWTON), "prepared products: the sampling direction's root");
+  static_assert(NEWTON || INV, "the root without its Newton step: the inverse only");
   T z;
+  [[maybe_unused]] T two_s;                       // NEWTON=false: 2 s, shared by the root and the derivative
   if (INV) {
     const T dy = vclamp(v - y0, bh);              // bh * w, w clipped to [0, 1]
-    const T c = -s * dy;
-    const T b = vfma(-st, dy, d0 * bh);
-    const T a = vfma(s, bh, -b);
-    const T disc = vfma(b, b, a * c * -4.0f);
-    if constexpr (NEWTON) z = clip01(M::div(c * -2.0f, b + M::sqrt(disc)));
-    else z = clip01(c * -2.0f * M::rcp(b + M::sqrt(disc)));
+    if constexpr (NEWTON) {
+      const T c = -s * dy;
+      const T b = vfma(-st, dy, d0 * bh);
+      const T a = vfma(s, bh, -b);
+      const T disc = vfma(b, b, a * c * -4.0f);
+      z = clip01(M::div(c * -2.0f, b + M::sqrt(disc)));
+    } else {
+      two_s = PRE ? s2 : s * 2.0f;
+      const T c2 = two_s * dy;
+      const T b = vfma(-st, dy, PRE ? d0bh : d0 * bh);
+      const T a = vfma(s, bh, -b);
+      const T disc = vfma(b, b, a * (c2 + c2));
+      z = mul_clip01(c2, M::rcp(b + M::sqrt(disc)));
+    }
     out = vfma(bw, z, x0);
   } else {
     z = clip01((v - x0) * ibw);
@@ -287,7 +317,7 @@ __device__ __forceinline__ void rqs_bin_eval(T v, T x0, T y0, T bw, T bh, T ibw,
   const T den = vfma(st, z1mz, s);
   const T iden = M::rcp(den);
   if (!INV) out = vfma(bh * vfma(s, sq_z, d0 * z1mz), iden, y0);
-  const T num2 = vfma(d1, sq_z, vfma(s * 2.0f, z1mz, d0 * omz * omz));
+  const T num2 = vfma(d1, sq_z, vfma(NEWTON ? s * 2.0f : two_s, z1mz, d0 * omz * omz));
   // 2 log s + log(num2) - 2 log(den)
   if constexpr (ARG) {
     static_assert(!L2S_GIVEN, "the argument form folds s^2 in");
@@ -321,6 +351,8 @@ template <int K, class R> __device__ __forceinline__ int bin_of(const R* pos, R 
 // -2^60 knot_j twice in a row (F_XKB / F_YKB), so the FMA's third operand is one ds_read_b64 from a uniform
 // address: per knot one LDS read and one VALU instruction (11 VALU per pair in all, against 26 for per-sample
 // sign-bit arithmetic).
+// (The asm statement's operands come from an LDS read and plain arithmetic.  An asm statement that reads the result
+// of a transcendental -- v_rcp_f32, v_sqrt_f32, v_exp_f32, v_log_f32 -- needs a wait state of its own: mul_clip01.)
 template <int K> __device__ __forceinline__ v2i bin_of_pairs(const float* kb, v2f v) {
   const v2f big = v2f{1.152921504606846976e18f, 1.152921504606846976e18f};       // 2^60
   v2f c = v2f{0.0f, 0.0f};
@@ -375,7 +407,13 @@ __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab,
   // (the pair rows are read through volatile pointers: a field the direction does not use must not be asked for)
   const T bw = INV ? row.template get<K>(F_BW) : splat<T>(0.0f);          // the inverse never divides by bw ...
   const T ibw = INV ? splat<T>(0.0f) : row.template get<K>(F_IBW);        // ... the forward map only does
-  if constexpr (ARG)
+  if constexpr (ARG && LEAN && INV)
+    rqs_bin_eval<INV, FAST, T, false, true, false, true>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
+                                            row.template get<K>(F_BH), ibw,
+                                            row.template get<K>(F_S), row.template get<K>(F_ST), row.template get<K>(F_D0),
+                                            row.template get<K>(F_D1), splat<T>(0.0f), out, ld,
+                                            row.template get<K>(F_D0BH), row.template get<K>(F_2S));
+  else if constexpr (ARG)
     rqs_bin_eval<INV, FAST, T, false, true, !LEAN>(v, row.template get<K>(F_X0), row.template get<K>(F_Y0), bw,
                                             row.template get<K>(F_BH), ibw,
                                             row.template get<K>(F_S), row.template get<K>(F_ST), row.template get<K>(F_D0),
@@ -405,7 +443,8 @@ __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab,
 // ---------------------------------------------------------------------------
 // 0/1 mask of (d > 0) for a sample pair: clamp(d * 2^60) -- one v_pk_mul_f32
 // with the clamp modifier (differences below 2^-60 count as ties, i.e. the
-// lower bin, where the spline is continuous anyway).
+// lower bin, where the spline is continuous anyway).  `d` must not be a transcendental's result: an asm statement
+// gets no wait state from the compiler (mul_clip01).
 __device__ __forceinline__ v2f step_mask(v2f d, v2f big) {
   v2f m;
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(m) : "v"(d), "v"(big));

@@ -152,6 +152,10 @@ __global__ void prepare_kernel(const float* __restrict__ params, float* __restri
     prep[tab_off(F_D0, K) + k] = (float)dl[k];
     prep[tab_off(F_D1, K) + k] = (float)dl[k + 1];
     prep[tab_off(F_L2S, K) + k] = (float)(2.0 * log(s));
+    // the per-bin products of the sampling direction's quadratic (rqs_bin_eval PRE)
+    td[tab_off(F_D0BH, K) + k] = dl[k] * bh;     td[tab_off(F_2S, K) + k] = 2.0 * s;
+    prep[tab_off(F_D0BH, K) + k] = (float)(dl[k] * bh);
+    prep[tab_off(F_2S, K) + k] = 2.0f * (float)s;      // exactly twice F_S, which the derivative's denominator reads
   }
   for (int k = threadIdx.x; k <= K; k += blockDim.x) {
     const float big = 1.152921504606846976e18f;      // 2^60

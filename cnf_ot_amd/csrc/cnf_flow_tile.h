@@ -352,8 +352,11 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       }
       // One logarithm per layer where every lane takes the shift-free form: both splines return the argument of
       // their log|f'| (the derivative itself) and the product goes through one v_log_f32.  The conditioned
-      // factor is bounded there (slope logits in [-3, 40], bins >= 1e-4 of a range of 20: ~1e-9 .. 1e6), so the
-      // product leaves the fp32 range only for a `first` spline with derivatives beyond 1e-29 .. 1e32.
+      // factor is bounded there (slope logits in [-3, 40]: knot slopes d in [0.049, 40]; bins >= 1e-4 of a range of
+      // 20: s in [5e-6, 2e5]).  With t = z (1 - z) <= 1/4, f' = s^2 num2 / den^2 has num2 >= min(d0, d1) / 2 and
+      // s / 2 <= den <= max(s, (d0 + d1 + 2 s) / 4), hence 2 s^2 d_lo / (d_hi + s)^2 ~ 1.5e-15 <= f' <= 4 max(d, s)
+      // ~ 8e5.  The product of the two factors of a layer stays a normal fp32 number for a `first` spline with
+      // derivatives within 1e-22 .. 1e32.
       constexpr bool LOGPROD = LEAN;
       // Both splines read the layer's inputs (uf, uo): one wave-level test guards both linear-tail fix-ups.
       bool tails = true;
