@@ -390,7 +390,14 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   // PWL_TS samples exist.  A lane's share is then a 32-bit offset from a scalar base address, and a full tile
   // -- every tile but the last of a slice of odd size -- takes the unmasked path.
   // A block's tiles are contiguous: only its first tile's slice takes a division, each next tile steps (slice, ti).
-  struct Tile { int slice; int ti; int valid; int64_t g0; int64_t st0; int64_t gin; };
+  // `left`: the slice's samples from the tile's first one on, in 32 bits where the launch's slice length is below
+  // 2^30 (`big` otherwise, a launch constant: every slice of such a launch, a short last one included, keeps tile_at
+  // per tile): within a slice the next tile is then a handful of 32-bit scalar steps, and the 64-bit arithmetic of
+  // tile_at runs once per slice.  No slice is longer than slice_len and a slice has fewer than slice_len / PWL_TS + 1
+  // tiles, so `left` stays within (-2^30 - PWL_TS, 2^30) however far the steps go; it is clamped before it is
+  // narrowed all the same.
+  const bool big = a.slice_len >= ((int64_t)1 << 30);
+  struct Tile { int slice; int ti; int valid; int left; int64_t g0; int64_t st0; int64_t gin; };
   auto tile_at = [&](int slice, int ti) {
     Tile t;
     t.slice = slice;
@@ -400,6 +407,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     const int64_t jt = (int64_t)ti * PWL_TS;
     const int64_t left = len - jt;
     t.valid = left >= PWL_TS ? PWL_TS : (left > 0 ? (int)left : 0);
+    t.left = big ? 0 : (int)(left < -(int64_t)PWL_TS ? -(int64_t)PWL_TS : left);
     t.g0 = s0 + jt;
     t.gin = a.in_shared ? jt : t.g0;
     t.st0 = a.first_sample + (int64_t)t.slice * a.slice_stride + jt;      // (seeded calls: the tile's first stream sample)
@@ -407,9 +415,19 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   };
   auto tile_of = [&](int tile) { const int sl = tile / a.tiles_per_slice; return tile_at(sl, tile - sl * a.tiles_per_slice); };
   auto tile_next = [&](const Tile& t) {
-    return t.ti + 1 < a.tiles_per_slice ? tile_at(t.slice, t.ti + 1) : tile_at(t.slice + 1, 0);
+    if (t.ti + 1 >= a.tiles_per_slice) return tile_at(t.slice + 1, 0);
+    if (big) return tile_at(t.slice, t.ti + 1);
+    Tile n = t;
+    n.ti = t.ti + 1;
+    n.left = t.left - PWL_TS;
+    n.valid = n.left >= PWL_TS ? PWL_TS : (n.left > 0 ? n.left : 0);
+    n.g0 = t.g0 + PWL_TS; n.gin = t.gin + PWL_TS; n.st0 = t.st0 + PWL_TS;
+    return n;
   };
   const uint32_t lane2 = 2u * (uint32_t)tid;             // the lane's first sample within the tile
+  // What the launch asks for is the same in every tile: bit 0 aux, bit 1 out, bit 2 aux is log_prob.
+  const bool lp = a.aux_mode == AUX_LOGPROB;
+  const int omode = (a.aux ? 1 : 0) | (a.out ? 2 : 0) | (lp ? 4 : 0);
   auto tile_points = [&](const Tile& t) {
     f4 x = {0.f, 0.f, 0.f, 0.f};
     if (SEEDED && !a.in) {   // the pair's four normals (one Philox block when the pair starts on an even sample)
@@ -439,6 +457,7 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   [[maybe_unused]] f4 xn = {0.f, 0.f, 0.f, 0.f};
   Tile tn{};
   if (t0 < t1) { tn = tile_of(t0); xn = tile_points(tn); }
+  f4 x = xn;
   for (int tile = t0; tile < t1; ++tile) {
     const Tile tl = tn;
     const int slice = tl.slice;
@@ -449,35 +468,51 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
       __syncthreads();
     }
     const bool full = tl.valid == PWL_TS;
-    const bool v0 = (int)lane2 < tl.valid, v1 = (int)lane2 + 1 < tl.valid;
-    const f4 x = xn;
     if (tile + 1 < t1) { tn = tile_next(tl); xn = tile_points(tn); }
     __builtin_amdgcn_sched_barrier(0);
     v2f u0 = {x[0], x[2]}, u1 = {x[1], x[3]};
     [[maybe_unused]] v2f poison = splat<v2f>(0.0f);      // (flow_kernel: a NaN coordinate must come out as NaN)
     if constexpr (TO_BASE) poison = (u0 - u0) + (u1 - u1);
 
+    // (pinned here: left to the compiler the base term is sunk to the end of the tile, which keeps the four input
+    // registers live across the whole flow and costs four moves to re-pair them)
     v2f base = splat<v2f>(0.0f);
-    if (!TO_BASE && a.aux_mode == AUX_LOGPROB && a.aux) base = (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI);
+    if (!TO_BASE && lp && a.aux) base = (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI);
+    if (!TO_BASE) asm volatile("" : "+v"(base));
     BaseAcc<v2f> bacc;
     const v2f acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX, true>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
                                                             u0, u1, &a.m.scd, e2tab, tabd, &bacc);
-    if (a.aux) {
-      v2f r = acc;
-      if constexpr (PRECISE) { if (a.aux_mode == AUX_LOGPROB) r = bacc.log_prob(acc, 2); }
-      else if (a.aux_mode == AUX_LOGPROB)
-        r = TO_BASE ? (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI) + acc : base - acc;
-      if constexpr (TO_BASE) r += poison;
-      float* q = a.aux + tl.g0;
-      if (full || v1) *reinterpret_cast<v2f*>(q + lane2) = r;
-      else if (v0) q[lane2] = r.x;
-    }
-    if (a.out) {
-      float* q = a.out + 2 * tl.g0;
-      if constexpr (TO_BASE) { u0 += poison; u1 += poison; }
-      if (full || v1) *reinterpret_cast<f4*>(q + 2u * lane2) = f4{u0.x, u1.x, u0.y, u1.y};
-      else if (v0) { q[2u * lane2] = u0.x; q[2u * lane2 + 1] = u1.x; }
-    }
+    // The next tile's points are taken BEFORE this tile's stores are issued: stores count in vmcnt, and a wait for
+    // the points behind them is a wait for the stores' acknowledgement -- once per tile, with nothing to overlap it.
+    // In front of them only the load and the previous tile's stores are outstanding; these stores drain under the
+    // next tile's arithmetic.
+    asm volatile("" : "+v"(xn));
+    __builtin_amdgcn_sched_barrier(0);
+    // has_aux / is_lp / has_out / whole: constants in the branch of a full tile of a call for both outputs (every
+    // tile but a slice's last in the sampling calls), where the stores are then unconditional and lane validity
+    // is not even formed; the launch's own values otherwise.
+    auto emit = [&](bool has_aux, bool is_lp, bool has_out, bool whole) {
+      const bool v0 = (int)lane2 < tl.valid, v1 = (int)lane2 + 1 < tl.valid;
+      if (has_aux) {
+        v2f r = acc;
+        if constexpr (PRECISE) { if (is_lp) r = bacc.log_prob(acc, 2); }
+        else if (is_lp)
+          r = TO_BASE ? (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI) + acc : base - acc;
+        if constexpr (TO_BASE) r += poison;
+        float* q = a.aux + tl.g0;
+        if (whole || v1) *reinterpret_cast<v2f*>(q + lane2) = r;
+        else if (v0) q[lane2] = r.x;
+      }
+      if (has_out) {
+        float* q = a.out + 2 * tl.g0;
+        if constexpr (TO_BASE) { u0 += poison; u1 += poison; }
+        if (whole || v1) *reinterpret_cast<f4*>(q + 2u * lane2) = f4{u0.x, u1.x, u0.y, u1.y};
+        else if (v0) { q[2u * lane2] = u0.x; q[2u * lane2 + 1] = u1.x; }
+      }
+    };
+    if (full && omode == 7) emit(true, true, true, true);
+    else emit(a.aux != nullptr, lp, a.out != nullptr, full);
+    x = xn;
   }
 }
 
