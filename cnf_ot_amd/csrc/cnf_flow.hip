@@ -360,6 +360,10 @@ __global__ void cond_uniform_kernel(const float* __restrict__ c, int64_t B, uint
   if (__syncthreads_or(diff) && threadIdx.x == 0) *flag = epoch;
 }
 
+// s_waitcnt vmcnt(0) as the builtin's immediate (gfx9: vmcnt in bits 3:0 and 15:14), the export and LDS / scalar
+// counters at their maxima, i.e. not waited for
+constexpr int PWL_WAIT_VM0 = 0x0F70;
+
 template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, int LROWS = PWL_LROWS, int LFIX = 0, bool SEEDED = false>
 __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs a) {
   const int PWL_THREADS = blockDim.x, PWL_TS = 2 * PWL_THREADS;
@@ -447,9 +451,14 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
       return x;
     }
     const float* p = a.in + 2 * t.gin;
-    if (t.valid == PWL_TS) x = *reinterpret_cast<const f4*>(p + 2u * lane2);
-    else if ((int)lane2 + 1 < t.valid) x = *reinterpret_cast<const f4*>(p + 2u * lane2);
+    if (t.valid == PWL_TS) return *reinterpret_cast<const f4*>(p + 2u * lane2);
+    if ((int)lane2 + 1 < t.valid) x = *reinterpret_cast<const f4*>(p + 2u * lane2);
     else if ((int)lane2 < t.valid) { x[0] = p[2u * lane2]; x[1] = p[2u * lane2 + 1]; }
+    // A partial tile's masked loads (a slice's last tile, once per slice at most) are waited for where they are
+    // issued.  Left pending they reach the block where they merge with the full-tile load, and the compiler's
+    // wait-count bookkeeping then guards the full tile's address computation with an s_waitcnt vmcnt(0) in front of
+    // the prefetch: every wave waited there, once per tile, for the two stores it had issued a moment before.
+    __builtin_amdgcn_s_waitcnt(PWL_WAIT_VM0);
     return x;
   };
   // The points of tile i + 1 are requested before tile i is computed: measured (r02e PMC) a wave spent half its
@@ -458,6 +467,10 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
   Tile tn{};
   if (t0 < t1) { tn = tile_of(t0); xn = tile_points(tn); }
   f4 x = xn;
+  // (the first tile's points, taken here: with the wait in tile_points alone the compiler puts a vmcnt(0) at the top
+  // of the tile body, directly behind the prefetch -- worse than what it replaces; with both, the full-tile path has
+  // one vmcnt wait per tile, the one in front of the stores below.  Read the assembly after any edit around here.)
+  __builtin_amdgcn_s_waitcnt(PWL_WAIT_VM0);
   for (int tile = t0; tile < t1; ++tile) {
     const Tile tl = tn;
     const int slice = tl.slice;
