@@ -71,6 +71,17 @@ class CnfMmdSpec(ctypes.Structure):
   _fields_ = [("kind", ctypes.c_int32), ("n_bw", ctypes.c_int32), ("bw", ctypes.c_float * MMD_MAX_BW)]
 
 
+INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS = 4, 1 << 20
+INTERACTION_KINDS = {"gaussian": 0, "exponential": 1, "quadratic": 2}
+
+
+class CnfInteractionSpec(ctypes.Structure):
+  """The pair kernel of cnf_interaction (include/cnf_ot_amd.h): kind 0 = a signed sum of Gaussians, 1 = of exponentials
+  of the distance (Morse), 2 = amp[0] r^2 / 2."""
+  _fields_ = [("kind", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("amp", ctypes.c_float * INTERACTION_MAX_TERMS),
+              ("bw", ctypes.c_float * INTERACTION_MAX_TERMS)]
+
+
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
 TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
@@ -190,6 +201,13 @@ SYMBOLS = {
   "cnf_knn_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_knn": (ctypes.c_int, [ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _I64,
                              _P]),
+  # the interaction energy of x [S, N, D] (self mode) or its field at q [S, Q, D]: sums [S] doubles, pot [S, rows] and
+  # force [S, rows, D] each or NULL
+  "cnf_interaction_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.POINTER(_I64)]),
+  "cnf_interaction_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_interaction": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32,
+                                     _P, _P, _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi, two_sample
+from . import interaction as ia      # (the composites take a keyword of that name)
 from .distributed import Shard, all_reduce_sums, current_shard, shard_range
 from .flows import DeviceRng, FlowEngine, _OnDevice, _stream_ptr, seed_to_u64
 
@@ -1107,31 +1108,38 @@ def importance_stats(model, params, target, conds, rng, batch_size, scale=None, 
 # ---- sample-only fitting terms: a distance between the flow's samples and given target samples ----------------------
 
 def _sample_term(name, why, model, params, target, cond, rng, batch_size, shard, grad, refuse, stat):
-  """The mean over the times of `cond` of a point-set statistic (two_sample) between batch_size flow samples per time
-  -- the same base draw of `rng` for every time -- and `target`, [M, D] or one set per time; with `grad` its parameter
-  gradient, by ONE cnf_pass_vjp call seeded with the statistic's gradient in the samples / S.  The term supplies
-  refuse(S, target shape [S, M, D]): its own ValueErrors, returning what its checks resolved; and
-  stat(samples [S, B, D], target [S, M, D], what refuse returned, want_grad) -> (values [S], gradient [S, B, D] or
-  None).  Every refusal, the term's included, comes before the backend is touched.  `why`: the subject of the
-  single-rank refusal."""
+  """The mean over the times of `cond` of a point-set statistic (two_sample, interaction) of batch_size flow samples
+  per time -- the same base draw of `rng` for every time -- against `target`, [M, D] or one set per time, or (target
+  None) of the samples alone; with `grad` its parameter gradient, by ONE cnf_pass_vjp call seeded with the statistic's
+  gradient in the samples / S.  The term supplies
+  refuse(S, target shape [S, M, D] or None): its own ValueErrors, returning what its checks resolved; and
+  stat(samples [S, B, D], target [S, M, D] or None, what refuse returned, want_grad) -> (values [S], gradient [S, B, D]
+  or None).  Every refusal, the term's included, comes before the backend is touched; a term without a target also
+  refuses a terms backend that is not the HIP engine, before it is used.  `why`: the subject of the single-rank
+  refusal."""
   shard = shard if shard is not None else current_shard()
   if shard.world > 1:
     raise ValueError(f"{name}: single rank only ({why} an all-gather of the samples)")
   conds = _conds(cond)
   S = _n_conds(conds)
-  tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
-  if tgt.dim() == 2:
-    tgt = tgt[None].expand(S, -1, -1)
-  if tgt.dim() != 3 or tgt.shape[0] != S:
-    raise ValueError(f"{name}: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
-  checked = refuse(S, tgt.shape)
+  tgt = None
+  if target is not None:
+    tgt = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target))
+    if tgt.dim() == 2:
+      tgt = tgt[None].expand(S, -1, -1)
+    if tgt.dim() != 3 or tgt.shape[0] != S:
+      raise ValueError(f"{name}: target must be [M, D] or [{S}, M, D] (one set per time), not {tuple(tgt.shape)}")
+  checked = refuse(S, None if tgt is None else tgt.shape)
   ctx = _Ctx(model, params, rng, shard, grad)
+  if tgt is None and not ctx.hip:
+    raise ValueError(f"{name}: the terms backend must be the HIP engine, not {type(ctx.be).__name__}")
   be = ctx.be
   z, _, count = ctx.noise(batch_size)
   zs = z.repeat(S, 1)                                         # the same draw for every time
   c = be.slice_conds(conds)
   samples, _ = be.forward_logdet(zs, c, want_logdet=False)
-  values, xgrad = stat(samples.view(S, count, -1), tgt.to(device=samples.device, dtype=torch.float32), checked,
+  values, xgrad = stat(samples.view(S, count, -1),
+                       None if tgt is None else tgt.to(device=samples.device, dtype=torch.float32), checked,
                        grad is not None)
   if grad is not None:
     be.pass_vjp(zs, c, (xgrad * (1.0 / S)).view(S * count, -1), None, False, grad=grad, want_xbar=False)
@@ -1214,17 +1222,80 @@ def sliced_loss_fn(model, dim, params, target, cond, rng, batch_size, directions
                       grad, refuse, stat)
 
 
+# ---- the nonlocal cost of a mean-field control problem: the interaction energy of the flow's own samples --------------
+
+def interaction_loss_fn(model, dim, params, cond, rng, batch_size, kind, amplitudes=None, bandwidths=None, shard=None,
+                        grad=None):
+  """The mean over the times of `cond` of the interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1))
+  (utils.interaction_energy: kind, amplitudes and bandwidths are utils.interaction_spec's) of batch_size flow samples at
+  that time -- the same base draw of `rng` for every time, as the other sample terms.  W > 0 is congestion, W < 0 or
+  quadratic W aggregation, a Morse W swarming.  With `grad` (the convention of the other term functions;
+  `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_interaction call (value and
+  d / d samples) and ONE cnf_pass_vjp call; more than 64 times go in chunks of 64 sets.  Single rank: the pairs across
+  ranks would need an all-gather of the samples, so a shard (or a torch.distributed world) of more than one rank raises
+  ValueError, as does a terms backend that is not the HIP engine."""
+  def refuse(S, _):      # -> the spec
+    ia.interaction_check_shapes((min(S, _capi.MMD_MAX_SETS), int(batch_size), int(dim)))
+    return ia.interaction_spec(kind, amplitudes, bandwidths)
+
+  def stat(samples, _, spec, want_grad):
+    return ia.energy_of_sets(spec, samples, want_grad)
+  return _sample_term("interaction_loss_fn", "pairs across ranks need", model, params, None, cond, rng, batch_size, shard,
+                      grad, refuse, stat)
+
+
+def _interaction_refuse(name, given, rng, shard, sub, dim):
+  """(spec, strength) of a composite loss's `interaction=(spec_kwargs, strength)` -- ValueError, before any device work,
+  for what the interaction part refuses: a captured step, more than one rank, fewer than 2 samples per time, a bad
+  spec."""
+  spec_kwargs, strength = given
+  if isinstance(rng, DeviceRng):
+    raise ValueError(f"{name}: an interaction term is for the eager update only (the captured step draws on the device)")
+  if (shard if shard is not None else current_shard()).world > 1:
+    raise ValueError(f"{name}: an interaction term is single rank only (pairs across ranks need an all-gather of the "
+                     "samples)")
+  if sub < 2:
+    raise ValueError(f"{name}: an interaction term needs batch_size // 32 >= 2 samples per time, not {sub}")
+  ia.interaction_check_shapes((1, int(sub), int(dim)))
+  return ia.interaction_spec(**spec_kwargs), float(strength)
+
+
+def _interaction_values(ctx, spec, conds, sub, coef):
+  """F [S] (float64) of the first `sub` samples of the loss's draw at the times `conds` (a host array), by ONE
+  cnf_interaction call per 64 times; with ctx.grad, coef / S times the gradient of their sum is queued as one base ->
+  data backward pass (defer_pass_vjp: it leaves with the loss's other passes, in `reduce`)."""
+  if not ctx.hip:
+    raise ValueError(f"an interaction term needs the HIP engine as the terms backend, not {type(ctx.be).__name__}")
+  be = ctx.be
+  z, _, count = ctx.noise(sub)
+  th = _conds(conds)
+  S = _n_conds(th)
+  zs = z.repeat(S, 1)                                         # the same draw for every time
+  samples, _ = be.forward_logdet(zs, be.slice_conds(th), want_logdet=False)
+  values, xgrad = ia.energy_of_sets(spec, samples.view(S, count, -1), ctx.grad is not None)
+  if ctx.grad is not None:
+    ctx.defer_pass_vjp(zs, th, count, (xgrad * (coef / S)).view(S * count, -1), None)
+  return values
+
+
 # ---- composite losses ---------------------------------------------------------
 
 def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, batch_size,
-               source="mixture", shard=None, grad=None, overlap=None):
+               source="mixture", shard=None, grad=None, overlap=None, interaction=None):
   """applications.py:377-402.  overlap (sharded value_and_grad only; default OVERLAP_ALLREDUCE): the density-fit
-  terms' all-reduce runs under the kinetic / obstacle slices."""
+  terms' all-reduce runs under the kinetic / obstacle slices.  interaction=(spec_kwargs, strength): the loss gains
+  strength T mean_t F(rho_t), the interaction energy (interaction_loss_fn; spec_kwargs: utils.interaction_spec's
+  arguments) at the time batch the loss drew, on the batch_size // 32 samples of the kinetic term -- no extra host
+  draw; its gradient lands in `grad`.  Eager, single rank."""
+  if interaction is not None:
+    ia_spec, ia_strength = _interaction_refuse("ot_loss_fn", interaction, rng, shard, batch_size // 32, dim)
   ctx = _Ctx(model, params, rng, shard, grad)
   t_batch = draw_t_batch(rng, t_batch_size)
   sub = batch_size // 32
   c_kl, c_kin = _lambda / batch_size, 0.5 / (sub * t_batch_size)
   first = [_kl_sum(ctx, T, 0.0, batch_size, source, c_kl), _kl_sum(ctx, T, float(T), batch_size, source, c_kl)]
+  if interaction is not None:      # (after the full draw: its samples are that draw's first rows)
+    ia_values = _interaction_values(ctx, ia_spec, t_batch, sub, ia_strength * T)
 
   def later():
     if subtype == "obstacle":      # summed, not averaged, over slices (applications.py:397-400)
@@ -1237,19 +1308,27 @@ def ot_loss_fn(model, dim, T, dt, t_batch_size, subtype, params, rng, _lambda, b
   c_later = [c_kin] + ([1.0 / sub] if subtype == "obstacle" else [])
   if (OVERLAP_ALLREDUCE if overlap is None else overlap) and ctx.shard.world > 1 and ctx.grad is not None:
     return ctx.combine_overlapped(first, [c_kl, c_kl], later, c_later)
-  return ctx.combine(first + later(), [c_kl, c_kl] + c_later)
+  loss = ctx.combine(first + later(), [c_kl, c_kl] + c_later)
+  # (one addition, in the float64 `combine` returns; the part's backward pass left with the others, in `reduce`)
+  return loss if interaction is None else loss + (ia_strength * T) * (ia_values.sum() / t_batch_size)
 
 
 def rwpo_loss_fn(model, dim, T, beta, dt, dx, t_batch_size, subtype, a, params, rng, _lambda, batch_size,
-                 shard=None, grad=None):
-  """applications.py:405-421"""
+                 shard=None, grad=None, interaction=None):
+  """applications.py:405-421.  interaction=(spec_kwargs, strength): as ot_loss_fn's."""
+  if interaction is not None:
+    ia_spec, ia_strength = _interaction_refuse("rwpo_loss_fn", interaction, rng, shard, batch_size // 32, dim)
   ctx = _Ctx(model, params, rng, shard, grad)
   t_batch = draw_t_batch(rng, t_batch_size, T)
   sub = batch_size // 32
   c_rkl, c_pot, c_kin = _lambda / batch_size, 1.0 / batch_size, 0.5 * T / (sub * t_batch_size)
-  return ctx.combine([_reverse_kl_sum(ctx, T, beta, 0.0, batch_size, c_rkl),
-                      _potential_sum(ctx, a, subtype, [float(T)], batch_size, c_pot),
-                      _kinetic_score_sum(ctx, beta, dt, dx, t_batch, sub, c_kin)], [c_rkl, c_pot, c_kin])
+  sums = [_reverse_kl_sum(ctx, T, beta, 0.0, batch_size, c_rkl),
+          _potential_sum(ctx, a, subtype, [float(T)], batch_size, c_pot),
+          _kinetic_score_sum(ctx, beta, dt, dx, t_batch, sub, c_kin)]
+  if interaction is not None:      # (after the full draw: its samples are that draw's first rows)
+    ia_values = _interaction_values(ctx, ia_spec, t_batch, sub, ia_strength * T)
+  loss = ctx.combine(sums, [c_rkl, c_pot, c_kin])
+  return loss if interaction is None else loss + (ia_strength * T) * (ia_values.sum() / t_batch_size)
 
 
 def fp_loss_fn(model, dim, T, a, sigma, dt, dx, t_batch_size, subtype, params, rng, _lambda, batch_size,

@@ -15,7 +15,7 @@ the parameters only; its time derivatives are finite differences).
 """
 import torch
 
-from . import _capi, two_sample
+from . import _capi, interaction, two_sample
 from .flows import FlowEngine, _stream_ptr
 
 
@@ -145,3 +145,28 @@ def sliced_wasserstein(x: torch.Tensor, y: torch.Tensor, directions):
   (applications.sliced_loss_fn is the hand-written fast path)."""
   stat = lambda a, b, want_grad, first: two_sample.sliced_wasserstein(a, b, directions, want_grad=want_grad)
   return _PointSetStat.apply(x, y, stat, "sw")
+
+
+class _InteractionEnergy(torch.autograd.Function):
+  """The interaction energy of one point set: the forward call stores dF / dx, backward is it times the incoming scalar."""
+
+  @staticmethod
+  def forward(ctx, x, kind, amplitudes, bandwidths):
+    res = interaction.interaction_energy(x.detach(), kind, amplitudes, bandwidths, want_grad=ctx.needs_input_grad[0])
+    ctx.save_for_backward(res.get("grad"))
+    return res["energy"]
+
+  @staticmethod
+  def backward(ctx, gbar):
+    g, = ctx.saved_tensors
+    w = gbar.to(torch.float32)
+    return (None if g is None else g * w[:, None, None] if g.dim() == 3 else g * w[0]), None, None, None
+
+
+def interaction_energy(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None):
+  """The mean-field interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1)) of the sample sets x [N, D] or
+  [S, N, D] (utils.interaction_energy: a signed Gaussian, exponential or quadratic pair kernel), [S] float64 ([1] for a
+  2-D input), differentiable in x: backward is the gradient cnf_interaction stored times the incoming scalar.  The
+  kernel's amplitudes and bandwidths are constants.  With `flow_forward` a flow trains on the energy through ordinary
+  autograd (applications.interaction_loss_fn is the hand-written fast path)."""
+  return _InteractionEnergy.apply(x, kind, amplitudes, bandwidths)

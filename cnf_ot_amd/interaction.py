@@ -1,0 +1,140 @@
+"""The mean-field interaction energy of a point cloud -- the one cost of a mean-field control problem that is not
+local in the density: F[rho] = 1/2 int int W(x - y) rho(x) rho(y) dx dy on samples, its first variation W * rho (a
+field) and its Wasserstein gradient grad (W * rho) (a force), for a signed Gaussian, exponential (Morse) or quadratic
+pair kernel W(|x - y|).  One fused call over all sets (cnf_interaction); composed in torch the same
+double sum materialises an N x N matrix per set and its backward.  What surrounds a call is `two_sample`'s.  `utils`
+re-exports the public names.
+"""
+import numpy as np
+import torch
+
+from . import _capi
+from .flows import _OnDevice, _stream_ptr
+from .two_sample import _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes
+
+INTERACTION_KINDS = tuple(_capi.INTERACTION_KINDS)
+INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS = _capi.INTERACTION_MAX_TERMS, _capi.INTERACTION_MAX_POINTS
+
+
+def _floats(v):
+  return [float(b) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
+
+
+def interaction_spec(kind, amplitudes=None, bandwidths=None):
+  """The CnfInteractionSpec of a pair kernel -- ValueError for what cnf_interaction refuses in a spec:
+    kind="gaussian":     W(r) = sum_b amplitudes[b] exp(-r^2 / (2 bandwidths[b]^2))
+    kind="exponential":  W(r) = sum_b amplitudes[b] exp(-r / bandwidths[b])  (Morse: amplitudes (C_r, -C_a))
+    kind="quadratic":    W(r) = amplitudes[0] r^2 / 2  (bandwidths are not used)
+  Amplitudes are signed, non-zero and finite (None: 1.0 each); 1..4 bandwidths (None: 1.0), positive and finite as
+  float32 with 1 / bw^2, and amp / bw^2 (Gaussian) or amp / bw (exponential), in float32's range."""
+  if kind not in _capi.INTERACTION_KINDS:
+    raise ValueError(f"interaction: kind is one of {INTERACTION_KINDS}, not {kind!r}")
+  spec = _capi.CnfInteractionSpec()
+  spec.kind = _capi.INTERACTION_KINDS[kind]
+  if kind == "quadratic":
+    amps = [1.0] if amplitudes is None else _floats(amplitudes)
+    if len(amps) != 1:
+      raise ValueError(f"interaction: the quadratic kind has one amplitude, not {len(amps)}")
+    bws = []
+  else:
+    bws = [1.0] * (1 if amplitudes is None else len(_floats(amplitudes))) if bandwidths is None else _floats(bandwidths)
+    amps = [1.0] * len(bws) if amplitudes is None else _floats(amplitudes)
+    if not 1 <= len(bws) <= INTERACTION_MAX_TERMS or len(amps) != len(bws):
+      raise ValueError(f"interaction: between 1 and {INTERACTION_MAX_TERMS} terms, an amplitude and a bandwidth each, not "
+                       f"{len(amps)} amplitudes and {len(bws)} bandwidths")
+  for a in amps:
+    a32 = float(np.float32(a))
+    if not (np.isfinite(a32) and a32 != 0.0):
+      raise ValueError(f"interaction: every amplitude must be non-zero and finite (in float32): {amps}")
+  for a, b in zip(amps, bws):
+    a32, b32 = float(np.float32(a)), float(np.float32(b))      # (as the kernel sees them)
+    if not (b32 > 0.0 and np.isfinite(b32) and 1.0 / (b32 * b32) <= 3.0e38):
+      raise ValueError(f"interaction: every bandwidth must be positive and finite (in float32, with 1 / bw^2): {bws}")
+    ib = 1.0 / (b32 * b32) if kind == "gaussian" else 1.0 / b32
+    if not abs(a32 * ib) <= 3.4028234663852886e38:
+      raise ValueError(f"interaction: amplitude / bandwidth{'^2' if kind == 'gaussian' else ''} leaves float32's range: "
+                       f"{a}, {b}")
+  spec.n_terms = max(1, len(bws))
+  for i, a in enumerate(amps):
+    spec.amp[i] = a
+  for i, b in enumerate(bws):
+    spec.bw[i] = b
+  return spec
+
+
+def interaction_check_shapes(x_shape, q_shape=None):
+  """ValueError for what cnf_interaction refuses: sources [S, N, D] with S in 1..64, N in 2..2^20, D in 1..14 and, in
+  query mode, points [S, Q, D] with Q in 1..2^20."""
+  S, N, D = x_shape
+  if not 1 <= S <= _capi.MMD_MAX_SETS or not 1 <= D <= _capi.MMD_MAX_DIM or not 2 <= N <= INTERACTION_MAX_POINTS:
+    raise ValueError(f"interaction: needs 1..{_capi.MMD_MAX_SETS} sets of 2..2^20 points of dimension "
+                     f"1..{_capi.MMD_MAX_DIM}, not {tuple(x_shape)}")
+  if q_shape is not None:
+    if len(q_shape) != 3 or q_shape[0] != S or q_shape[2] != D or not 1 <= q_shape[1] <= INTERACTION_MAX_POINTS:
+      raise ValueError(f"interaction: the query points must be [{S}, Q, {D}] with Q in 1..2^20, not {tuple(q_shape)}")
+
+
+def _call(spec, x3, q3, want_pot, want_force):
+  """ONE cnf_interaction call on staged tensors: (sums [S], pot [S, rows] or None, force [S, rows, D] or None)."""
+  S, N, D = x3.shape
+  Q = 0 if q3 is None else q3.shape[1]
+  rows, dev = Q or N, x3.device
+  ws = _workspace(dev, _workspace_bytes("cnf_interaction_workspace", S, N, Q, D, 1 if want_force else 0))
+  sums = torch.empty(S, dtype=torch.float64, device=dev)
+  pot = torch.empty(S, rows, dtype=torch.float32, device=dev) if want_pot else None
+  force = torch.empty(S, rows, D, dtype=torch.float32, device=dev) if want_force else None
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_interaction(_capi.ctypes.byref(spec), S, x3.data_ptr(), N, _ptr(q3), Q, D, sums.data_ptr(),
+                                            _ptr(pot), _ptr(force), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+                "cnf_interaction")
+  return sums, pot, force
+
+
+def energy_of_sets(spec, x3, want_grad):
+  """(F [S] float64, dF / dx [S, N, D] or None) of staged sets x3 [S, N, D] with any S: ONE cnf_interaction call per 64
+  sets."""
+  N = x3.shape[1]
+  parts = [_call(spec, x3[i:i + _capi.MMD_MAX_SETS], None, False, want_grad)
+           for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
+  sums = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+  force = None if not want_grad else parts[0][2] if len(parts) == 1 else torch.cat([p[2] for p in parts])
+  return sums / (2.0 * N * (N - 1.0)), None if force is None else force * (1.0 / N)
+
+
+def interaction_energy(x, kind, amplitudes=None, bandwidths=None, want_grad=False, want_field=False) -> dict:
+  """The interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1)) of the point sets x [N, D] or [S, N, D] for the
+  pair kernel of `interaction_spec`, ONE fused cnf_interaction call over all sets (self mode: the pair i == j is
+  skipped by index; duplicated points at other indices do interact).  float32 on the device (float64 inputs are
+  rounded; host inputs are uploaded).  Returns a dict: energy [S] (float64), sums [S] (the raw double sum) and, with
+  want_field, potential [S, N] (float32; [N] for 2-D x) = (W * rho)(x_i) over the other N - 1 points, with want_grad,
+  grad [S, N, D] ([N, D] for 2-D x) = dF / dx = the force grad (W * rho)(x_i) / N.  Two calls give the same bits, and
+  the energy does not depend on the want_ flags.  ValueError before any device work for what the C ABI refuses."""
+  x3 = _sets("interaction", x, "x")
+  interaction_check_shapes(x3.shape)
+  spec = interaction_spec(kind, amplitudes, bandwidths)
+  N = x3.shape[1]
+  dev, one, (x3, _) = _stage(x, x3, x3[:, :0])
+  sums, pot, force = _call(spec, x3, None, want_field, want_grad)
+  out = {"energy": sums / (2.0 * N * (N - 1.0)), "sums": sums}
+  if want_field:
+    out["potential"] = _unstack(pot, one)
+  if want_grad:
+    out["grad"] = _unstack(force * (1.0 / N), one)
+  return out
+
+
+def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, want_force=True) -> dict:
+  """The field of the sources [N, D] or [S, N, D] at the points [Q, D] or [S, Q, D] (set s against set s), ONE fused
+  cnf_interaction call in query mode (nothing is skipped): potential [S, Q] (float32; [Q] for 2-D points) =
+  (W * rho)(q_i) = mean_j W(q_i - x_j), with want_force force [S, Q, D] = grad (W * rho)(q_i) -- what a particle method
+  with this interaction would call per step -- and sums [S] (float64) = sum_i sum_j W.  ValueError before any device
+  work for what the C ABI refuses and for points and sources that differ in S or D."""
+  q3, x3 = _sets("interaction", points, "points"), _sets("interaction", sources, "sources")
+  interaction_check_shapes(x3.shape, tuple(q3.shape))
+  spec = interaction_spec(kind, amplitudes, bandwidths)
+  dev, one, (q3, x3) = _stage(points, q3, x3)
+  sums, pot, force = _call(spec, x3, q3, True, want_force)
+  out = {"potential": _unstack(pot, one), "sums": sums}
+  if want_force:
+    out["force"] = _unstack(force, one)
+  return out

@@ -9,7 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
-                               [--path-errors] [--fit]
+                               [--path-errors] [--fit] [--interaction]
 """
 import argparse
 import sys
@@ -33,6 +33,9 @@ DEFAULT_CONFIG: Dict[str, Dict[str, Any]] = {
   "fp": {"T": 1, "a": 1, "sigma": 0.5, "velocity_field_type": "gradient"},
   "cnf": {"flow_num_layers": 2, "mlp_num_layers": 2, "hidden_size": 16, "num_bins": 5},
   "train": {"epochs": 30000, "lr": 0.001, "_lambda": 5000.0, "batch_size": 2048, "eval_frequency": 100},
+  # not in the reference: a nonlocal running cost strength * int_0^T F(rho_t) dt for ot and rwpo, F the interaction energy
+  # of utils.interaction_energy (kind "none": no such cost; "gaussian", "exponential", "quadratic": utils.interaction_spec)
+  "interaction": {"kind": "none", "strength": 1.0, "amplitudes": [1.0], "bandwidths": [1.0]},
 }
 
 
@@ -60,19 +63,37 @@ def build_model(config) -> FlowModel:
 
 
 def bind_loss(config, model) -> Callable:
-  """solvers.py:58-88: loss_fn(params, rng, _lambda, batch_size)."""
+  """solvers.py:58-88: loss_fn(params, rng, _lambda, batch_size).  With an `interaction` section whose kind is not
+  "none", ot and rwpo gain its running cost (the losses' `interaction=`); fp has no such term: ValueError."""
   g = config["general"]
   _type, dim, dt, dx, tbs = g["type"], g["dim"], g["dt"], g["dx"], g["t_batch_size"]
+  kw = {}
+  if _interaction_kind(config) != "none":
+    if _type == "fp":
+      raise ValueError("an interaction term is defined for ot and rwpo: fp_loss_fn's drifts are compiled into the "
+                       "flow-matching kernel (an interacting drift is out of scope)")
+    kw["interaction"] = (_interaction_kwargs(config), float(config["interaction"]["strength"]))
   if _type == "rwpo":
     r = config["rwpo"]
-    return partial(applications.rwpo_loss_fn, model, dim, r["T"], r["beta"], dt, dx, tbs, r["pot_type"], r["a"])
+    return partial(applications.rwpo_loss_fn, model, dim, r["T"], r["beta"], dt, dx, tbs, r["pot_type"], r["a"], **kw)
   if _type == "fp":
     f = config["fp"]
     return partial(applications.fp_loss_fn, model, dim, f["T"], f["a"], f["sigma"], dt, dx, tbs,
                    f["velocity_field_type"])
   if _type == "ot":
-    return partial(applications.ot_loss_fn, model, dim, 1, dt, tbs, config["ot"]["subtype"])
+    return partial(applications.ot_loss_fn, model, dim, 1, dt, tbs, config["ot"]["subtype"], **kw)
   raise Exception(f"Unknown problem type: {_type}...")        # solvers.py:87-88
+
+
+def _interaction_kind(config) -> str:
+  return config.get("interaction", {}).get("kind", "none")
+
+
+def _interaction_kwargs(config) -> Dict[str, Any]:
+  """utils.interaction_spec's arguments from the config's `interaction` section"""
+  i = config["interaction"]
+  return {"kind": i["kind"], "amplitudes": i.get("amplitudes"),
+          "bandwidths": None if i["kind"] == "quadratic" else i.get("bandwidths")}
 
 
 @dataclass
@@ -208,7 +229,10 @@ def make_update(loss_fn: Callable, optimizer: Adam, batch_size: int, capture: bo
 def train(config, epochs: int = None, log=None, capture: bool = False):
   """The training loop of solvers.py:99-127 without tqdm/plots: returns
   (params, loss history as a list of 0-dim device tensors).  capture=True: every step after the first two is the
-  replay of one HIP graph (CapturedUpdate)."""
+  replay of one HIP graph (CapturedUpdate); ValueError, before any device work, with an interaction term (eager update
+  only)."""
+  if capture and _interaction_kind(config) != "none":
+    raise ValueError("train: an interaction term is for the eager update only (the captured step draws on the device)")
   model = build_model(config)
   seed = int(config["general"]["seed"])
   params = model.init(seed)
@@ -584,6 +608,60 @@ def print_fp_knn(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f}".format(*row))
 
 
+# ---- the nonlocal running cost of a trained flow: its interaction energy along the path ------------------------------
+
+INTERACTION_KEYS = ("times", "energy", "floor", "running_cost", "trace_cov", "kind", "strength", "n")
+
+
+def evaluate_interaction(config, model: FlowModel, params: Params, times=None, n=8192, seed=0) -> Dict[str, Any]:
+  """The interaction energy F(rho_t) (utils.interaction_energy, the kernel of the config's `interaction` section) of the
+  flow's samples at `times` (default: 9 times of [0, T]; T = 1 for ot).  Per time n samples are drawn
+  (model.apply.sample of `seed`) and read as two halves of n / 2.  Lists of floats, one per time:
+    times
+    energy        F of the first half
+    floor         |F(first half) - F(second half)|: two samples of one law, so the Monte-Carlo level of `energy`
+    trace_cov     quadratic kind: amp_0 tr(cov) / 2 of the first half from utils.point_stats (cov: unbiased, the factor
+                  N / (N - 1) applied) -- the same number as `energy`; else None
+  and running_cost = strength * the trapezoid rule of `energy` over `times` (what the training term estimates by
+  strength T mean_t F), kind, strength and n (the points per set).  The 2 x len(times) sets are ONE cnf_interaction
+  call (up to 32 times).  ValueError, before any device work, for kind "none", n < 4 and what utils.interaction_spec and
+  utils.interaction_check_shapes refuse."""
+  kind = _interaction_kind(config)
+  if kind == "none":
+    raise ValueError("evaluate_interaction: the config's interaction kind is 'none'")
+  _type = config["general"]["type"]
+  T = 1.0 if _type == "ot" else float(config[_type]["T"])
+  ts = np.linspace(0.0, T, 9) if times is None else utils._times_of(times)
+  half, S, dim = int(n) // 2, len(ts), config["general"]["dim"]
+  kw, strength = _interaction_kwargs(config), float(config["interaction"]["strength"])
+  utils.interaction_spec(**kw)
+  utils.interaction_check_shapes((min(2 * S, _capi.MMD_MAX_SETS), half, dim))
+  draws = [model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(2 * half,)) for t in ts]
+  x = torch.stack([d[:half] for d in draws] + [d[half:] for d in draws]).float()
+  F = torch.cat([utils.interaction_energy(x[i:i + _capi.MMD_MAX_SETS], **kw)["energy"]
+                 for i in range(0, 2 * S, _capi.MMD_MAX_SETS)])
+  energy = F[:S].tolist()
+  trace_cov = None
+  if kind == "quadratic":
+    cov = torch.cat([utils.point_stats(x[i:i + _capi.MMD_MAX_SETS])["cov"] for i in range(0, S, _capi.MMD_MAX_SETS)])[:S]
+    amp = float(np.float32(kw["amplitudes"][0] if kw["amplitudes"] is not None else 1.0))
+    trace_cov = (0.5 * amp * half / (half - 1.0) * cov.diagonal(dim1=1, dim2=2).sum(1)).tolist()
+  return {"times": [float(t) for t in ts], "energy": energy, "floor": (F[:S] - F[S:]).abs().tolist(),
+          "running_cost": strength * sum(0.5 * (energy[i] + energy[i + 1]) * float(ts[i + 1] - ts[i]) for i in range(S - 1)),
+          "trace_cov": trace_cov,
+          "kind": kind, "strength": strength, "n": half}
+
+
+def print_interaction(res: Dict[str, Any]) -> None:
+  """evaluate_interaction's table, one line per time, and the running cost"""
+  quad = res["trace_cov"] is not None
+  print("interaction energy of the flow's samples ({} kernel, {} points per set):  t | F | floor{}".format(
+    res["kind"], res["n"], " | amp tr(cov) / 2" if quad else ""))
+  for i, row in enumerate(zip(res["times"], res["energy"], res["floor"])):
+    print("  {:.4f} | {:.6e} | {:.2e}".format(*row) + (" | {:.6e}".format(res["trace_cov"][i]) if quad else ""))
+  print("running cost strength * int F dt (strength {}): {:.6e}".format(res["strength"], res["running_cost"]))
+
+
 # ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------
 
 OT_REFERENCE_KEYS = ("coupling_cost", "kinetic_energy", "w2_flow", "gap_flow", "map_rmse", "map_blur", "w2_problem",
@@ -783,13 +861,14 @@ def _eval_rng(seed, step):
 
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
-         two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False) -> Dict[str, Any]:
+         two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
+         interaction: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
-  table."""
+  table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -800,6 +879,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     raise ValueError(f"--sliced compares the flow with the fp particle reference: not defined for {_type}")
   if knn and _type != "fp":
     raise ValueError(f"--knn compares the flow with the fp particle reference: not defined for {_type}")
+  if interaction and _interaction_kind(config) == "none":
+    raise ValueError("--interaction prints the interaction energy of the config's `interaction` section: its kind is 'none'")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -859,6 +940,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_sliced(evaluate_fp_sliced(config, model, params))
   if knn:
     print_fp_knn(evaluate_fp_knn(config, model, params))
+  if interaction:
+    print_interaction(evaluate_interaction(config, model, params))
   return res
 
 
@@ -888,6 +971,9 @@ def _parse(argv):
   p.add_argument("--knn", action="store_true",
                  help="print the nearest-neighbour estimates of KL, in nats and in the full dimension, between the flow's "
                       "samples and the particle reference, beside their floor, and the flow's entropy two ways (fp)")
+  p.add_argument("--interaction", action="store_true",
+                 help="print the interaction energy of the flow's samples along the path, beside its Monte-Carlo floor, and "
+                      "the running cost (a config with an `interaction` section whose kind is not none)")
   return p.parse_args(argv)
 
 
@@ -895,4 +981,4 @@ if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
-       sliced=args.sliced, knn=args.knn)
+       sliced=args.sliced, knn=args.knn, interaction=args.interaction)

@@ -4,7 +4,7 @@
     loop; here a chunk of slices is ONE fused launch (grid over (slice, sample tile)) that returns one sum per slice;
   - the arrays under its figures (:598-798): density, velocity and score fields, trajectories, and `point_stats`;
   - the distances between two point clouds (mmd2, sinkhorn, sliced_wasserstein and their helpers), which live in
-    `two_sample` and are re-exported here.
+    `two_sample` and are re-exported here, as is the interaction energy of one cloud (`interaction`).
 """
 from typing import Optional
 
@@ -21,6 +21,9 @@ from .two_sample import (  # noqa: F401
     SLICED_MAX_PROJ, SLICED_MAX_POINTS, SLICED_WORKSPACE_BYTES, sliced_directions, sliced_check_shapes, sliced_group,
     sliced_wasserstein,
     KNN_MAX_K, KNN_MAX_POINTS, knn_check_shapes, knn, knn_estimates, knn_divergence, knn_entropy)
+from .interaction import (  # noqa: F401
+    INTERACTION_KINDS, INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS, interaction_spec, interaction_check_shapes,
+    interaction_energy, interaction_field)
 
 
 def _model_of(fn_or_model):

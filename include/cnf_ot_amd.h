@@ -911,6 +911,56 @@ int cnf_knn(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int
             float *dist_xx, int32_t *idx_xx, float *dist_xy, int32_t *idx_xy, double *sums,
             void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the mean-field interaction energy of a point cloud, its field and its force -------------------------------------
+ * The nonlocal cost of a mean-field control problem, F[rho] = 1/2 int int W(x - y) rho(x) rho(y) dx dy, on samples: a
+ * double sum with first variation W * rho (a field) and Wasserstein gradient grad (W * rho) (a force).  Model-free.
+ * The pair kernel is a function of r = |x - y| with SIGNED amplitudes (W > 0: congestion, W < 0: aggregation):
+ *   kind CNF_INTERACTION_GAUSSIAN:     W = sum_b amp_b exp(-r^2 / (2 bw_b^2)),  b < n_terms <= 4
+ *   kind CNF_INTERACTION_EXPONENTIAL:  W = sum_b amp_b exp(-r / bw_b)           (Morse: n_terms = 2, amp = (C_r, -C_a));
+ *                                      grad W is 0 at a coincident pair (r^2 <= 1e-30)
+ *   kind CNF_INTERACTION_QUADRATIC:    W = amp_0 r^2 / 2                        (n_terms and bw are ignored)
+ * For S independent sets x [S, N, D] (device, float32), one entry with two modes:
+ *   self mode  (q == NULL, Q == 0): the rows are the particles themselves; the pair i == j is skipped by INDEX (a
+ *              duplicate of x_i at another index does interact); n = N - 1;
+ *   query mode (q [S, Q, D], Q >= 1): the rows are the points q against the sources x; nothing is skipped; n = N.
+ * cnf_interaction writes
+ *   sums [S] (device, double, overwritten): sum_i sum_j W(row_i - x_j), the RAW double sum over the rows; in self mode
+ *     the caller forms F = sums / (2 N (N - 1)), and because W is even dF / dx_i = force_i / N;
+ *   pot [S, rows] (device, float32, or NULL): (1 / n) sum_j W(row_i - x_j), that is (W * rho)(row_i);
+ *   force [S, rows, D] (device, float32, or NULL): (1 / n) sum_j grad W(row_i - x_j), that is grad (W * rho)(row_i).
+ * Distances are formed from coordinate differences in float32 in the fmaf order of cnf_mmd2; no float32 accumulator
+ * holds more than 64 pair terms before it is added into a double.  One launch computes all sets, the columns split over
+ * cnf_interaction_splits(S, N, Q, D) workgroups (a function of the sizes alone); a second adds a row's splits in
+ * ascending order and the rows in a fixed order: no atomics, two calls are bit-identical, sums does not depend on
+ * whether pot or force are asked for, and the result does not depend on what the workspace held.  The spec is a HOST
+ * argument.
+ * cnf_interaction_workspace: the bytes of device workspace (8-byte aligned) a call needs -- want_rows != 0: a call
+ * that asks for force (pot needs no more than sums); no HIP call.  The workspace is the caller's: cnf_interaction
+ * neither allocates nor synchronises (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x, sums or workspace; q NULL with Q != 0 or q
+ * given with Q == 0; S outside 1..64; D outside 1..14; N outside 2..2^20; Q outside 1..2^20 and not 0; an unknown
+ * kind; n_terms outside 1..4; an amp that is zero or not finite; a bw that is not positive and finite, whose 1 / bw^2
+ * leaves float32's range or for which amp / bw^2 (Gaussian) or amp / bw (exponential) does; a workspace smaller than
+ * cnf_interaction_workspace says.
+ * Out of scope: weighted particles, kernels singular at 0 (Coulomb, log), more than one rank, D > 14, N > 2^20. */
+#define CNF_INTERACTION_MAX_TERMS 4
+typedef enum {
+  CNF_INTERACTION_GAUSSIAN = 0, CNF_INTERACTION_EXPONENTIAL = 1, CNF_INTERACTION_QUADRATIC = 2
+} CnfInteractionKind;
+typedef struct CnfInteractionSpec {
+  int32_t kind;                 /* CnfInteractionKind                                     */
+  int32_t n_terms;              /* 1 .. CNF_INTERACTION_MAX_TERMS; quadratic: ignored     */
+  float amp[CNF_INTERACTION_MAX_TERMS];
+  float bw[CNF_INTERACTION_MAX_TERMS];
+} CnfInteractionSpec;
+int cnf_interaction_workspace(int32_t S, int64_t N, int64_t Q, int32_t D, int32_t want_rows,
+                              int64_t *bytes);
+/* the column splits at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_interaction_splits(int32_t S, int64_t N, int64_t Q, int32_t D);
+int cnf_interaction(const CnfInteractionSpec *spec, int32_t S, const float *x, int64_t N,
+                    const float *q, int64_t Q, int32_t D, double *sums, float *pot, float *force,
+                    void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
