@@ -208,6 +208,13 @@ SYMBOLS = {
   "cnf_interaction_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_interaction": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32,
                                      _P, _P, _P, _P, _I64, _P]),
+  # the interacting (McKean-Vlasov) particle reference: R replicas of N particles (snap_step: a host array); state
+  # [R, N, D], sums [S, R, 3 + D + D D] doubles, pos [S, R, N, D] and hist [S, ny, nx] each or NULL
+  "cnf_mv_particles_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_mv_particles": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.c_float, ctypes.c_double, ctypes.c_double, _I64, ctypes.c_double, _U64, _I64,
+                                      ctypes.c_int32, _I64, _P, ctypes.POINTER(_I64), ctypes.c_int32,
+                                      ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

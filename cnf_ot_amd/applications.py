@@ -951,6 +951,98 @@ def fp_reference_particles(dim, T, a, sigma, subtype, times, n_particles=1 << 20
   return out
 
 
+# ---- the particle reference of the interacting (McKean-Vlasov) fp problem -------------------------------------------
+# d rho / dt = -div(rho (drift - strength grad (W * rho))) + sigma lap rho is the mean-field limit of N particles that
+# feel, beside the drift and the noise, the force of the other N - 1 through the pair kernel W: cnf_mv_particles
+# (include/cnf_ot_amd.h) steps R independent replicas of such a system, the pair force by
+# cnf_interaction's own kernel, the step, stream and statistics cnf_fp_particles'.
+
+def mv_quadratic_ou_variance(t, a, sigma, strength, amp, var0):
+  """Per-coordinate variance at time t of the mean-field limit for the drift "ou" (-a x) and the quadratic kernel
+  W = amp r^2 / 2, started from N(0, var0 I): the force strength amp (x - mean) adds to the drift's pull, so with
+  lam = a + strength amp the variance obeys v' = -2 lam v + 2 sigma: v_inf + (var0 - v_inf) exp(-2 lam t), v_inf =
+  sigma / lam (ou_variance with a -> lam); for lam = 0, var0 + 2 sigma t."""
+  lam = float(a) + float(strength) * float(amp)
+  if lam == 0.0:
+    return var0 + 2.0 * sigma * t
+  v_inf = sigma / lam
+  return v_inf + (var0 - v_inf) * math.exp(-2.0 * lam * t)
+
+
+def mv_reference_particles(dim, T, a, sigma, subtype, interaction, strength, times, n_particles=16384, replicas=2,
+                           h=1e-3, seed=0, var0=None, x0=None, grid=None, axes=(0, 1), positions=False):
+  """The interacting fp problem's density along `times` from `replicas` independent systems of n_particles particles
+    x_i <- x_i + h (drift(x_i) - strength G_i) + sqrt(2 sigma h) z,  G_i = mean_{j != i} grad W(x_i - x_j),
+  drift `subtype` with parameter a as in fp_reference_particles, W the pair kernel of `interaction` (the keyword
+  arguments of utils.interaction_spec), in ONE cnf_mv_particles call: float64 state, the pair force by cnf_interaction's
+  kernel on the float32 rounding of the positions (self mode), two launches per step.  Start, stream and times as
+  fp_reference_particles (global particle r n_particles + i); x0: [replicas, n_particles, dim].  strength = 0 gives
+  fp_reference_particles' paths bit for bit.  A particle that is not finite is counted in `bad` and is not masked out
+  of the pair sums: from the next step on its whole replica is not finite.
+  Returns fp_reference_particles' dictionary over the POOLED replicas (count, bad, mean, cov, times, hist and density
+  with `grid`) and, per replica, energy [S, R] = F = sum_{i != j} W / (2 N (N - 1)) of the step's own pair pass,
+  replica_mean [S, R, D], replica_cov [S, R, D, D], the raw sums [S, R, 3 + D + D D] (their last column: the W sum; the
+  pooled moments are the other columns added over R) and, with positions=True, pos [S, R, N, D].
+  ValueError before any device work for what fp_reference_particles, utils.interaction_spec and
+  utils.interaction_check_shapes refuse, a strength that is not finite, and more than one rank (pairs across ranks need
+  an all-gather of the positions per step)."""
+  name = "mv_reference_particles"
+  if subtype not in _capi.DRIFTS:
+    raise ValueError(f"unknown drift {subtype!r}")
+  dim, N, R = int(dim), int(n_particles), int(replicas)
+  if not 1 <= dim <= 14 or FP_DRIFT_DIM.get(subtype, dim) != dim:
+    raise ValueError(f"{name}: drift {subtype!r} is not defined at dim {dim}")
+  ts, steps = fp_step_indices(times, float(h), T)
+  var0 = fp_initial_variance(T) if var0 is None else float(var0)
+  if not (var0 > 0.0 and math.isfinite(var0)) or not (sigma >= 0.0 and math.isfinite(sigma)) or not math.isfinite(a):
+    raise ValueError(f"{name}: needs var0 > 0, sigma >= 0 and a finite a")
+  if not math.isfinite(float(strength)):
+    raise ValueError(f"{name}: the strength must be finite, not {strength}")
+  spec = ia.interaction_spec(**dict(interaction))
+  ia.interaction_check_shapes((R, N, dim))
+  g = stats_grid(grid, axes, dim)
+  if current_shard().world > 1:
+    raise ValueError(f"{name}: single rank only (pairs across ranks need an all-gather of the positions per step)")
+  if x0 is not None:
+    x0 = torch.as_tensor(x0)
+    if tuple(x0.shape) != (R, N, dim):
+      raise ValueError(f"{name}: x0 must be [{R}, {N}, {dim}], not {tuple(x0.shape)}")
+  u64, off = seed_to_u64(seed)
+  S = len(steps)
+  n_steps = max(int(round(float(T) / float(h))), int(steps[-1]))      # (the stream's stride: fp_reference_particles')
+  if n_steps > 1 << 30 or (off + R * N) > ((1 << 63) - 1) // 4 // (-(-(n_steps + 1) * dim // 4)):
+    raise ValueError(f"{name}: more than 2^30 steps, or the normals' stream index does not fit")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  if x0 is not None:
+    x0 = x0.to(device=dev, dtype=torch.float64).contiguous()
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_mv_particles_workspace(R, N, dim, S, C.byref(nbytes)), "cnf_mv_particles_workspace")
+  f64 = dict(dtype=torch.float64, device=dev)
+  K = 3 + dim + dim * dim
+  ws = torch.empty(-(-nbytes.value // 8), **f64)
+  state, sums = torch.empty(R, N, dim, **f64), torch.empty(S, R, K, **f64)
+  pos = torch.empty(S, R, N, dim, **f64) if positions else None
+  hist = None if g is None else torch.empty(S, g.ny, g.nx, dtype=torch.int32, device=dev)
+  snap = (C.c_int64 * S)(*[int(k) for k in steps])
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_mv_particles(C.byref(spec), float(strength), _capi.DRIFTS[subtype], dim, float(a), float(sigma),
+                                     float(h), n_steps, var0, u64, off, R, N, None if x0 is None else x0.data_ptr(),
+                                     snap, S, None if g is None else C.byref(g), state.data_ptr(),
+                                     None if pos is None else pos.data_ptr(), sums.data_ptr(),
+                                     None if hist is None else hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                     _stream_ptr(dev)), "cnf_mv_particles")
+  out = stats_from_sums(sums[:, :, :K - 1].sum(1), hist, R * N, g, dim)
+  per = stats_from_sums(sums[:, :, :K - 1].reshape(S * R, K - 1), None, N, None, dim)
+  out["times"] = torch.as_tensor(ts, device=dev)
+  out["energy"] = sums[:, :, K - 1] / (2.0 * N * (N - 1.0))
+  out["replica_mean"], out["replica_cov"] = per["mean"].reshape(S, R, dim), per["cov"].reshape(S, R, dim, dim)
+  out["sums"] = sums
+  if positions:
+    out["pos"] = pos
+  return out
+
+
 # ---- importance-sampling diagnostics against the densities known in closed form -------------------------------------
 # The reference's kl_ess (tests/test_fit_prob.py:50-56, "metrics used in the tori paper"): draw y from the flow, weight
 # w = p_target(y) / q_flow(y), report Z = mean w, KL = mean(log q - log p) + log Z, ESS = (sum w)^2 / sum w^2.  It

@@ -16,119 +16,14 @@
 // bit-identical.  Histogram counts go to global memory by no-return integer atomics (order-free).  A workgroup brings
 // FP_CHUNK particles to a snapshot: an LDS-private histogram of nx ny cells would be cleared and flushed for 256
 // increments, so it is not used.
-#include "cnf_terms.h"
-
-#include <math.h>
+#include "cnf_fp_stats.h"
 
 #include <algorithm>
-#include <cmath>
 
 namespace cnf {
 namespace {
 
-constexpr int FP_CHUNK = 256;      // particles per chunk = lanes per workgroup: the unit of the sums' fixed partition
-constexpr int FP_WAVES = FP_CHUNK / 64;
-constexpr int FP_MAX_S = 64;
-constexpr int FP_MAX_D = 14;
 constexpr int64_t FP_MAX_N = int64_t(1) << 31;
-constexpr int64_t FP_MAX_STEPS = int64_t(1) << 30;
-constexpr int64_t FP_MAX_CELLS = int64_t(1) << 24;
-
-__host__ __device__ constexpr int fp_terms(int D) { return 2 + D + D * D; }
-
-// Where the statistics of a snapshot go: partial [S][K][n_chunks] (K = fp_terms(D)), hist [S][ny][nx]
-struct FpStats {
-  double* partial;
-  uint32_t* hist;
-  int64_t n_chunks;
-  double edge_x, edge_y, step_x, step_y;     // edge = lo - step / 2: cell j is centred on lo + j step
-  int32_t nx, ny, axis_x, axis_y;
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// One chunk's contribution to snapshot s: the particle of this lane is x (live: the lane holds one).  Every lane of the
-// workgroup calls this (it synchronises).  A non-finite particle counts as such and enters neither sums nor histogram.
-template <int D>
-__device__ __forceinline__ void fp_accumulate(const double (&x)[D], bool live, int s, int64_t chunk, const FpStats& o,
-                                              double* s_part) {
-  constexpr int K = fp_terms(D);
-  bool finite = live;
-#pragma unroll
-  for (int d = 0; d < D; ++d) finite = finite && isfinite(x[d]);
-  if (o.hist && finite) {
-    double cx = 0.0, cy = 0.0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      if (d == o.axis_x) cx = x[d];
-      if (d == o.axis_y) cy = x[d];
-    }
-    // IEEE float64 division (no reciprocal): the same cell as the float64 restatement
-    const double qx = floor((cx - o.edge_x) / o.step_x), qy = floor((cy - o.edge_y) / o.step_y);
-    if (qx >= 0.0 && qx < (double)o.nx && qy >= 0.0 && qy < (double)o.ny) {
-      const int64_t cell = ((int64_t)s * o.ny + (int64_t)qy) * o.nx + (int64_t)qx;
-      (void)__hip_atomic_fetch_add(o.hist + cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (!o.partial) return;
-  const int wave = (int)threadIdx.x >> 6;
-  const bool lead = (threadIdx.x & 63) == 0;
-  double* mine = s_part + wave * K;
-  double y[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) y[d] = finite ? x[d] : 0.0;
-  const double n_ok = wave_sum(finite ? 1.0 : 0.0), n_bad = wave_sum(live && !finite ? 1.0 : 0.0);
-  if (lead) { mine[0] = n_ok; mine[1] = n_bad; }
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    const double v = wave_sum(y[d]);
-    if (lead) mine[2 + d] = v;
-  }
-#pragma unroll
-  for (int d = 0; d < D; ++d)
-#pragma unroll
-    for (int e = 0; e < D; ++e) {
-      const double v = wave_sum(y[d] * y[e]);
-      if (lead) mine[2 + D + d * D + e] = v;
-    }
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    double v = s_part[threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < FP_WAVES; ++w) v += s_part[w * K + threadIdx.x];
-    o.partial[((int64_t)s * K + threadIdx.x) * o.n_chunks + chunk] = v;
-  }
-  __syncthreads();
-}
-
-// sums[s][k] = the chunks' partials in ascending order, one thread per (s, k)
-__global__ __launch_bounds__(64) void fp_sum_chunks_kernel(const double* partial, int64_t n_chunks, int n_out,
-                                                           double* sums) {
-  const int i = blockIdx.x * 64 + (int)threadIdx.x;
-  if (i >= n_out) return;
-  const double* p = partial + (int64_t)i * n_chunks;
-  double v = 0.0;
-  for (int64_t c = 0; c < n_chunks; ++c) v += p[c];
-  sums[i] = v;
-}
-
-// The lane's walk through its Philox blocks.  The position is the same in every lane of the launch (all particles are
-// at the same step), so the refill branch and the selects are wave-uniform.
-struct NormalWalk {
-  uint64_t seed, blk;
-  float z[4];
-  int e;
-  __device__ __forceinline__ double next() {
-    const int r = e & 3;
-    if (r == 0) philox_normals4(seed, blk++, z);
-    ++e;
-    return (double)(r == 0 ? z[0] : r == 1 ? z[1] : r == 2 ? z[2] : z[3]);
-  }
-};
 
 struct FpArgs {
   uint64_t seed;
@@ -164,7 +59,7 @@ __global__ __launch_bounds__(FP_CHUNK) void fp_particles_kernel(const FpArgs p) 
 #pragma unroll
           for (int d = 0; d < D; ++d) p.pos[((int64_t)si * p.N + i) * D + d] = x[d];
         }
-        fp_accumulate<D>(x, live, si, chunk, p.st, s_part);
+        fp_accumulate<D>(x, live, si, si, chunk, p.st, s_part);
         ++si;
       }
       if (k == last) break;
@@ -198,7 +93,7 @@ __global__ __launch_bounds__(FP_CHUNK) void point_stats_kernel(const PsArgs p) {
     double x[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) x[d] = live ? (double)p.pts[((int64_t)s * p.N + i) * D + d] : 0.0;
-    fp_accumulate<D>(x, live, s, chunk, p.st, s_part);
+    fp_accumulate<D>(x, live, s, s, chunk, p.st, s_part);
   }
 }
 
@@ -239,7 +134,6 @@ struct LaunchStats {
 };
 
 bool fp_shape_ok(int64_t N, int32_t D, int32_t S) { return N >= 1 && N <= FP_MAX_N && D >= 1 && D <= FP_MAX_D && S >= 1 && S <= FP_MAX_S; }
-int64_t fp_chunks(int64_t N) { return (N + FP_CHUNK - 1) / FP_CHUNK; }
 int64_t fp_workspace_bytes(int64_t N, int32_t D, int32_t S) {
   return (int64_t)S * fp_terms(D) * fp_chunks(N) * (int64_t)sizeof(double);
 }
@@ -253,35 +147,7 @@ bool fp_stats_of(int64_t N, int32_t D, int32_t S, const CnfFieldGrid* grid, doub
     if (!workspace || workspace_bytes < fp_workspace_bytes(N, D, S)) return false;
     o->partial = (double*)workspace;
   }
-  if (hist) {
-    if (!grid) return false;
-    const CnfFieldGrid& g = *grid;
-    if (g.nx < 1 || g.ny < 1 || (int64_t)g.nx * g.ny > FP_MAX_CELLS) return false;
-    if (!(g.step_x > 0.0) || !(g.step_y > 0.0) || !std::isfinite(g.step_x) || !std::isfinite(g.step_y) ||
-        !std::isfinite(g.lo_x) || !std::isfinite(g.lo_y))
-      return false;
-    if (g.axis_x < 0 || g.axis_x >= D || g.axis_y < 0 || g.axis_y >= D || g.axis_x == g.axis_y) return false;
-    o->hist = hist;
-    o->edge_x = g.lo_x - g.step_x / 2;
-    o->edge_y = g.lo_y - g.step_y / 2;
-    o->step_x = g.step_x;
-    o->step_y = g.step_y;
-    o->nx = g.nx; o->ny = g.ny; o->axis_x = g.axis_x; o->axis_y = g.axis_y;
-  }
-  return true;
-}
-
-int fp_clear_hist(const FpStats& o, int32_t S, hipStream_t st) {
-  if (!o.hist) return CNF_OK;
-  return hipMemsetAsync(o.hist, 0, (size_t)S * o.nx * o.ny * sizeof(uint32_t), st) == hipSuccess ? CNF_OK : CNF_ERR_HIP;
-}
-
-int fp_finish_sums(const FpStats& o, int32_t D, int32_t S, double* sums, hipStream_t st) {
-  if (!sums) return CNF_OK;
-  const int n_out = S * fp_terms(D);
-  hipLaunchKernelGGL(fp_sum_chunks_kernel, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, st, o.partial, o.n_chunks,
-                     n_out, sums);
-  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+  return fp_hist_of(D, grid, hist, o);
 }
 
 }  // namespace
@@ -302,14 +168,9 @@ extern "C" int cnf_fp_particles(int32_t drift, int32_t D, float a, double sigma,
   if (!fp_shape_ok(N, D, S) || drift < CNF_DRIFT_OU || drift > CNF_DRIFT_LORENZ) return CNF_ERR_INVALID;
   if (((drift == CNF_DRIFT_SMILE || drift == CNF_DRIFT_NONGRADIENT) && D != 2) || (drift == CNF_DRIFT_LORENZ && D != 3))
     return CNF_ERR_INVALID;
-  if (!(h > 0.0) || !std::isfinite(h) || !(var0 > 0.0) || !std::isfinite(var0) || !(sigma >= 0.0) ||
-      !std::isfinite(sigma) || !std::isfinite(a) || n_steps < 0 || n_steps > FP_MAX_STEPS || first_particle < 0)
-    return CNF_ERR_INVALID;
-  if (!snap_step || (!pos && !sums && !hist)) return CNF_ERR_INVALID;
-  for (int32_t s = 0; s < S; ++s)
-    if (snap_step[s] < 0 || snap_step[s] > n_steps || (s > 0 && snap_step[s] <= snap_step[s - 1])) return CNF_ERR_INVALID;
-  const int64_t per_particle = ((n_steps + 1) * D + 3) / 4;        // R / 4
-  if ((first_particle + N) > (INT64_MAX / 4) / per_particle) return CNF_ERR_INVALID;      // the element index fits
+  if (!pos && !sums && !hist) return CNF_ERR_INVALID;
+  int64_t per_particle = 0;
+  if (!fp_run_ok(D, a, sigma, h, n_steps, var0, first_particle, N, snap_step, S, &per_particle)) return CNF_ERR_INVALID;
   FpArgs args{};
   if (!fp_stats_of(N, D, S, grid, sums, hist, workspace, workspace_bytes, &args.st)) return CNF_ERR_INVALID;
   args.seed = seed;
@@ -330,7 +191,7 @@ extern "C" int cnf_fp_particles(int32_t drift, int32_t D, float a, double sigma,
   const unsigned grid_blocks = (unsigned)std::min<int64_t>(args.st.n_chunks, int64_t(1) << 20);
   fp_with_dim(D, LaunchParticles{drift, grid_blocks, st, &args});
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  return fp_finish_sums(args.st, D, S, sums, st);
+  return fp_finish_sums(args.st, S * fp_terms(D), sums, st);
 }
 
 extern "C" int cnf_point_stats(const float* pts, int64_t N, int32_t D, int32_t S, const CnfFieldGrid* grid,
@@ -347,5 +208,5 @@ extern "C" int cnf_point_stats(const float* pts, int64_t N, int32_t D, int32_t S
   const unsigned grid_blocks = (unsigned)std::min<int64_t>(args.st.n_chunks * S, int64_t(1) << 20);
   fp_with_dim(D, LaunchStats{grid_blocks, st, &args});
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  return fp_finish_sums(args.st, D, S, sums, st);
+  return fp_finish_sums(args.st, S * fp_terms(D), sums, st);
 }

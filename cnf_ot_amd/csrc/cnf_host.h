@@ -57,3 +57,20 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
 // ---- cnf_sliced.hip -------------------------------------------------------------------------------------------------
 // sliced_sort_kernel, sliced_merge_kernel, sliced_w2_kernel and the three finish kernels behind cnf_sliced_workspace /
 // cnf_sliced_tile / cnf_sliced_w2 (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).
+
+// ---- cnf_interaction.hip (called by cnf_mv_particles.hip) -----------------------------------------------------------
+// What ia_finish_kernel, or another reader of the pair pass's workspace, needs: row partials [S][P][rows] doubles from
+// the workspace's start, force partials [S][P][rows][D] from double `force_off` on; a row's W sum is cv times its
+// splits added in ascending order, its grad W sum cf times them
+struct IaPairLayout {
+  int32_t P;
+  int64_t force_off;
+  double cv, cf;
+};
+// cnf_interaction's checks of spec and shape and its pair launch (ia_kernel) WITHOUT the finish: the partials of S sets
+// x [S, N, D] (q, Q: query mode) into `workspace` (cnf_interaction_workspace bytes; force: with the force partials) and
+// the layout into *lay.  x == NULL: the checks and the layout alone, nothing enqueued.  CNF_ERR_INVALID as
+// cnf_interaction (nothing enqueued).
+int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x, int64_t N, const float* q, int64_t Q,
+                      int32_t D, bool force, void* workspace, int64_t workspace_bytes, hipStream_t stream,
+                      IaPairLayout* lay);

@@ -19,6 +19,7 @@
 // Each (split, row) writes one double (and D doubles of force) to the workspace; ia_finish_kernel adds a row's splits
 // in ascending order -- that is pot and force -- then the rows in a fixed strided order and a fixed tree -- that is
 // sums: bitwise reproducible, and every workspace word it reads was written by this call.  P depends on the sizes alone.
+#include "cnf_host.h"
 #include "cnf_terms.h"
 
 #include <math.h>
@@ -335,29 +336,45 @@ extern "C" int cnf_interaction_splits(int32_t S, int64_t N, int64_t Q, int32_t D
   return ia_shape_ok(S, N, Q, D) ? ia_splits(S, Q > 0 ? Q : N, N) : CNF_ERR_INVALID;
 }
 
+int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x, int64_t N, const float* q, int64_t Q,
+                      int32_t D, bool force, void* workspace, int64_t workspace_bytes, hipStream_t stream,
+                      IaPairLayout* lay) {
+  if (!spec || !lay || !ia_shape_ok(S, N, Q, D)) return CNF_ERR_INVALID;
+  IaLaunch a{};
+  if (!ia_coef(spec, &a.k)) return CNF_ERR_INVALID;
+  a.force = force;
+  a.rows = Q > 0 ? Q : N;
+  a.P = ia_splits(S, a.rows, N);
+  a.force_off = ia_row_doubles(S, a.rows, a.P);
+  const bool quad = spec->kind == CNF_INTERACTION_QUADRATIC;
+  lay->P = a.P;
+  lay->force_off = a.force_off;
+  lay->cv = quad ? 0.5 * (double)spec->amp[0] : 1.0;
+  lay->cf = quad ? (double)spec->amp[0] : 1.0;
+  if (!x) return CNF_OK;
+  if (!workspace || workspace_bytes < ia_workspace_doubles(S, a.rows, N, D, a.force) * (int64_t)sizeof(double))
+    return CNF_ERR_INVALID;
+  a.grid = dim3((unsigned)(row_groups(a.rows) * a.P), (unsigned)S);
+  a.st = stream;
+  a.x = x; a.q = q; a.N = N;
+  a.ws = (double*)workspace;
+  ia_launch_dim(D, spec->kind, a);
+  return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
+}
+
 extern "C" int cnf_interaction(const CnfInteractionSpec* spec, int32_t S, const float* x, int64_t N, const float* q,
                                int64_t Q, int32_t D, double* sums, float* pot, float* force, void* workspace,
                                int64_t workspace_bytes, void* stream) {
   if (!spec || !x || !sums || !workspace || !ia_shape_ok(S, N, Q, D)) return CNF_ERR_INVALID;
   if ((q == nullptr) != (Q == 0)) return CNF_ERR_INVALID;
-  IaLaunch a{};
-  if (!ia_coef(spec, &a.k)) return CNF_ERR_INVALID;
-  a.force = force != nullptr;
-  a.rows = Q > 0 ? Q : N;
-  if (workspace_bytes < ia_workspace_doubles(S, a.rows, N, D, a.force) * (int64_t)sizeof(double)) return CNF_ERR_INVALID;
-  a.P = ia_splits(S, a.rows, N);
-  a.grid = dim3((unsigned)(row_groups(a.rows) * a.P), (unsigned)S);
-  a.st = (hipStream_t)stream;
-  a.x = x; a.q = q; a.N = N;
-  a.ws = (double*)workspace;
-  a.force_off = ia_row_doubles(S, a.rows, a.P);
-  ia_launch_dim(D, spec->kind, a);
-  if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
-  const bool quad = spec->kind == CNF_INTERACTION_QUADRATIC;
-  const double cv = quad ? 0.5 * (double)spec->amp[0] : 1.0, cf = quad ? (double)spec->amp[0] : 1.0;
+  hipStream_t st = (hipStream_t)stream;
+  IaPairLayout lay{};
+  const int rc = interaction_pairs(spec, S, x, N, q, Q, D, force != nullptr, workspace, workspace_bytes, st, &lay);
+  if (rc != CNF_OK) return rc;
+  const int64_t rows = Q > 0 ? Q : N;
   const double inv_n = 1.0 / (double)(Q > 0 ? N : N - 1);
-  const int64_t force_wgs = a.force ? ((int64_t)S * a.rows * D + IA_THREADS - 1) / IA_THREADS : 0;
-  hipLaunchKernelGGL(ia_finish_kernel, dim3((unsigned)(S + force_wgs)), dim3(IA_THREADS), 0, a.st, (const double*)a.ws, S,
-                     a.rows, D, a.P, a.force_off, cv, cf, inv_n, sums, pot, force);
+  const int64_t force_wgs = force ? ((int64_t)S * rows * D + IA_THREADS - 1) / IA_THREADS : 0;
+  hipLaunchKernelGGL(ia_finish_kernel, dim3((unsigned)(S + force_wgs)), dim3(IA_THREADS), 0, st, (const double*)workspace,
+                     S, rows, D, lay.P, lay.force_off, lay.cv, lay.cf, inv_n, sums, pot, force);
   return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }

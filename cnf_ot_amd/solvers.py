@@ -625,7 +625,8 @@ def evaluate_interaction(config, model: FlowModel, params: Params, times=None, n
   and running_cost = strength * the trapezoid rule of `energy` over `times` (what the training term estimates by
   strength T mean_t F), kind, strength and n (the points per set).  The 2 x len(times) sets are ONE cnf_interaction
   call (up to 32 times).  ValueError, before any device work, for kind "none", n < 4 and what utils.interaction_spec and
-  utils.interaction_check_shapes refuse."""
+  utils.interaction_check_shapes refuse.  For an fp configuration with an interaction, evaluate_mv_reference gives the
+  interacting particle system's own F(t), the ground truth of such a problem."""
   kind = _interaction_kind(config)
   if kind == "none":
     raise ValueError("evaluate_interaction: the config's interaction kind is 'none'")
@@ -660,6 +661,71 @@ def print_interaction(res: Dict[str, Any]) -> None:
   for i, row in enumerate(zip(res["times"], res["energy"], res["floor"])):
     print("  {:.4f} | {:.6e} | {:.2e}".format(*row) + (" | {:.6e}".format(res["trace_cov"][i]) if quad else ""))
   print("running cost strength * int F dt (strength {}): {:.6e}".format(res["strength"], res["running_cost"]))
+
+
+# ---- the particle reference of an fp problem with an interaction: what an interacting training term would be held to ---
+
+MV_REFERENCE_KEYS = ("times", "mean", "trace_cov", "free_mean", "free_trace_cov", "trace_cov_floor", "energy",
+                     "energy_floor", "bad", "trace_cov_exact", "kind", "strength", "n", "replicas")
+
+
+def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1e-3, seed=0) -> Dict[str, Any]:
+  """The ground truth of an fp configuration whose `interaction` section has a kind: the interacting particle system
+  of applications.mv_reference_particles (`replicas` systems of n_particles, step h, the config's drift, sigma and
+  kernel, strength as the force's factor) whose law converges to d rho / dt = -div(rho (drift - strength grad(W * rho)))
+  + sigma lap rho.  It takes no model: bind_loss refuses this configuration (there is no interacting training term
+  yet), so `main` has no flag for it.  Per time of `times` (default: the figure's, rounded to multiples of h), lists:
+    times
+    mean, trace_cov            of the interacting ensemble, pooled over the replicas (mean: [D] per time)
+    free_mean, free_trace_cov  the same of applications.fp_reference_particles with the same seed and
+                               replicas * n_particles particles: the same normals without the force -- what the
+                               interaction does
+    trace_cov_floor            the largest replica-to-replica difference of tr cov
+    energy, energy_floor       F(t), the mean over the replicas of the interaction energy, and its largest
+                               replica-to-replica difference: the Monte-Carlo and finite-N level of both
+    bad                        particles that were not finite
+    trace_cov_exact            drift ou with the quadratic kernel: dim * applications.mv_quadratic_ou_variance, the
+                               mean-field limit (the ensemble's h-bias and 1 / N are not in it); else None
+  and kind, strength, n (particles per replica), replicas.  ValueError, before any device work, for what _fp_prelude
+  refuses, an interaction kind "none", fewer than 2 replicas and what mv_reference_particles refuses."""
+  name = "evaluate_mv_reference"
+  st, ts, n_particles, (dim, T, a, sigma, sub) = _fp_prelude(name, config, times, n_particles, h, 2)
+  kind = _interaction_kind(config)
+  if kind == "none":
+    raise ValueError(f"{name}: defined for fp with an interaction kind, not 'none'")
+  replicas = int(replicas)
+  if replicas < 2:
+    raise ValueError(f"{name}: needs replicas >= 2 (the floors compare them), not {replicas}")
+  kw, strength = _interaction_kwargs(config), float(config["interaction"]["strength"])
+  mv = applications.mv_reference_particles(dim, T, a, sigma, sub, kw, strength, ts, n_particles, replicas, h, seed)
+  free = applications.fp_reference_particles(dim, T, a, sigma, sub, ts, replicas * n_particles, h, seed)
+  tr = lambda cov: cov.diagonal(dim1=-2, dim2=-1).sum(-1)
+  rep_tr, F = tr(mv["replica_cov"]), mv["energy"]
+  exact = None
+  if sub == "ou" and kind == "quadratic":
+    amp = float(np.float32(kw["amplitudes"][0] if kw["amplitudes"] is not None else 1.0))
+    var0 = applications.fp_initial_variance(T)
+    exact = [dim * applications.mv_quadratic_ou_variance(float(t), a, sigma, strength, amp, var0) for t in ts]
+  return {"times": [float(t) for t in ts],
+          "mean": mv["mean"].tolist(), "trace_cov": tr(mv["cov"]).tolist(),
+          "free_mean": free["mean"].tolist(), "free_trace_cov": tr(free["cov"]).tolist(),
+          "trace_cov_floor": (rep_tr.max(1).values - rep_tr.min(1).values).tolist(),
+          "energy": F.mean(1).tolist(), "energy_floor": (F.max(1).values - F.min(1).values).tolist(),
+          "bad": mv["bad"].tolist(), "trace_cov_exact": exact,
+          "kind": kind, "strength": strength, "n": n_particles, "replicas": replicas}
+
+
+def print_mv_reference(res: Dict[str, Any]) -> None:
+  """evaluate_mv_reference's table, one line per time"""
+  exact = res["trace_cov_exact"] is not None
+  print("interacting particle reference ({} kernel, strength {}, {} replicas of {}):  t | |mean| | tr cov | floor | "
+        "tr cov without the force | F | floor | bad{}".format(res["kind"], res["strength"], res["replicas"], res["n"],
+                                                              " | tr cov, mean-field limit" if exact else ""))
+  for i, t in enumerate(res["times"]):
+    print("  {:.4f} | {:.3e} | {:.6f} | {:.2e} | {:.6f} | {:.6e} | {:.2e} | {:.0f}".format(
+      t, float(np.linalg.norm(res["mean"][i])), res["trace_cov"][i], res["trace_cov_floor"][i],
+      res["free_trace_cov"][i], res["energy"][i], res["energy_floor"][i], res["bad"][i])
+      + (" | {:.6f}".format(res["trace_cov_exact"][i]) if exact else ""))
 
 
 # ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------

@@ -961,6 +961,49 @@ int cnf_interaction(const CnfInteractionSpec *spec, int32_t S, const float *x, i
                     const float *q, int64_t Q, int32_t D, double *sums, float *pot, float *force,
                     void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- a particle reference for the interacting (McKean-Vlasov) Fokker-Planck equation --------------------------------
+ *   d rho / dt = -div(rho (drift - kappa grad (W * rho))) + sigma lap rho
+ * (aggregation-diffusion, crowd aversion, swarming: the forward half of a mean-field game).  It replaces a loop of one
+ * cnf_interaction call in query mode plus a composed float64 update per step, and is the ground truth an interacting
+ * fp training term would be held to.  R independent replicas of N particles of dimension D, replica r particle i:
+ *   x_i <- x_i + h (drift(x_i) - kappa G_i) + sqrt(2 sigma h) z,   G_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j)
+ * State and update are float64, drift as in cnf_fp_particles; per coordinate v = fma(-kappa, G_d, drift_d),
+ * xn_d = fma(h, v, x_d) for every d from the OLD x, then x_d = fma(sqrt(2 sigma h), z, xn_d): kappa = 0 is
+ * cnf_fp_particles' step bit for bit.  The pair force is formed exactly as cnf_interaction forms it in self mode, by
+ * the same kernel, on the float32 rounding of the current positions (a replica is one of its sets, so replicas never
+ * interact; the pair i == j is skipped by index); then G_d = (cf (split 0 + split 1 + ...)) / (N - 1) in double, cf =
+ * amp_0 for the quadratic kind and 1 otherwise, with NO float32 rounding of the force in between.
+ * Normals: cnf_fp_particles' stream layout with global particle p = first_particle + r N + i.
+ * snap_step [S] as in cnf_fp_particles; nothing is integrated past the last snapshot.  Outputs (device), overwritten:
+ *   state [R, N, D]              double, required: the positions, advanced in place; on return those of the last snapshot
+ *   sums  [S, R, 3 + D + D D]    double, required: per snapshot and replica the number of finite particles, of
+ *                                non-finite ones, sum x_d, sum x_d x_e, and sum_i sum_{j != i} W(x_i - x_j) over the
+ *                                finite i from that step's pair pass (double row partials): F = last / (2 N (N - 1))
+ *   pos   [S, R, N, D]           double or NULL
+ *   hist  [S, ny, nx]            uint32 or NULL: counts on `grid` pooled over the replicas, as cnf_fp_particles'
+ * The sums go over a fixed partition into chunks of 256 particles WITHIN a replica, the chunks' partials added in
+ * ascending order: two calls are bit-identical, and one call with R replicas equals R calls with one (first_particle
+ * moved by N each).  A particle that is not finite is counted as such at snapshots and is NOT masked out of the pair
+ * pass: every force of its own replica is non-finite one step later (and the replica's W sum from the same step on).
+ * Each step is two launches on `stream` (the pair pass, then the step kernel, ordered by the stream alone; the last
+ * snapshot's pair pass computes no force) after one that draws the start, and one that adds the chunks' partials at
+ * the end.  x0 [R, N, D] (device, double; optional) replaces the drawn start.
+ * The caller passes `state`; `workspace` (cnf_mv_particles_workspace(R, N, D, S) bytes, 8-byte aligned) holds the pair
+ * partials, the chunks' partials and the float32 mirror of the state: no allocation, no synchronisation.
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: every refusal of cnf_fp_particles (drift, D, h, var0, sigma,
+ * a, n_steps, first_particle, S, snapshot steps, hist and its grid; a drift defined at another D) and of
+ * cnf_interaction (a NULL or bad spec, D outside 1..14, N outside 2..2^20, R outside 1..64); a kappa that is not
+ * finite; a NULL state, sums or workspace or a workspace that is too small; a stream element index
+ * (first_particle + R N) (n_steps + 1) D, rounded up, that would not fit in 63 bits.
+ * Out of scope: more than one rank, weighted particles, kernels singular at 0, float64 pair forces, N > 2^20. */
+int cnf_mv_particles_workspace(int32_t R, int64_t N, int32_t D, int32_t S, int64_t *bytes);
+int cnf_mv_particles(const CnfInteractionSpec *spec, double kappa, int32_t drift, int32_t D, float a,
+                     double sigma, double h, int64_t n_steps, double var0, uint64_t seed,
+                     int64_t first_particle, int32_t R, int64_t N, const double *x0,
+                     const int64_t *snap_step, int32_t S, const CnfFieldGrid *grid, double *state,
+                     double *pos, double *sums, uint32_t *hist, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
