@@ -135,6 +135,9 @@ SYMBOLS = {
                                       ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _I64, _P]),
   "cnf_score_residual": (ctypes.c_int, [_P, _P, _I64, _I64, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
+  "cnf_score_residual_force": (ctypes.c_int, [_P, _P, _P, ctypes.c_float, _I64, _I64, ctypes.c_int32, ctypes.c_float,
+                                              ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P,
+                                              _P]),
   "cnf_term_residual": (ctypes.c_int, [ctypes.c_int32, _P, _P, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                        ctypes.c_float, _P, _P, _P, _P]),
   "cnf_rkl_residual": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -208,6 +211,10 @@ SYMBOLS = {
   "cnf_interaction_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_interaction": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32,
                                      _P, _P, _P, _P, _I64, _P]),
+  # the vector-Jacobian product of the self-mode force: x, g, xbar [S, N, D]
+  "cnf_interaction_vjp_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_interaction_vjp": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P,
+                                         _P, _I64, _P]),
   # the interacting (McKean-Vlasov) particle reference: R replicas of N particles (snap_step: a host array); state
   # [R, N, D], sums [S, R, 3 + D + D D] doubles, pos [S, R, N, D] and hist [S, ny, nx] each or NULL
   "cnf_mv_particles_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),

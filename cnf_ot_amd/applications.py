@@ -470,13 +470,18 @@ UNFUSED_SCORE_MIN_DIM = 6
 UNFUSED_RKL_MAX_BATCH = 131072
 
 
-def _score_terms_unfused(ctx, conds, batch_size, dt, dx, coef_score, loss_coef, drift=-1, a=0.0):
+def _score_terms_unfused(ctx, conds, batch_size, dt, dx, coef_score, loss_coef, drift=-1, a=0.0, interaction=None):
   """per-slice sums of  sum_d ((r2-r1)/dt + coef_score * score_d(r3) - drift_d(r3))^2  from three launches:
   ONE base -> data pass over the 3 x S x count points (conditions t -+ dt/2 and t; at this size the
   wave-per-dimension kernel), ONE central-difference score launch over the S x count points r3 (its 2 D
   evaluation points per sample exist only inside the kernel) and ONE epilogue (cnf_score_residual).  With ctx.grad
   the epilogue also emits the adjoints, and two backward launches (cnf_logprob_fd_vjp, cnf_pass_vjp) accumulate
-  the parameter gradient -- the reverse sweep written out by hand: no autograd graph, a dozen host calls."""
+  the parameter gradient -- the reverse sweep written out by hand: no autograd graph, a dozen host calls.
+  interaction = (spec, strength): the residual gains strength * f(r3), f the self-mode interaction force of each time's
+  `count` samples (ONE cnf_interaction call per 64 times, between the forward pass and the score launch); the epilogue
+  is cnf_score_residual_force, and its fbar goes through ONE cnf_interaction_vjp call per 64 times (the pair Hessian of
+  W against fbar) into the adjoint of r3, before cnf_logprob_fd_vjp.  Always this composed route: the launch that fuses
+  value and backward has no force."""
   be = ctx.be
   z, _, count = ctx.noise(batch_size)
   S = _n_conds(conds)
@@ -490,6 +495,19 @@ def _score_terms_unfused(ctx, conds, batch_size, dt, dx, coef_score, loss_coef, 
   z3 = z.repeat(3 * S, 1)                                     # the same draw for every slice and condition
   want = ctx.grad is not None
   r, _ = be.forward_logdet(z3, c3, want_logdet=False)
+  if interaction is not None:
+    ia_spec, strength = interaction
+    r3 = r[2 * n:]
+    sets = r3.view(S, count, -1)
+    force = ia.force_of_sets(ia_spec, sets).view(n, -1)
+    score = be.logprob_fd(r3, tt, dx)
+    sums, rbar, sbar, fbar = be.score_residual_force(r, score, force, strength, count, dt, coef_score, drift, a, loss_coef,
+                                                     want)
+    if want:
+      rbar[2 * n:] += ia.force_vjp_of_sets(ia_spec, sets, fbar.view(S, count, -1)).view(n, -1)
+      rbar[2 * n:] += be.logprob_fd_vjp(r3, tt, dx, sbar, ctx.grad)
+      ctx.defer_pass_vjp(z3, _cat_conds([th - half, th + half, th]), count, rbar, None)
+    return sums
   if want and drift in (-1, _capi.DRIFTS["ou"]):
     # value AND backward of the score term in one launch: the kernel that differentiates the 2 D evaluation points
     # forms the score from its own forward passes (no separate forward launch over them)
@@ -534,7 +552,7 @@ def _kinetic_score_sum(ctx, beta, dt, dx, conds, batch_size, coef):
   return ctx.terms(_spec(_capi.TERM_KINETIC_SCORE, dt=dt, dx=dx, coef=1.0 / beta), z, conds, count, coef)
 
 
-def _flow_matching_sum(ctx, dim, a, sigma, subtype, conds, batch_size, coef):
+def _flow_matching_check(dim, subtype):
   if subtype not in _capi.DRIFTS:
     raise ValueError(f"unknown velocity field {subtype!r}")
   if subtype in ("nongradient",) and dim != 2:
@@ -544,7 +562,13 @@ def _flow_matching_sum(ctx, dim, a, sigma, subtype, conds, batch_size, coef):
   if subtype == "gradient" and dim != 2:
     raise ValueError("the reference's 'gradient' target is a 2-D field (applications.py:353-357); "
                      "use subtype='ou' for the documented drift -a*r in other dimensions")
+
+
+def _flow_matching_sum(ctx, dim, a, sigma, subtype, conds, batch_size, coef, interaction=None):
+  _flow_matching_check(dim, subtype)
   z, _, count = ctx.noise(batch_size)
+  if interaction is not None:      # (the composed route at every dimension and for every drift)
+    return _score_terms_unfused(ctx, conds, batch_size, 0.01, 0.01, sigma, coef, _capi.DRIFTS[subtype], a, interaction)
   if _use_unfused(ctx, dim) and subtype in ("ou", "lorenz"):
     return _score_terms_unfused(ctx, conds, batch_size, 0.01, 0.01, sigma, coef, _capi.DRIFTS[subtype], a)
   # dt and dx are overridden to 0.01 inside the reference function (:286,301)
@@ -1424,14 +1448,30 @@ def rwpo_loss_fn(model, dim, T, beta, dt, dx, t_batch_size, subtype, a, params, 
 
 
 def fp_loss_fn(model, dim, T, a, sigma, dt, dx, t_batch_size, subtype, params, rng, _lambda, batch_size,
-               shard=None, grad=None):
-  """applications.py:424-441 (beta = 4: the initial Gaussian has variance 1, :432)"""
+               shard=None, grad=None, interaction=None):
+  """applications.py:424-441 (beta = 4: the initial Gaussian has variance 1, :432).  interaction=(spec_kwargs, strength):
+  the interacting (McKean-Vlasov) problem d rho / dt = -div(rho (drift - strength grad (W * rho))) + sigma lap rho, whose
+  particle form is mv_reference_particles: the flow-matching residual gains strength * f, f the self-mode force of the
+  batch_size // 32 samples of each time (utils.interaction_energy's, spec_kwargs: utils.interaction_spec's arguments).
+  The force sits inside the square, so its backward is the pair-Hessian pass cnf_interaction_vjp; the term takes the
+  composed route at every dimension (`_score_terms_unfused`).  The gradient is the exact one of the discrete objective
+  (for the exponential kind in dimension 1 it has no delta term from the kink of W).  Eager, single rank, the HIP engine
+  as the terms backend: ValueError otherwise, before any device work.  None: the code as it was."""
+  if interaction is not None:
+    ia_spec, ia_strength = _interaction_refuse("fp_loss_fn", interaction, rng, shard, batch_size // 32, dim)
+    ia.interaction_vjp_check_spec(ia_spec)
+    if not np.isfinite(ia_strength):
+      raise ValueError(f"fp_loss_fn: the interaction's strength must be finite, not {ia_strength}")
+    _flow_matching_check(dim, subtype)
   ctx = _Ctx(model, params, rng, shard, grad)
+  if interaction is not None and not ctx.hip:
+    raise ValueError(f"fp_loss_fn: an interaction term needs the HIP engine as the terms backend, not {type(ctx.be).__name__}")
   t_batch = draw_t_batch(rng, t_batch_size, T)
   sub = batch_size // 32
   c_rkl, c_fm = _lambda / batch_size, 0.5 * T / (sub * t_batch_size)
+  given = None if interaction is None else (ia_spec, ia_strength)
   return ctx.combine([_reverse_kl_sum(ctx, T, 4.0, 0.0, batch_size, c_rkl),
-                      _flow_matching_sum(ctx, dim, a, sigma, subtype, t_batch, sub, c_fm)], [c_rkl, c_fm])
+                      _flow_matching_sum(ctx, dim, a, sigma, subtype, t_batch, sub, c_fm, given)], [c_rkl, c_fm])
 
 
 def value_and_grad(loss_fn):

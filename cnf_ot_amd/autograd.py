@@ -170,3 +170,35 @@ def interaction_energy(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=N
   kernel's amplitudes and bandwidths are constants.  With `flow_forward` a flow trains on the energy through ordinary
   autograd (applications.interaction_loss_fn is the hand-written fast path)."""
   return _InteractionEnergy.apply(x, kind, amplitudes, bandwidths)
+
+
+class _InteractionForce(torch.autograd.Function):
+  """The self-mode force of point sets: forward is cnf_interaction's force, backward cnf_interaction_vjp on the incoming
+  adjoint."""
+
+  @staticmethod
+  def forward(ctx, x, kind, amplitudes, bandwidths):
+    x3 = interaction._sets("interaction", x, "x")
+    interaction.interaction_check_shapes((min(x3.shape[0], _capi.MMD_MAX_SETS),) + tuple(x3.shape[1:]))
+    spec = interaction.interaction_vjp_check_spec(interaction.interaction_spec(kind, amplitudes, bandwidths))
+    _, one, (x3, _) = interaction._stage(x, x3, x3[:, :0])
+    ctx.spec, ctx.one = spec, one
+    ctx.save_for_backward(x3)
+    return interaction._unstack(interaction.force_of_sets(spec, x3), one)
+
+  @staticmethod
+  def backward(ctx, fbar):
+    x3, = ctx.saved_tensors
+    g3 = fbar.detach().to(device=x3.device, dtype=torch.float32).reshape(x3.shape).contiguous()
+    return interaction._unstack(interaction.force_vjp_of_sets(ctx.spec, x3, g3), ctx.one), None, None, None
+
+
+def interaction_force(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None):
+  """The mean-field force f_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j) of the sample sets x [N, D] or [S, N, D]
+  (cnf_interaction in self mode; the pair kernel of utils.interaction_spec), float32 of x's shape, differentiable in x:
+  backward is ONE cnf_interaction_vjp call per 64 sets (utils.interaction_force_vjp) -- the second pair sum, with the
+  pair Hessian of W, that a loss needs when the force sits inside a square, as in the interacting Fokker-Planck residual
+  (applications.fp_loss_fn(interaction=...) is the hand-written fast path).  The backward is the exact gradient of the
+  discrete force: for the exponential kind in dimension 1 it does not contain the delta term of the kink of W at 0.
+  The kernel's amplitudes and bandwidths are constants."""
+  return _InteractionForce.apply(x, kind, amplitudes, bandwidths)

@@ -74,3 +74,8 @@ struct IaPairLayout {
 int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x, int64_t N, const float* q, int64_t Q,
                       int32_t D, bool force, void* workspace, int64_t workspace_bytes, hipStream_t stream,
                       IaPairLayout* lay);
+
+// ---- cnf_interaction_vjp.hip ------------------------------------------------------------------------------------------
+// iv_kernel and iv_finish_kernel behind cnf_interaction_vjp_workspace / cnf_interaction_vjp (include/cnf_ot_amd.h).
+// Model-free: the unit calls into no other and none calls into it; it shares cnf_interaction_pairs.h (the workgroup's
+// geometry, the column splits, the spec and shape checks) with cnf_interaction.hip.

@@ -68,9 +68,14 @@ struct ResidArgs {
   int64_t n, count;
   int32_t D, subtype;    // subtype < 0: no drift (kinetic_with_score), else CnfDrift
   float inv_dt, coef, a, loss_coef;
+  const float* force;    // [n, D]: an interaction force at r3, or null (FORCE instantiation alone reads the three)
+  float* fbar;           // [n, D] or null
+  float strength;
 };
 
-// sum_d ((r2 - r1)/dt + coef score_d - drift_d(r3))^2 per slice (applications.py:245-374) and its adjoints
+// sum_d ((r2 - r1)/dt + coef score_d - drift_d(r3))^2 per slice (applications.py:245-374) and its adjoints.  FORCE:
+// u gains strength * force_d (the interacting Fokker-Planck residual) and fbar = strength * u_bar leaves with the rest
+template <bool FORCE>
 __global__ __launch_bounds__(256) void score_residual_kernel(const ResidArgs a) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int D = a.D;
@@ -89,10 +94,12 @@ __global__ __launch_bounds__(256) void score_residual_kernel(const ResidArgs a) 
     float ub0 = 0.f, ub1 = 0.f, ub2 = 0.f;
     for (int d = 0; d < D; ++d) {
       const float drift = ou ? ou_drift(r3[d], a.a) : drift_field<float>(r, d, a.subtype, a.a);
-      const float u = score_residual((r2[d] - r1[d]) * a.inv_dt, sc[d], a.coef, drift);
+      float u = score_residual((r2[d] - r1[d]) * a.inv_dt, sc[d], a.coef, drift);
+      if constexpr (FORCE) u = fmaf(a.strength, a.force[i * D + d], u);
       acc = fmaf(u, u, acc);
       if (a.rbar) {
         const float ub = score_residual_bar(u, a.loss_coef);
+        if constexpr (FORCE) a.fbar[i * D + d] = a.strength * ub;
         a.rbar[i * D + d] = -ub * a.inv_dt;
         a.rbar[(a.n + i) * D + d] = ub * a.inv_dt;
         a.sbar[i * D + d] = a.coef * ub;
@@ -326,7 +333,25 @@ extern "C" int cnf_score_residual(const float* r, const float* score, int64_t n,
   ResidArgs a;
   a.r = r; a.score = score; a.rbar = rbar; a.sbar = sbar; a.sums = sums; a.n = n; a.count = count;
   a.D = D; a.subtype = drift; a.inv_dt = 1.0f / dt; a.coef = coef; a.a = a_; a.loss_coef = loss_coef;
-  return launch_plain(score_residual_kernel, (n + 255) / 256, 256, 0, stream, a);
+  a.force = nullptr; a.fbar = nullptr; a.strength = 0.0f;
+  return launch_plain(score_residual_kernel<false>, (n + 255) / 256, 256, 0, stream, a);
+}
+
+extern "C" int cnf_score_residual_force(const float* r, const float* score, const float* force, float strength, int64_t n,
+                                        int64_t count, int32_t D, float dt, float coef, int32_t drift, float a_,
+                                        float loss_coef, double* sums, float* rbar, float* sbar, float* fbar,
+                                        void* stream_) {
+  if (!r || !score || !force || !sums || n < 0 || count < 1 || D < 1 || !(dt > 0.f) ||
+      (rbar == nullptr) != (sbar == nullptr) || (rbar == nullptr) != (fbar == nullptr))
+    return CNF_ERR_INVALID;
+  if (drift != -1 && !drift_ok(drift, D)) return CNF_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int todo = zero_sums(sums, (n + count - 1) / count, n, stream); todo <= 0) return todo;
+  ResidArgs a;
+  a.r = r; a.score = score; a.rbar = rbar; a.sbar = sbar; a.sums = sums; a.n = n; a.count = count;
+  a.D = D; a.subtype = drift; a.inv_dt = 1.0f / dt; a.coef = coef; a.a = a_; a.loss_coef = loss_coef;
+  a.force = force; a.fbar = fbar; a.strength = strength;
+  return launch_plain(score_residual_kernel<true>, (n + 255) / 256, 256, 0, stream, a);
 }
 
 // (cnf_host.h.  The float2 kernel where the points allow it: cnf_kinetic_potential_vjp's, 16-byte aligned, always do.)

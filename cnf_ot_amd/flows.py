@@ -887,6 +887,25 @@ class FlowEngine:
                                               _stream_ptr(self.device)), "cnf_score_residual")
     return sums, rbar, sbar
 
+  def score_residual_force(self, r, score, force, strength: float, count: int, dt: float, coef: float, drift: int,
+                           a: float, loss_coef: float = 0.0, want_adjoints: bool = False):
+    """cnf_score_residual_force: `score_residual` with strength * force [n, D] (the interaction force at r3) inside the
+    square; with want_adjoints also (rbar [3n, D], sbar [n, D], fbar [n, D] = the force's adjoint)."""
+    n, D = score.shape
+    if tuple(force.shape) != (n, D) or force.dtype != torch.float32 or not force.is_contiguous():
+      raise ValueError(f"score_residual_force: force must be contiguous float32 {(n, D)}, not {tuple(force.shape)}")
+    sums = torch.empty(-(-n // count), dtype=torch.float64, device=self.device)
+    rbar = torch.empty_like(r) if want_adjoints else None
+    sbar = torch.empty_like(score) if want_adjoints else None
+    fbar = torch.empty_like(score) if want_adjoints else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with _OnDevice(self.device):
+      _capi.check(self.lib.cnf_score_residual_force(r.data_ptr(), score.data_ptr(), force.data_ptr(), float(strength), n,
+                                                    count, D, float(dt), float(coef), int(drift), float(a),
+                                                    float(loss_coef), sums.data_ptr(), ptr(rbar), ptr(sbar), ptr(fbar),
+                                                    _stream_ptr(self.device)), "cnf_score_residual_force")
+    return sums, rbar, sbar, fbar
+
   def term_residual(self, kind: int, r, aux, count: int, subtype: int = 0, p0: float = 0.0, loss_coef: float = 0.0,
                     want_adjoints: bool = True, rbar_out=None):
     """cnf_term_residual: per-slice sums (float64) of a kinetic / potential / density-fit term from the outputs of

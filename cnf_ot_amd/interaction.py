@@ -2,8 +2,9 @@
 local in the density: F[rho] = 1/2 int int W(x - y) rho(x) rho(y) dx dy on samples, its first variation W * rho (a
 field) and its Wasserstein gradient grad (W * rho) (a force), for a signed Gaussian, exponential (Morse) or quadratic
 pair kernel W(|x - y|).  One fused call over all sets (cnf_interaction); composed in torch the same
-double sum materialises an N x N matrix per set and its backward.  What surrounds a call is `two_sample`'s.  `utils`
-re-exports the public names.
+double sum materialises an N x N matrix per set and its backward.  `interaction_force_vjp` is the backward of the force
+itself (cnf_interaction_vjp): what a loss needs that has the force inside a square, as the interacting
+Fokker-Planck residual does.  What surrounds a call is `two_sample`'s.  `utils` re-exports the public names.
 """
 import numpy as np
 import torch
@@ -138,3 +139,62 @@ def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, w
   if want_force:
     out["force"] = _unstack(force, one)
   return out
+
+
+# ---- the force's vector-Jacobian product: what a loss with the force inside a square differentiates through ----------
+
+def interaction_vjp_check_spec(spec):
+  """ValueError for what cnf_interaction_vjp refuses in a spec that `interaction_spec` accepted: a pair-Hessian
+  coefficient amp / bw^4 (Gaussian) or amp / bw^2 (exponential) outside float32's range."""
+  if spec.kind == _capi.INTERACTION_KINDS["quadratic"]:
+    return spec
+  power = 4 if spec.kind == _capi.INTERACTION_KINDS["gaussian"] else 2
+  for b in range(spec.n_terms):
+    if not abs(float(spec.amp[b]) / float(spec.bw[b]) ** power) <= 3.4028234663852886e38:
+      raise ValueError(f"interaction: amplitude / bandwidth^{power} (the pair Hessian's coefficient) leaves float32's "
+                       f"range: {float(spec.amp[b])}, {float(spec.bw[b])}")
+  return spec
+
+
+def _vjp_call(spec, x3, g3):
+  """ONE cnf_interaction_vjp call on staged tensors: xbar [S, N, D]."""
+  S, N, D = x3.shape
+  dev = x3.device
+  ws = _workspace(dev, _workspace_bytes("cnf_interaction_vjp_workspace", S, N, D))
+  xbar = torch.empty(S, N, D, dtype=torch.float32, device=dev)
+  with _OnDevice(dev):
+    _capi.check(_capi.lib().cnf_interaction_vjp(_capi.ctypes.byref(spec), S, x3.data_ptr(), g3.data_ptr(), N, D,
+                                                xbar.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+                "cnf_interaction_vjp")
+  return xbar
+
+
+def force_of_sets(spec, x3):
+  """The self-mode force [S, N, D] of staged sets x3 with any S: ONE cnf_interaction call per 64 sets."""
+  parts = [_call(spec, x3[i:i + _capi.MMD_MAX_SETS], None, False, True)[2] for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
+  return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def force_vjp_of_sets(spec, x3, g3):
+  """xbar [S, N, D] of staged sets x3 and force adjoints g3 with any S: ONE cnf_interaction_vjp call per 64 sets."""
+  parts = [_vjp_call(spec, x3[i:i + _capi.MMD_MAX_SETS], g3[i:i + _capi.MMD_MAX_SETS])
+           for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
+  return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def interaction_force_vjp(x, g, kind, amplitudes=None, bandwidths=None):
+  """The vector-Jacobian product of the self-mode force f_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j) of the point
+  sets x [N, D] or [S, N, D] (what utils.interaction_energy's grad is, times N) with the adjoint g of the same shape:
+    xbar_k = (1 / (N - 1)) sum_{j != k} H(x_k - x_j) (g_k - g_j),   H the pair Hessian of W,
+  float32 [S, N, D] ([N, D] for 2-D x), ONE fused cnf_interaction_vjp call per 64 sets; composed in
+  torch it is a double backward through an N x N x D pair tensor per set.  It is the exact gradient of sum_i g_i . f_i
+  as the kernel computes f: for the exponential kind a coincident pair contributes nothing, and in dimension 1 the
+  result does not contain the delta term of the kink of W at 0.  Two calls give the same bits.  ValueError before any
+  device work for what the C ABI refuses."""
+  x3, g3 = _sets("interaction", x, "x"), _sets("interaction", g, "g")
+  interaction_check_shapes((min(x3.shape[0], _capi.MMD_MAX_SETS),) + tuple(x3.shape[1:]))
+  if tuple(g3.shape) != tuple(x3.shape):
+    raise ValueError(f"interaction: the force's adjoint must have the points' shape {tuple(x3.shape)}, not {tuple(g3.shape)}")
+  spec = interaction_vjp_check_spec(interaction_spec(kind, amplitudes, bandwidths))
+  dev, one, (x3, g3) = _stage(x, x3, g3)
+  return _unstack(force_vjp_of_sets(spec, x3, g3), one)

@@ -9,7 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
-                               [--path-errors] [--fit] [--interaction]
+                               [--path-errors] [--fit] [--interaction] [--mv-path]
 """
 import argparse
 import sys
@@ -34,7 +34,8 @@ DEFAULT_CONFIG: Dict[str, Dict[str, Any]] = {
   "cnf": {"flow_num_layers": 2, "mlp_num_layers": 2, "hidden_size": 16, "num_bins": 5},
   "train": {"epochs": 30000, "lr": 0.001, "_lambda": 5000.0, "batch_size": 2048, "eval_frequency": 100},
   # not in the reference: a nonlocal running cost strength * int_0^T F(rho_t) dt for ot and rwpo, F the interaction energy
-  # of utils.interaction_energy (kind "none": no such cost; "gaussian", "exponential", "quadratic": utils.interaction_spec)
+  # of utils.interaction_energy (kind "none": no such cost; "gaussian", "exponential", "quadratic": utils.interaction_spec).
+  # An optional key `role` (absent: "cost"): "drift" puts -strength grad (W * rho) into fp's drift instead (bind_loss)
   "interaction": {"kind": "none", "strength": 1.0, "amplitudes": [1.0], "bandwidths": [1.0]},
 }
 
@@ -64,14 +65,20 @@ def build_model(config) -> FlowModel:
 
 def bind_loss(config, model) -> Callable:
   """solvers.py:58-88: loss_fn(params, rng, _lambda, batch_size).  With an `interaction` section whose kind is not
-  "none", ot and rwpo gain its running cost (the losses' `interaction=`); fp has no such term: ValueError."""
+  "none", the section's optional key `role` says what the interaction is: "cost" (the default when the key is absent), a
+  running cost of ot and rwpo (the losses' `interaction=`), which fp does not have: ValueError; "drift", the force
+  -strength grad (W * rho) in fp's drift (fp_loss_fn's `interaction=`: the McKean-Vlasov problem whose particle form
+  evaluate_mv_reference integrates), which ot and rwpo do not have: ValueError.  Any other role: ValueError."""
   g = config["general"]
   _type, dim, dt, dx, tbs = g["type"], g["dim"], g["dt"], g["dx"], g["t_batch_size"]
   kw = {}
   if _interaction_kind(config) != "none":
-    if _type == "fp":
-      raise ValueError("an interaction term is defined for ot and rwpo: fp_loss_fn's drifts are compiled into the "
-                       "flow-matching kernel (an interacting drift is out of scope)")
+    role = _interaction_role(config)
+    if _type == "fp" and role != "drift":
+      raise ValueError("an interaction COST is defined for ot and rwpo: fp_loss_fn's drifts are compiled into the "
+                       "flow-matching kernel; the section's `role: drift` puts the interaction's force into fp's drift")
+    if _type != "fp" and role == "drift":
+      raise ValueError(f"an interaction with `role: drift` is defined for fp (fp_loss_fn's interaction=), not for {_type}")
     kw["interaction"] = (_interaction_kwargs(config), float(config["interaction"]["strength"]))
   if _type == "rwpo":
     r = config["rwpo"]
@@ -79,10 +86,22 @@ def bind_loss(config, model) -> Callable:
   if _type == "fp":
     f = config["fp"]
     return partial(applications.fp_loss_fn, model, dim, f["T"], f["a"], f["sigma"], dt, dx, tbs,
-                   f["velocity_field_type"])
+                   f["velocity_field_type"], **kw)
   if _type == "ot":
     return partial(applications.ot_loss_fn, model, dim, 1, dt, tbs, config["ot"]["subtype"], **kw)
   raise Exception(f"Unknown problem type: {_type}...")        # solvers.py:87-88
+
+
+INTERACTION_ROLES = ("cost", "drift")
+
+
+def _interaction_role(config) -> str:
+  """The `interaction` section's optional key `role` ("cost" when absent; not in DEFAULT_CONFIG) -- ValueError for any
+  other value than INTERACTION_ROLES"""
+  role = config.get("interaction", {}).get("role", "cost")
+  if role not in INTERACTION_ROLES:
+    raise ValueError(f"interaction: role is one of {INTERACTION_ROLES}, not {role!r}")
+  return role
 
 
 def _interaction_kind(config) -> str:
@@ -663,7 +682,7 @@ def print_interaction(res: Dict[str, Any]) -> None:
   print("running cost strength * int F dt (strength {}): {:.6e}".format(res["strength"], res["running_cost"]))
 
 
-# ---- the particle reference of an fp problem with an interaction: what an interacting training term would be held to ---
+# ---- the particle reference of an fp problem with an interaction: what the interacting training term is held to ------
 
 MV_REFERENCE_KEYS = ("times", "mean", "trace_cov", "free_mean", "free_trace_cov", "trace_cov_floor", "energy",
                      "energy_floor", "bad", "trace_cov_exact", "kind", "strength", "n", "replicas")
@@ -673,8 +692,8 @@ def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1
   """The ground truth of an fp configuration whose `interaction` section has a kind: the interacting particle system
   of applications.mv_reference_particles (`replicas` systems of n_particles, step h, the config's drift, sigma and
   kernel, strength as the force's factor) whose law converges to d rho / dt = -div(rho (drift - strength grad(W * rho)))
-  + sigma lap rho.  It takes no model: bind_loss refuses this configuration (there is no interacting training term
-  yet), so `main` has no flag for it.  Per time of `times` (default: the figure's, rounded to multiples of h), lists:
+  + sigma lap rho.  It takes no model: it is what the interacting training term (the section's `role: drift`,
+  fp_loss_fn's `interaction=`) is held to, and evaluate_mv_path puts a trained flow beside it.  Per time of `times` (default: the figure's, rounded to multiples of h), lists:
     times
     mean, trace_cov            of the interacting ensemble, pooled over the replicas (mean: [D] per time)
     free_mean, free_trace_cov  the same of applications.fp_reference_particles with the same seed and
@@ -726,6 +745,66 @@ def print_mv_reference(res: Dict[str, Any]) -> None:
       t, float(np.linalg.norm(res["mean"][i])), res["trace_cov"][i], res["trace_cov_floor"][i],
       res["free_trace_cov"][i], res["energy"][i], res["energy_floor"][i], res["bad"][i])
       + (" | {:.6f}".format(res["trace_cov_exact"][i]) if exact else ""))
+
+
+# ---- a flow trained on the interacting fp problem beside the particle reference ---------------------------------------
+
+MV_PATH_KEYS = ("times", "flow_mean", "flow_trace_cov", "flow_energy", "mean", "trace_cov", "trace_cov_floor", "energy",
+                "energy_floor", "free_trace_cov", "trace_cov_exact", "bad", "kind", "strength", "n", "n_particles", "replicas")
+
+
+def evaluate_mv_path(config, model: FlowModel, params: Params, times=None, n=8192, n_particles=16384, replicas=2, h=1e-3,
+                     seed=0) -> Dict[str, Any]:
+  """A flow trained on an fp configuration whose `interaction` section has `role: drift`, beside the interacting particle
+  reference: per time of `times` (evaluate_mv_reference's default and rounding), lists
+    times
+    flow_mean, flow_trace_cov  of n flow samples (model.apply.sample of `seed`; utils.point_stats, cov over n)
+    flow_energy                their interaction energy F (utils.interaction_energy, the section's kernel)
+    mean, trace_cov, trace_cov_floor, energy, energy_floor, free_trace_cov, bad, trace_cov_exact
+                               evaluate_mv_reference's columns for the same arguments: the pooled values, the replica
+                               floors, the ensemble without the force and, for drift ou with the quadratic kernel, the
+                               mean-field limit (else None)
+  and kind, strength, n, n_particles, replicas.  A flow agrees with the reference where its columns differ by the
+  floors' order.  ValueError, before any device work, for n < 2, what utils.interaction_check_shapes refuses at n and
+  what evaluate_mv_reference refuses."""
+  name = "evaluate_mv_path"
+  n = int(n)
+  _, ts, _, (dim, _, _, _, _) = _fp_prelude(name, config, times, n_particles, h, 2)
+  if _interaction_kind(config) == "none":
+    raise ValueError(f"{name}: defined for fp with an interaction kind, not 'none'")
+  if n < 2:
+    raise ValueError(f"{name}: needs n >= 2 flow samples per time, not {n}")
+  utils.interaction_check_shapes((1, n, dim))
+  kw = _interaction_kwargs(config)
+  utils.interaction_spec(**kw)
+  ref = evaluate_mv_reference(config, times, n_particles, replicas, h, seed)
+  x = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n,)) for t in ref["times"]]).float()
+  chunks = range(0, x.shape[0], _capi.MMD_MAX_SETS)
+  stats = [utils.point_stats(x[i:i + _capi.MMD_MAX_SETS]) for i in chunks]
+  F = torch.cat([utils.interaction_energy(x[i:i + _capi.MMD_MAX_SETS], **kw)["energy"] for i in chunks])
+  out = {"times": ref["times"],
+         "flow_mean": torch.cat([s["mean"] for s in stats]).tolist(),
+         "flow_trace_cov": torch.cat([s["cov"] for s in stats]).diagonal(dim1=-2, dim2=-1).sum(-1).tolist(),
+         "flow_energy": F.tolist(), "n": n, "n_particles": ref["n"]}
+  for k in ("mean", "trace_cov", "trace_cov_floor", "energy", "energy_floor", "free_trace_cov", "trace_cov_exact", "bad",
+            "kind", "strength", "replicas"):
+    out[k] = ref[k]
+  return out
+
+
+def print_mv_path(res: Dict[str, Any]) -> None:
+  """evaluate_mv_path's table, one line per time"""
+  exact = res["trace_cov_exact"] is not None
+  print("flow against the interacting particle reference ({} kernel, strength {}, {} flow samples, {} replicas of {}):  "
+        "t | |mean| flow | reference | tr cov flow | reference | floor | without the force{} | F flow | reference | floor"
+        .format(res["kind"], res["strength"], res["n"], res["replicas"], res["n_particles"],
+                " | mean-field limit" if exact else ""))
+  for i, t in enumerate(res["times"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f} | {:.2e} | {:.6f}".format(
+      t, float(np.linalg.norm(res["flow_mean"][i])), float(np.linalg.norm(res["mean"][i])), res["flow_trace_cov"][i],
+      res["trace_cov"][i], res["trace_cov_floor"][i], res["free_trace_cov"][i])
+      + (" | {:.6f}".format(res["trace_cov_exact"][i]) if exact else "")
+      + " | {:.6e} | {:.6e} | {:.2e}".format(res["flow_energy"][i], res["energy"][i], res["energy_floor"][i]))
 
 
 # ---- the optimal-transport reference of the ot problems: Sinkhorn divergences between point clouds -------------------
@@ -928,13 +1007,14 @@ def _eval_rng(seed, step):
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
-         interaction: bool = False) -> Dict[str, Any]:
+         interaction: bool = False, mv_path: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
-  table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table."""
+  table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
+  `interaction` section whose role is drift): print evaluate_mv_path's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -947,6 +1027,9 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     raise ValueError(f"--knn compares the flow with the fp particle reference: not defined for {_type}")
   if interaction and _interaction_kind(config) == "none":
     raise ValueError("--interaction prints the interaction energy of the config's `interaction` section: its kind is 'none'")
+  if mv_path and (_type != "fp" or _interaction_kind(config) == "none" or _interaction_role(config) != "drift"):
+    raise ValueError("--mv-path compares an fp flow trained with the interaction in its drift (`role: drift`) with the "
+                     "interacting particle reference")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -1008,6 +1091,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_knn(evaluate_fp_knn(config, model, params))
   if interaction:
     print_interaction(evaluate_interaction(config, model, params))
+  if mv_path:
+    print_mv_path(evaluate_mv_path(config, model, params))
   return res
 
 
@@ -1040,6 +1125,9 @@ def _parse(argv):
   p.add_argument("--interaction", action="store_true",
                  help="print the interaction energy of the flow's samples along the path, beside its Monte-Carlo floor, and "
                       "the running cost (a config with an `interaction` section whose kind is not none)")
+  p.add_argument("--mv-path", action="store_true",
+                 help="print the mean, tr cov and interaction energy of the flow's samples beside the interacting particle "
+                      "reference and its replica floors (fp with an `interaction` section whose role is drift)")
   return p.parse_args(argv)
 
 
@@ -1047,4 +1135,4 @@ if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
-       sliced=args.sliced, knn=args.knn, interaction=args.interaction)
+       sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path)

@@ -23,7 +23,7 @@ from .two_sample import (  # noqa: F401
     KNN_MAX_K, KNN_MAX_POINTS, knn_check_shapes, knn, knn_estimates, knn_divergence, knn_entropy)
 from .interaction import (  # noqa: F401
     INTERACTION_KINDS, INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS, interaction_spec, interaction_check_shapes,
-    interaction_energy, interaction_field)
+    interaction_energy, interaction_field, interaction_force_vjp)
 
 
 def _model_of(fn_or_model):

@@ -502,6 +502,16 @@ int cnf_score_residual(const float *r, const float *score, int64_t n,
                        int64_t count, int32_t D, float dt, float coef,
                        int32_t drift, float a, float loss_coef, double *sums,
                        float *rbar, float *sbar, void *stream);
+/* cnf_score_residual with an interaction force inside the square (the interacting Fokker-Planck residual):
+ * force [n, D] = the force at the n samples r3 (cnf_interaction, self mode, per slice),
+ *   u = (r2 - r1)/dt + coef score - drift_d(r3) + strength force,   sums[s] = sum_{i,d} u_{i,d}^2,
+ * for every drift cnf_score_residual takes.  With rbar / sbar / fbar non-NULL (all three or none) it also writes
+ * fbar [n, D] = strength * u_bar, the adjoint of the force: the seed of cnf_interaction_vjp.  CNF_ERR_INVALID: what
+ * cnf_score_residual refuses, a NULL force, an fbar that does not match rbar. */
+int cnf_score_residual_force(const float *r, const float *score, const float *force, float strength,
+                             int64_t n, int64_t count, int32_t D, float dt, float coef,
+                             int32_t drift, float a, float loss_coef, double *sums, float *rbar,
+                             float *sbar, float *fbar, void *stream);
 int cnf_rkl_residual(const float *y, const float *lp, int64_t n, int32_t D,
                      float t, float T, float beta, float loss_coef, double *sum,
                      float *ybar, float *lpbar, void *stream);
@@ -960,6 +970,31 @@ int cnf_interaction_splits(int32_t S, int64_t N, int64_t Q, int32_t D);
 int cnf_interaction(const CnfInteractionSpec *spec, int32_t S, const float *x, int64_t N,
                     const float *q, int64_t Q, int32_t D, double *sums, float *pot, float *force,
                     void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---- the vector-Jacobian product of the self-mode force ---------------------------------------------------------------
+ * For S sets x [S, N, D] and an adjoint g [S, N, D] of the force f_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j)
+ * that cnf_interaction writes in self mode, cnf_interaction_vjp OVERWRITES
+ *   xbar [S, N, D] (device, float32):  xbar_k = (1 / (N - 1)) sum_{j != k} H(x_k - x_j) (g_k - g_j),
+ * H(d) v = c1 v + d (d . v) c2 the pair Hessian of W (W is even) with, r = |d| and e_b the term's exponential,
+ *   Gaussian:     c1 = sum_b (-amp_b / bw_b^2) e_b,  c2 = sum_b (amp_b / bw_b^4) e_b
+ *   exponential:  c1 = w / r,  c2 = w' / r^2 - w / r^3,  w = sum_b (-amp_b / bw_b) e_b,  w' = sum_b (amp_b / bw_b^2) e_b;
+ *                 both 0 at a coincident pair (r^2 <= 1e-30), the force's own rule
+ *   quadratic:    c1 = amp_0,  c2 = 0
+ * the exact gradient of sum_i g_i . f_i in x for fixed g.  (For the exponential kind in dimension 1 it does not contain
+ * the delta term of the kink of W at 0: the discrete objective has none.)  The pair j == k contributes 0 by itself.
+ * Built as cnf_interaction's pair pass: the same workgroup geometry and cnf_interaction_splits(S, N, 0, D) column
+ * splits, one v_exp_f32 per term and pair, float32 accumulators for 64 columns, then doubles, a fixed-order merge, no
+ * atomics: two calls are bit-identical and the result does not depend on what the workspace held.  The spec is a HOST
+ * argument; the workspace (cnf_interaction_vjp_workspace bytes, 8-byte aligned) is the caller's: no allocation, no
+ * synchronisation (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: everything cnf_interaction refuses in self mode (spec, S, N,
+ * D), a NULL g or xbar, a Hessian coefficient amp / bw^4 (Gaussian) or amp / bw^2 (exponential) outside float32's
+ * range, a workspace smaller than cnf_interaction_vjp_workspace says.
+ * Out of scope: query mode, more than one rank. */
+int cnf_interaction_vjp_workspace(int32_t S, int64_t N, int32_t D, int64_t *bytes);
+int cnf_interaction_vjp(const CnfInteractionSpec *spec, int32_t S, const float *x, const float *g,
+                        int64_t N, int32_t D, float *xbar, void *workspace, int64_t workspace_bytes,
+                        void *stream);
 
 /* ---- a particle reference for the interacting (McKean-Vlasov) Fokker-Planck equation --------------------------------
  *   d rho / dt = -div(rho (drift - kappa grad (W * rho))) + sigma lap rho
