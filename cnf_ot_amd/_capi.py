@@ -72,14 +72,16 @@ class CnfMmdSpec(ctypes.Structure):
 
 
 INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS = 4, 1 << 20
-INTERACTION_KINDS = {"gaussian": 0, "exponential": 1, "quadratic": 2}
+INTERACTION_KINDS = {"gaussian": 0, "exponential": 1, "quadratic": 2, "power": 4}       # (3 is not a kind)
+INTERACTION_MAX_EXPONENT = 16.0
 
 
 class CnfInteractionSpec(ctypes.Structure):
   """The pair kernel of cnf_interaction (include/cnf_ot_amd.h): kind 0 = a signed sum of Gaussians, 1 = of exponentials
-  of the distance (Morse), 2 = amp[0] r^2 / 2."""
+  of the distance (Morse), 2 = amp[0] r^2 / 2, 4 = softened power laws and logs with the exponents pw and the softening
+  length bw[0]."""
   _fields_ = [("kind", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("amp", ctypes.c_float * INTERACTION_MAX_TERMS),
-              ("bw", ctypes.c_float * INTERACTION_MAX_TERMS)]
+              ("bw", ctypes.c_float * INTERACTION_MAX_TERMS), ("pw", ctypes.c_float * INTERACTION_MAX_TERMS)]
 
 
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)

@@ -993,6 +993,19 @@ def mv_quadratic_ou_variance(t, a, sigma, strength, amp, var0):
   return v_inf + (var0 - v_inf) * math.exp(-2.0 * lam * t)
 
 
+def mv_log_second_moment(t, dim, sigma, strength, amp, m0):
+  """E mean_i |x_i|^2 at time t of the interacting system with the log kernel W = amp ln r (utils.interaction_spec's
+  kind "power", one exponent 0, no softening), no drift and noise sigma, started at E mean |x|^2 = m0:
+    m0 + (2 dim sigma - strength amp) t,
+  exact in every dimension and for EVERY N, not only in the mean-field limit (the Keller-Segel virial identity).  With
+  G_i = (1 / (N - 1)) sum_{j != i} amp (x_i - x_j) / |x_i - x_j|^2, antisymmetry of the pair force gives
+  sum_i x_i . G_i = (amp / (N - 1)) sum_{i < j} |x_i - x_j|^2 / |x_i - x_j|^2 = amp N / 2, so Ito's formula for
+  dx_i = -strength G_i dt + sqrt(2 sigma) dB reads d E mean |x|^2 / dt = -2 strength amp / 2 + 2 dim sigma.  A softening
+  length eps replaces each pair's 1 by d^2 / (d^2 + eps^2) (the drift term shrinks by the pair mean of eps^2 / (d^2 +
+  eps^2)), and Euler-Maruyama with step h adds h strength^2 mean |G|^2 per unit time: neither is in this form."""
+  return float(m0) + (2.0 * float(dim) * float(sigma) - float(strength) * float(amp)) * float(t)
+
+
 def mv_reference_particles(dim, T, a, sigma, subtype, interaction, strength, times, n_particles=16384, replicas=2,
                            h=1e-3, seed=0, var0=None, x0=None, grid=None, axes=(0, 1), positions=False):
   """The interacting fp problem's density along `times` from `replicas` independent systems of n_particles particles
@@ -1341,10 +1354,10 @@ def sliced_loss_fn(model, dim, params, target, cond, rng, batch_size, directions
 # ---- the nonlocal cost of a mean-field control problem: the interaction energy of the flow's own samples --------------
 
 def interaction_loss_fn(model, dim, params, cond, rng, batch_size, kind, amplitudes=None, bandwidths=None, shard=None,
-                        grad=None):
+                        grad=None, exponents=None):
   """The mean over the times of `cond` of the interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1))
-  (utils.interaction_energy: kind, amplitudes and bandwidths are utils.interaction_spec's) of batch_size flow samples at
-  that time -- the same base draw of `rng` for every time, as the other sample terms.  W > 0 is congestion, W < 0 or
+  (utils.interaction_energy: kind, amplitudes, bandwidths and exponents are utils.interaction_spec's) of batch_size flow
+  samples at that time -- the same base draw of `rng` for every time, as the other sample terms.  W > 0 is congestion, W < 0 or
   quadratic W aggregation, a Morse W swarming.  With `grad` (the convention of the other term functions;
   `value_and_grad` supplies it) the parameter gradient is accumulated by ONE cnf_interaction call (value and
   d / d samples) and ONE cnf_pass_vjp call; more than 64 times go in chunks of 64 sets.  Single rank: the pairs across
@@ -1352,7 +1365,7 @@ def interaction_loss_fn(model, dim, params, cond, rng, batch_size, kind, amplitu
   ValueError, as does a terms backend that is not the HIP engine."""
   def refuse(S, _):      # -> the spec
     ia.interaction_check_shapes((min(S, _capi.MMD_MAX_SETS), int(batch_size), int(dim)))
-    return ia.interaction_spec(kind, amplitudes, bandwidths)
+    return ia.interaction_spec(kind, amplitudes, bandwidths, exponents)
 
   def stat(samples, _, spec, want_grad):
     return ia.energy_of_sets(spec, samples, want_grad)

@@ -151,8 +151,9 @@ class _InteractionEnergy(torch.autograd.Function):
   """The interaction energy of one point set: the forward call stores dF / dx, backward is it times the incoming scalar."""
 
   @staticmethod
-  def forward(ctx, x, kind, amplitudes, bandwidths):
-    res = interaction.interaction_energy(x.detach(), kind, amplitudes, bandwidths, want_grad=ctx.needs_input_grad[0])
+  def forward(ctx, x, kind, amplitudes, bandwidths, exponents):
+    res = interaction.interaction_energy(x.detach(), kind, amplitudes, bandwidths, want_grad=ctx.needs_input_grad[0],
+                                         exponents=exponents)
     ctx.save_for_backward(res.get("grad"))
     return res["energy"]
 
@@ -160,16 +161,16 @@ class _InteractionEnergy(torch.autograd.Function):
   def backward(ctx, gbar):
     g, = ctx.saved_tensors
     w = gbar.to(torch.float32)
-    return (None if g is None else g * w[:, None, None] if g.dim() == 3 else g * w[0]), None, None, None
+    return (None if g is None else g * w[:, None, None] if g.dim() == 3 else g * w[0]), None, None, None, None
 
 
-def interaction_energy(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None):
+def interaction_energy(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None, exponents=None):
   """The mean-field interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1)) of the sample sets x [N, D] or
-  [S, N, D] (utils.interaction_energy: a signed Gaussian, exponential or quadratic pair kernel), [S] float64 ([1] for a
-  2-D input), differentiable in x: backward is the gradient cnf_interaction stored times the incoming scalar.  The
-  kernel's amplitudes and bandwidths are constants.  With `flow_forward` a flow trains on the energy through ordinary
-  autograd (applications.interaction_loss_fn is the hand-written fast path)."""
-  return _InteractionEnergy.apply(x, kind, amplitudes, bandwidths)
+  [S, N, D] (utils.interaction_energy: a signed Gaussian, exponential, quadratic or softened power-law / log pair
+  kernel), [S] float64 ([1] for a 2-D input), differentiable in x: backward is the gradient cnf_interaction stored times
+  the incoming scalar.  The kernel's amplitudes, bandwidths and exponents are constants.  With `flow_forward` a flow
+  trains on the energy through ordinary autograd (applications.interaction_loss_fn is the hand-written fast path)."""
+  return _InteractionEnergy.apply(x, kind, amplitudes, bandwidths, exponents)
 
 
 class _InteractionForce(torch.autograd.Function):
@@ -177,10 +178,11 @@ class _InteractionForce(torch.autograd.Function):
   adjoint."""
 
   @staticmethod
-  def forward(ctx, x, kind, amplitudes, bandwidths):
+  def forward(ctx, x, kind, amplitudes, bandwidths, exponents):
     x3 = interaction._sets("interaction", x, "x")
     interaction.interaction_check_shapes((min(x3.shape[0], _capi.MMD_MAX_SETS),) + tuple(x3.shape[1:]))
-    spec = interaction.interaction_vjp_check_spec(interaction.interaction_spec(kind, amplitudes, bandwidths))
+    spec = interaction.interaction_vjp_check_spec(
+        interaction.interaction_spec(kind, amplitudes, bandwidths, exponents))
     _, one, (x3, _) = interaction._stage(x, x3, x3[:, :0])
     ctx.spec, ctx.one = spec, one
     ctx.save_for_backward(x3)
@@ -190,15 +192,15 @@ class _InteractionForce(torch.autograd.Function):
   def backward(ctx, fbar):
     x3, = ctx.saved_tensors
     g3 = fbar.detach().to(device=x3.device, dtype=torch.float32).reshape(x3.shape).contiguous()
-    return interaction._unstack(interaction.force_vjp_of_sets(ctx.spec, x3, g3), ctx.one), None, None, None
+    return interaction._unstack(interaction.force_vjp_of_sets(ctx.spec, x3, g3), ctx.one), None, None, None, None
 
 
-def interaction_force(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None):
+def interaction_force(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=None, exponents=None):
   """The mean-field force f_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j) of the sample sets x [N, D] or [S, N, D]
   (cnf_interaction in self mode; the pair kernel of utils.interaction_spec), float32 of x's shape, differentiable in x:
   backward is ONE cnf_interaction_vjp call per 64 sets (utils.interaction_force_vjp) -- the second pair sum, with the
   pair Hessian of W, that a loss needs when the force sits inside a square, as in the interacting Fokker-Planck residual
   (applications.fp_loss_fn(interaction=...) is the hand-written fast path).  The backward is the exact gradient of the
   discrete force: for the exponential kind in dimension 1 it does not contain the delta term of the kink of W at 0.
-  The kernel's amplitudes and bandwidths are constants."""
-  return _InteractionForce.apply(x, kind, amplitudes, bandwidths)
+  The kernel's amplitudes, bandwidths and exponents are constants."""
+  return _InteractionForce.apply(x, kind, amplitudes, bandwidths, exponents)

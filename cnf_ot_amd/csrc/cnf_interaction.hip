@@ -1,7 +1,7 @@
 // cnf_interaction.hip -- the mean-field interaction energy of a point cloud, F = 1/2 sum sum W(x_i - x_j) / (N (N - 1)),
 // its first variation (W * rho)(row_i) and its Wasserstein gradient grad (W * rho)(row_i), for a pair kernel of r = |x - y|
 //   Gaussian     W = sum_b amp_b exp(-r^2 / (2 bw_b^2)),   exponential  W = sum_b amp_b exp(-r / bw_b)  (Morse: two terms),
-//   quadratic    W = amp_0 r^2 / 2,
+//   quadratic    W = amp_0 r^2 / 2,        power  W = sum_b amp_b u^(pw_b / 2) / pw_b (ln(u) / 2 for pw_b = 0), u = r^2 + eps^2,
 // with SIGNED amplitudes: repulsion, aggregation, swarming.  The one cost of a mean-field control problem that is not
 // local in the density.  Model-free, like cnf_mmd.hip, and built like it.
 //
@@ -11,8 +11,9 @@
 // read serves IA_R pairs per lane and a row's sum and force are that lane's alone: no atomics.  A column is the same
 // for every lane of the wave -- its address comes from blockIdx and loop counters only -- so it is read through the
 // scalar cache into SGPRs.  Distances come from coordinate differences, in cnf_mmd2's fmaf order.  One v_exp_f32 per term
-// and pair; the exponential kind adds one v_rsq_f32 per pair.  The term count is wave-uniform and chosen per TILE, inside
-// the kernel, so the unit has 14 x 3 x 2 kernels where a templated count would have four times as many.  float32
+// and pair; the exponential kind adds one v_rsq_f32 per pair, the power kind one v_log_f32.  The term count is
+// wave-uniform and chosen per TILE, inside the kernel, so the unit has 14 x 4 x 2 kernels where a templated count would
+// have four times as many.  float32
 // accumulators live for one tile of IA_TILE = 64 columns and are then added into doubles.  The full square is computed:
 // the per-row field and force are the product, and a triangle would need transposed accumulation.
 //
@@ -47,8 +48,8 @@ int64_t ia_workspace_doubles(int32_t S, int64_t rows, int64_t N, int32_t D, bool
 // The quadratic kind accumulates r^2 and (x - y); amp_0 joins the finish kernel's coefficients.
 template <int D, int KIND, bool FORCE, bool DIAG, int NT>
 __device__ __forceinline__ void ia_tile(const float* __restrict__ col, int64_t c0, int n, int first_local,
-                                        const float (&x)[IA_R][D], const IaCoef& k, double (&sum)[IA_R],
-                                        double (&gsum)[IA_R][D]) {
+                                        const float (&x)[IA_R][D], const IaCoef& k, const IaPower& pk,
+                                        double (&sum)[IA_R], double (&gsum)[IA_R][D]) {
   float ks[IA_R], g[IA_R][D];
 #pragma unroll
   for (int r = 0; r < IA_R; ++r) {
@@ -58,7 +59,8 @@ __device__ __forceinline__ void ia_tile(const float* __restrict__ col, int64_t c
   }
   const float* p = col + c0 * D;               // wave-uniform: scalar loads
   // columns in flight: at most 14 SGPRs of coordinates beside the 12 of coefficients
-  constexpr int U = D <= 3 ? 4 : D == 4 ? 3 : D <= 6 ? 2 : 1;
+  // (the power kind at D = 3: 3 columns, for its u and L beside the coefficients -- with 4 two SGPRs were spilled)
+  constexpr int U = KIND == CNF_INTERACTION_POWER && D == 3 ? 3 : D <= 3 ? 4 : D == 4 ? 3 : D <= 6 ? 2 : 1;
 #pragma unroll U
   for (int j = 0; j < n; ++j) {
     float c[D];
@@ -69,7 +71,8 @@ __device__ __forceinline__ void ia_tile(const float* __restrict__ col, int64_t c
     for (int r = 0; r < IA_R; ++r) {
 #pragma unroll
       for (int d = 0; d < D; ++d) diff[r][d] = x[r][d] - c[d];
-      d2[r] = diff[r][0] * diff[r][0];
+      if constexpr (KIND == CNF_INTERACTION_POWER) d2[r] = fmaf(diff[r][0], diff[r][0], pk.eps2);   // u = d2 + eps^2
+      else d2[r] = diff[r][0] * diff[r][0];
 #pragma unroll
       for (int d = 1; d < D; ++d) d2[r] = fmaf(diff[r][d], diff[r][d], d2[r]);
     }
@@ -79,6 +82,32 @@ __device__ __forceinline__ void ia_tile(const float* __restrict__ col, int64_t c
         v[r] = d2[r];
         w[r] = 1.0f;
       }
+    } else if constexpr (KIND == CNF_INTERACTION_POWER) {
+      // One v_log_f32 per pair, one v_exp_f32 per term: t_b = u^(pw_b / 2 - 1), the loop of the other kinds; the value
+      // is u sum_b amp_b t_b + cl L after it (a per-term choice between a power and a log term, though wave-uniform,
+      // compiled to both forms and a select per term and pair; the log terms' coefficients are added on the host instead).
+      // The clamp is what keeps a coincident pair with eps = 0 (every pw_b >= 2, so nc_b >= 0 and cl = 0) finite:
+      // u = 1e-30 gives a finite L and t_b <= 1, so the pair adds W(0) = 0 (below 1e-30 sum_b |amp_b|) and, with
+      // diff = 0, a zero force; log2(0) = -inf times nc_b = 0 would be NaN
+      float u[IA_R], L[IA_R];
+#pragma unroll
+      for (int r = 0; r < IA_R; ++r) {
+        u[r] = fmaxf(d2[r], 1e-30f);
+        L[r] = __builtin_amdgcn_logf(u[r]);
+        v[r] = 0.0f;
+        w[r] = 0.0f;
+      }
+#pragma unroll
+      for (int b = 0; b < NT; ++b) {
+#pragma unroll
+        for (int r = 0; r < IA_R; ++r) {
+          const float t = __builtin_amdgcn_exp2f(L[r] * k.nc[b]);
+          v[r] = fmaf(t, k.amp[b], v[r]);
+          if constexpr (FORCE) w[r] = fmaf(t, k.ga[b], w[r]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < IA_R; ++r) v[r] = fmaf(u[r], v[r], L[r] * pk.cl);
     } else {
       float a[IA_R], inv[IA_R];
 #pragma unroll
@@ -132,16 +161,16 @@ __device__ __forceinline__ void ia_tile(const float* __restrict__ col, int64_t c
 // code for its count (a count tested per column kept every column's scalar load and its wait between two branches)
 template <int D, int KIND, bool FORCE, bool DIAG>
 __device__ __forceinline__ void ia_tile_terms(const float* __restrict__ col, int64_t c0, int n, int first_local,
-                                              const float (&x)[IA_R][D], const IaCoef& k, double (&sum)[IA_R],
-                                              double (&gsum)[IA_R][D]) {
+                                              const float (&x)[IA_R][D], const IaCoef& k, const IaPower& pk,
+                                              double (&sum)[IA_R], double (&gsum)[IA_R][D]) {
   if constexpr (KIND == CNF_INTERACTION_QUADRATIC) {
-    ia_tile<D, KIND, FORCE, DIAG, 1>(col, c0, n, first_local, x, k, sum, gsum);
+    ia_tile<D, KIND, FORCE, DIAG, 1>(col, c0, n, first_local, x, k, pk, sum, gsum);
   } else {
     switch (k.nt) {
-      case 1: ia_tile<D, KIND, FORCE, DIAG, 1>(col, c0, n, first_local, x, k, sum, gsum); break;
-      case 2: ia_tile<D, KIND, FORCE, DIAG, 2>(col, c0, n, first_local, x, k, sum, gsum); break;
-      case 3: ia_tile<D, KIND, FORCE, DIAG, 3>(col, c0, n, first_local, x, k, sum, gsum); break;
-      default: ia_tile<D, KIND, FORCE, DIAG, 4>(col, c0, n, first_local, x, k, sum, gsum); break;
+      case 1: ia_tile<D, KIND, FORCE, DIAG, 1>(col, c0, n, first_local, x, k, pk, sum, gsum); break;
+      case 2: ia_tile<D, KIND, FORCE, DIAG, 2>(col, c0, n, first_local, x, k, pk, sum, gsum); break;
+      case 3: ia_tile<D, KIND, FORCE, DIAG, 3>(col, c0, n, first_local, x, k, pk, sum, gsum); break;
+      default: ia_tile<D, KIND, FORCE, DIAG, 4>(col, c0, n, first_local, x, k, pk, sum, gsum); break;
     }
   }
 }
@@ -150,7 +179,8 @@ __device__ __forceinline__ void ia_tile_terms(const float* __restrict__ col, int
 template <int D, int KIND, bool FORCE>
 __global__ __launch_bounds__(IA_THREADS) void ia_kernel(const float* __restrict__ x, const float* __restrict__ q,
                                                         int64_t N, int64_t n_rows, int32_t P, const IaCoef k,
-                                                        double* __restrict__ ws, int64_t force_off) {
+                                                        double* __restrict__ ws, int64_t force_off,
+                                                        const IaPower pk) {
   const int s = (int)blockIdx.y;
   const int64_t rg = blockIdx.x / (unsigned)P;
   const int p = (int)(blockIdx.x % (unsigned)P);
@@ -179,9 +209,9 @@ __global__ __launch_bounds__(IA_THREADS) void ia_kernel(const float* __restrict_
     const int n = (int)(N - c0 < IA_TILE ? N - c0 : IA_TILE);
     // IA_TILE divides IA_ROWS and row0 is a multiple of IA_ROWS: a tile lies inside the workgroup's rows or outside
     if (self && c0 >= row0 && c0 < row0 + IA_ROWS)
-      ia_tile_terms<D, KIND, FORCE, true>(col, c0, n, (int)(c0 - row0), xr, k, sum, gsum);
+      ia_tile_terms<D, KIND, FORCE, true>(col, c0, n, (int)(c0 - row0), xr, k, pk, sum, gsum);
     else
-      ia_tile_terms<D, KIND, FORCE, false>(col, c0, n, 0, xr, k, sum, gsum);
+      ia_tile_terms<D, KIND, FORCE, false>(col, c0, n, 0, xr, k, pk, sum, gsum);
   }
   double* part = ws + ((int64_t)s * P + p) * n_rows;
   double* gpart = ws + force_off + ((int64_t)s * P + p) * n_rows * D;
@@ -244,6 +274,7 @@ struct IaLaunch {
   int64_t N, rows;
   int32_t P;
   IaCoef k;
+  IaPower pk;
   double* ws;
   int64_t force_off;
   bool force;
@@ -252,15 +283,16 @@ struct IaLaunch {
 template <int D, int KIND> void ia_launch_force(const IaLaunch& a) {
   if (a.force)
     hipLaunchKernelGGL((ia_kernel<D, KIND, true>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.q, a.N, a.rows, a.P, a.k, a.ws,
-                       a.force_off);
+                       a.force_off, a.pk);
   else
     hipLaunchKernelGGL((ia_kernel<D, KIND, false>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.q, a.N, a.rows, a.P, a.k, a.ws,
-                       a.force_off);
+                       a.force_off, a.pk);
 }
 template <int D> void ia_launch_kind(int kind, const IaLaunch& a) {
   if (kind == CNF_INTERACTION_GAUSSIAN) ia_launch_force<D, CNF_INTERACTION_GAUSSIAN>(a);
   else if (kind == CNF_INTERACTION_EXPONENTIAL) ia_launch_force<D, CNF_INTERACTION_EXPONENTIAL>(a);
-  else ia_launch_force<D, CNF_INTERACTION_QUADRATIC>(a);
+  else if (kind == CNF_INTERACTION_POWER) ia_launch_force<D, CNF_INTERACTION_POWER>(a);
+  else ia_launch_force<D, CNF_INTERACTION_QUADRATIC>(a);   // (ia_coef has refused every other kind)
 }
 template <int D = 1> void ia_launch_dim(int dim, int kind, const IaLaunch& a) {
   if (dim == D) ia_launch_kind<D>(kind, a);
@@ -287,7 +319,7 @@ int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x,
                       IaPairLayout* lay) {
   if (!spec || !lay || !ia_shape_ok(S, N, Q, D)) return CNF_ERR_INVALID;
   IaLaunch a{};
-  if (!ia_coef(spec, &a.k)) return CNF_ERR_INVALID;
+  if (!ia_coef(spec, &a.k, &a.pk)) return CNF_ERR_INVALID;
   a.force = force;
   a.rows = Q > 0 ? Q : N;
   a.P = ia_splits(S, a.rows, N);

@@ -7,16 +7,18 @@
 //   exponential  c1 = w / r,  c2 = w' / r^2 - w / r^3 = (w' - c1) / r^2,   w = sum_b (-amp_b / bw_b) e_b,
 //                w' = sum_b (amp_b / bw_b^2) e_b;  both 0 at a coincident pair (d^2 <= 1e-30: ia_tile's rule)
 //   quadratic    c1 = amp_0 (it joins the finish kernel's coefficient),  c2 = 0
+//   power        c1 = sum_b amp_b t_b,  c2 = (sum_b amp_b (pw_b - 2) t_b) / u,   t_b = u^(pw_b / 2 - 1), u = d^2 + eps^2
 // What a loss needs that has the force inside a square (the interacting Fokker-Planck residual): a
 // second pair sum, which composed in torch is a double backward through an N x N x D pair tensor.  The pair j == k
 // contributes d = 0 and g_k - g_k = 0: nothing is masked.
 //
 // Built as ia_kernel is.  A workgroup owns IA_ROWS rows of one set and one of P column splits; a lane keeps IA_R rows
 // of x AND g in registers; a column's x_j and g_j are the same for every lane of the wave and come through the scalar
-// cache.  One v_exp_f32 per term and pair; the exponential kind adds one v_rsq_f32 per pair.  The term count is
-// wave-uniform and switched per TILE.  float32 accumulators live for one tile of IA_TILE = 64 columns and are then added
-// into doubles.  Each (split, row) writes D doubles to the workspace; iv_finish_kernel adds a row's splits in ascending
-// order: no atomics, bitwise reproducible, and every workspace word it reads was written by this call.
+// cache.  One v_exp_f32 per term and pair; the exponential kind adds one v_rsq_f32 per pair, the power kind one v_log_f32
+// and one v_rcp_f32.  The term count is wave-uniform and switched per TILE.  float32 accumulators live for one tile of
+// IA_TILE = 64 columns and are then added into doubles.  Each (split, row) writes D doubles to the workspace;
+// iv_finish_kernel adds a row's splits in ascending order: no atomics, bitwise reproducible, and every workspace word it
+// reads was written by this call.
 #include "cnf_host.h"
 #include "cnf_interaction_pairs.h"
 
@@ -28,7 +30,8 @@
 namespace cnf {
 namespace {
 
-// Term b of a pair: e_b = exp2(nc_b a) with IaCoef's nc_b and a; c1's sum += k1_b e_b, c2's sum += k2_b e_b
+// Term b of a pair: e_b = exp2(nc_b a) with IaCoef's nc_b and a (the power kind: a = log2 u); c1's sum += k1_b e_b,
+// c2's sum += k2_b e_b
 struct IvCoef {
   float nc[IA_MAX_TERMS], k1[IA_MAX_TERMS], k2[IA_MAX_TERMS];
   int32_t nt;
@@ -41,7 +44,7 @@ int64_t iv_workspace_doubles(int32_t S, int64_t N, int32_t D) { return (int64_t)
 template <int D, int KIND, int NT>
 __device__ __forceinline__ void iv_tile(const float* __restrict__ colx, const float* __restrict__ colg, int64_t c0, int n,
                                         const float (&x)[IA_R][D], const float (&g)[IA_R][D], const IvCoef& k,
-                                        double (&acc)[IA_R][D]) {
+                                        const float eps2, double (&acc)[IA_R][D]) {
   float o[IA_R][D];
 #pragma unroll
   for (int r = 0; r < IA_R; ++r) {
@@ -72,7 +75,8 @@ __device__ __forceinline__ void iv_tile(const float* __restrict__ colx, const fl
 #pragma unroll
         for (int d = 0; d < D; ++d) o[r][d] += dv[d];
       } else {
-        float d2 = diff[0] * diff[0], dot = diff[0] * dv[0];
+        // (the power kind: u = d2 + eps^2, the softening joining the first product)
+        float d2 = KIND == CNF_INTERACTION_POWER ? fmaf(diff[0], diff[0], eps2) : diff[0] * diff[0], dot = diff[0] * dv[0];
 #pragma unroll
         for (int d = 1; d < D; ++d) {
           d2 = fmaf(diff[d], diff[d], d2);
@@ -82,6 +86,11 @@ __device__ __forceinline__ void iv_tile(const float* __restrict__ colx, const fl
         if constexpr (KIND == CNF_INTERACTION_EXPONENTIAL) {
           inv = d2 > 1e-30f ? __builtin_amdgcn_rsqf(d2) : 0.0f;
           a = d2 * inv;
+        }
+        if constexpr (KIND == CNF_INTERACTION_POWER) {      // (ia_tile's clamp: a coincident pair with eps = 0 stays finite)
+          const float u = fmaxf(d2, 1e-30f);
+          inv = __builtin_amdgcn_rcpf(u);
+          a = __builtin_amdgcn_logf(u);
         }
         float c1 = 0.0f, c2 = 0.0f;
 #pragma unroll
@@ -94,6 +103,7 @@ __device__ __forceinline__ void iv_tile(const float* __restrict__ colx, const fl
           c1 = c1 * inv;                       // w / r
           c2 = (c2 - c1) * (inv * inv);        // (w' - w / r) / r^2
         }
+        if constexpr (KIND == CNF_INTERACTION_POWER) c2 = c2 * inv;   // u^(q - 1) = t / u
         const float s = dot * c2;
 #pragma unroll
         for (int d = 0; d < D; ++d) o[r][d] = fmaf(diff[d], s, fmaf(dv[d], c1, o[r][d]));
@@ -111,23 +121,25 @@ __device__ __forceinline__ void iv_tile(const float* __restrict__ colx, const fl
 template <int D, int KIND>
 __device__ __forceinline__ void iv_tile_terms(const float* __restrict__ colx, const float* __restrict__ colg, int64_t c0,
                                               int n, const float (&x)[IA_R][D], const float (&g)[IA_R][D],
-                                              const IvCoef& k, double (&acc)[IA_R][D]) {
+                                              const IvCoef& k, const float eps2, double (&acc)[IA_R][D]) {
   if constexpr (KIND == CNF_INTERACTION_QUADRATIC) {
-    iv_tile<D, KIND, 1>(colx, colg, c0, n, x, g, k, acc);
+    iv_tile<D, KIND, 1>(colx, colg, c0, n, x, g, k, eps2, acc);
   } else {
     switch (k.nt) {
-      case 1: iv_tile<D, KIND, 1>(colx, colg, c0, n, x, g, k, acc); break;
-      case 2: iv_tile<D, KIND, 2>(colx, colg, c0, n, x, g, k, acc); break;
-      case 3: iv_tile<D, KIND, 3>(colx, colg, c0, n, x, g, k, acc); break;
-      default: iv_tile<D, KIND, 4>(colx, colg, c0, n, x, g, k, acc); break;
+      case 1: iv_tile<D, KIND, 1>(colx, colg, c0, n, x, g, k, eps2, acc); break;
+      case 2: iv_tile<D, KIND, 2>(colx, colg, c0, n, x, g, k, eps2, acc); break;
+      case 3: iv_tile<D, KIND, 3>(colx, colg, c0, n, x, g, k, eps2, acc); break;
+      default: iv_tile<D, KIND, 4>(colx, colg, c0, n, x, g, k, eps2, acc); break;
     }
   }
 }
 
-// grid (row groups x P, S): blockIdx.y = the set, blockIdx.x = row group * P + split
+// grid (row groups x P, S): blockIdx.y = the set, blockIdx.x = row group * P + split.  eps2 (IaPower's; the power kind
+// alone reads it) is the last argument, so the other kinds' arguments stay where they were
 template <int D, int KIND>
 __global__ __launch_bounds__(IA_THREADS) void iv_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                        int64_t N, int32_t P, const IvCoef k, double* __restrict__ ws) {
+                                                        int64_t N, int32_t P, const IvCoef k, double* __restrict__ ws,
+                                                        const float eps2) {
   const int s = (int)blockIdx.y;
   const int64_t rg = blockIdx.x / (unsigned)P;
   const int p = (int)(blockIdx.x % (unsigned)P);
@@ -155,7 +167,7 @@ __global__ __launch_bounds__(IA_THREADS) void iv_kernel(const float* __restrict_
   for (int64_t t = t0; t < t1; ++t) {
     const int64_t c0 = t * IA_TILE;
     const int n = (int)(N - c0 < IA_TILE ? N - c0 : IA_TILE);
-    iv_tile_terms<D, KIND>(colx, colg, c0, n, xr, gr, k, acc);
+    iv_tile_terms<D, KIND>(colx, colg, c0, n, xr, gr, k, eps2, acc);
   }
   double* part = ws + ((int64_t)s * P + p) * N * D;
 #pragma unroll
@@ -189,15 +201,18 @@ struct IvLaunch {
   int32_t P;
   IvCoef k;
   double* ws;
+  float eps2;
 };
 
 template <int D> void iv_launch_kind(int kind, const IvLaunch& a) {
   if (kind == CNF_INTERACTION_GAUSSIAN)
-    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_GAUSSIAN>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws);
+    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_GAUSSIAN>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws, a.eps2);
   else if (kind == CNF_INTERACTION_EXPONENTIAL)
-    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_EXPONENTIAL>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws);
-  else
-    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_QUADRATIC>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws);
+    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_EXPONENTIAL>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws, a.eps2);
+  else if (kind == CNF_INTERACTION_POWER)
+    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_POWER>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws, a.eps2);
+  else                                         // (ia_coef has refused every other kind)
+    hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_QUADRATIC>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws, a.eps2);
 }
 template <int D = 1> void iv_launch_dim(int dim, int kind, const IvLaunch& a) {
   if (dim == D) iv_launch_kind<D>(kind, a);
@@ -205,11 +220,27 @@ template <int D = 1> void iv_launch_dim(int dim, int kind, const IvLaunch& a) {
 }
 
 // The spec as iv_kernel reads it; false for what cnf_interaction refuses in one and for a Hessian coefficient
-// (amp / bw^4, Gaussian; amp / bw^2, exponential) outside float32's range
-bool iv_coef(const CnfInteractionSpec* spec, IvCoef* k) {
+// (amp / bw^4, Gaussian; amp / bw^2, exponential; amp (pw - 2) eps^(pw - 4), power) outside float32's range
+bool iv_coef(const CnfInteractionSpec* spec, IvCoef* k, float* eps2) {
   IaCoef base;
+  IaPower pk;
   *k = IvCoef{};
-  if (!ia_coef(spec, &base)) return false;
+  *eps2 = 0.0f;
+  if (spec->kind == CNF_INTERACTION_POWER) {
+    base = IaCoef{};
+    pk = IaPower{};
+    if (!ia_coef_power(spec, &base, &pk, true)) return false;
+    k->nt = base.nt;
+    *eps2 = pk.eps2;
+    for (int b = 0; b < base.nt; ++b) {
+      k->nc[b] = base.nc[b];
+      k->k1[b] = base.ga[b];
+      k->k2[b] = (float)((double)spec->amp[b] * ((double)spec->pw[b] - 2.0));
+      if (!std::isfinite(k->k2[b])) return false;
+    }
+    return true;
+  }
+  if (!ia_coef(spec, &base, &pk)) return false;
   k->nt = base.nt;
   for (int b = 0; b < base.nt; ++b) {
     const double ib = 1.0 / ((double)spec->bw[b] * (double)spec->bw[b]);
@@ -236,7 +267,7 @@ extern "C" int cnf_interaction_vjp(const CnfInteractionSpec* spec, int32_t S, co
                                    int32_t D, float* xbar, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!spec || !x || !g || !xbar || !workspace || !ia_shape_ok(S, N, 0, D)) return CNF_ERR_INVALID;
   IvLaunch a{};
-  if (!iv_coef(spec, &a.k)) return CNF_ERR_INVALID;
+  if (!iv_coef(spec, &a.k, &a.eps2)) return CNF_ERR_INVALID;
   if (workspace_bytes < iv_workspace_doubles(S, N, D) * (int64_t)sizeof(double)) return CNF_ERR_INVALID;
   a.P = ia_splits(S, N, N);
   a.grid = dim3((unsigned)(row_groups(N) * a.P), (unsigned)S);

@@ -1,11 +1,14 @@
 """The mean-field interaction energy of a point cloud -- the one cost of a mean-field control problem that is not
 local in the density: F[rho] = 1/2 int int W(x - y) rho(x) rho(y) dx dy on samples, its first variation W * rho (a
-field) and its Wasserstein gradient grad (W * rho) (a force), for a signed Gaussian, exponential (Morse) or quadratic
-pair kernel W(|x - y|).  One fused call over all sets (cnf_interaction); composed in torch the same
-double sum materialises an N x N matrix per set and its backward.  `interaction_force_vjp` is the backward of the force
-itself (cnf_interaction_vjp): what a loss needs that has the force inside a square, as the interacting
-Fokker-Planck residual does.  What surrounds a call is `two_sample`'s.  `utils` re-exports the public names.
+field) and its Wasserstein gradient grad (W * rho) (a force), for a signed Gaussian, exponential (Morse), quadratic or
+softened power-law / log pair kernel W(|x - y|).  One fused call over all sets (cnf_interaction);
+composed in torch the same double sum materialises an N x N matrix per set and its backward.  `interaction_force_vjp`
+is the backward of the force itself (cnf_interaction_vjp): what a loss needs that has the force inside
+a square, as the interacting Fokker-Planck residual does.  What surrounds a call is `two_sample`'s.  `utils` re-exports
+the public names.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -21,17 +24,86 @@ def _floats(v):
   return [float(b) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
 
 
-def interaction_spec(kind, amplitudes=None, bandwidths=None):
+_F32_MAX = 3.4028234663852886e38
+
+
+def _pow(eps, e):
+  """eps^e as the C ABI's check forms it (std::pow): eps^0 = 1 also at eps = 0, inf where eps = 0 meets e < 0, and inf
+  where the power leaves float64"""
+  if e == 0.0:
+    return 1.0
+  if eps == 0.0:
+    return math.inf if e < 0.0 else 0.0
+  try:
+    return eps ** e
+  except OverflowError:
+    return math.inf
+
+
+def _fits(v):
+  return math.isfinite(v) and abs(v) <= _F32_MAX
+
+
+def _power_spec(spec, amplitudes, bandwidths, exponents):
+  """interaction_spec for kind="power": the checks of ia_coef_power (csrc/cnf_interaction_pairs.h), on the float32
+  values the kernel sees"""
+  if exponents is None:
+    raise ValueError("interaction: the power kind needs its exponents")
+  pws = [float(np.float32(p)) for p in _floats(exponents)]
+  amps = [1.0] * len(pws) if amplitudes is None else [float(np.float32(a)) for a in _floats(amplitudes)]
+  if not 1 <= len(pws) <= INTERACTION_MAX_TERMS or len(amps) != len(pws):
+    raise ValueError(f"interaction: between 1 and {INTERACTION_MAX_TERMS} terms, an amplitude and an exponent each, not "
+                     f"{len(amps)} amplitudes and {len(pws)} exponents")
+  eps = [0.0] if bandwidths is None else _floats(bandwidths)
+  if len(eps) != 1:
+    raise ValueError(f"interaction: the power kind has ONE softening length (bandwidths), not {len(eps)}")
+  eps = float(np.float32(eps[0]))
+  if not (math.isfinite(eps) and eps >= 0.0 and _fits(eps * eps)):
+    raise ValueError(f"interaction: the softening length must be finite and >= 0 (in float32, with its square): {eps}")
+  for a, p in zip(amps, pws):
+    if not (math.isfinite(a) and a != 0.0):
+      raise ValueError(f"interaction: every amplitude must be non-zero and finite (in float32): {amps}")
+    if not (math.isfinite(p) and abs(p) <= _capi.INTERACTION_MAX_EXPONENT):
+      raise ValueError(f"interaction: every exponent must be finite with |p| <= {_capi.INTERACTION_MAX_EXPONENT:g}: "
+                       f"{pws}")
+    if eps == 0.0 and not p >= 2.0:
+      raise ValueError(f"interaction: a softening length of 0 needs every exponent >= 2 (a singular kernel otherwise): "
+                       f"{pws}")
+    value = a * math.log(eps) if p == 0.0 else (a / p) * _pow(eps, p)
+    partial = 0.0 if p == 0.0 else (a / p) * _pow(eps, p - 2.0)      # (the value's sum before its factor u)
+    if not (_fits(a * _pow(eps, p - 2.0)) and _fits(value) and (p == 0.0 or _fits(a / p)) and _fits(partial)):
+      raise ValueError(f"interaction: amp eps^(p - 2) (the force) or amp eps^p / p (the value) leaves float32's range: "
+                       f"{a}, {p}, eps {eps}")
+  spec.n_terms = len(pws)
+  for i, (a, p) in enumerate(zip(amps, pws)):
+    spec.amp[i], spec.pw[i] = a, p
+  spec.bw[0] = eps
+  return spec
+
+
+def interaction_spec(kind, amplitudes=None, bandwidths=None, exponents=None):
   """The CnfInteractionSpec of a pair kernel -- ValueError for what cnf_interaction refuses in a spec:
     kind="gaussian":     W(r) = sum_b amplitudes[b] exp(-r^2 / (2 bandwidths[b]^2))
     kind="exponential":  W(r) = sum_b amplitudes[b] exp(-r / bandwidths[b])  (Morse: amplitudes (C_r, -C_a))
     kind="quadratic":    W(r) = amplitudes[0] r^2 / 2  (bandwidths are not used)
+    kind="power":        W(r) = sum_b amplitudes[b] u^(exponents[b] / 2) / exponents[b], u = r^2 + eps^2, a term with
+                         exponent 0 being amplitudes[b] ln(u) / 2 (the log kernel): grad W = (x - y) sum_b amplitudes[b]
+                         u^(exponents[b] / 2 - 1).  eps = bandwidths, ONE softening length (None: 0, allowed only with
+                         every exponent >= 2).  Coulomb / Newton in dimension D: exponents=[2 - D] (D = 2: [0]),
+                         amplitude < 0 for repulsion (W = amp u^(p / 2) / p, p < 0); attraction-repulsion r^a / a -
+                         r^b / b: exponents=[a, b], amplitudes=[1, -1]
   Amplitudes are signed, non-zero and finite (None: 1.0 each); 1..4 bandwidths (None: 1.0), positive and finite as
-  float32 with 1 / bw^2, and amp / bw^2 (Gaussian) or amp / bw (exponential), in float32's range."""
+  float32 with 1 / bw^2, and amp / bw^2 (Gaussian) or amp / bw (exponential), in float32's range.  Power: 1..4 exponents,
+  finite with |p| <= 16, one amplitude each; eps finite and >= 0; amp eps^(p - 2) and amp eps^p / p in float32's range.
+  `exponents` belong to the power kind alone."""
   if kind not in _capi.INTERACTION_KINDS:
     raise ValueError(f"interaction: kind is one of {INTERACTION_KINDS}, not {kind!r}")
   spec = _capi.CnfInteractionSpec()
   spec.kind = _capi.INTERACTION_KINDS[kind]
+  if kind == "power":
+    return _power_spec(spec, amplitudes, bandwidths, exponents)
+  if exponents is not None:
+    raise ValueError(f"interaction: exponents belong to the power kind, not to {kind!r}")
   if kind == "quadratic":
     amps = [1.0] if amplitudes is None else _floats(amplitudes)
     if len(amps) != 1:
@@ -102,7 +174,8 @@ def energy_of_sets(spec, x3, want_grad):
   return sums / (2.0 * N * (N - 1.0)), None if force is None else force * (1.0 / N)
 
 
-def interaction_energy(x, kind, amplitudes=None, bandwidths=None, want_grad=False, want_field=False) -> dict:
+def interaction_energy(x, kind, amplitudes=None, bandwidths=None, want_grad=False, want_field=False,
+                       exponents=None) -> dict:
   """The interaction energy F = sum_{i != j} W(x_i - x_j) / (2 N (N - 1)) of the point sets x [N, D] or [S, N, D] for the
   pair kernel of `interaction_spec`, ONE fused cnf_interaction call over all sets (self mode: the pair i == j is
   skipped by index; duplicated points at other indices do interact).  float32 on the device (float64 inputs are
@@ -112,7 +185,7 @@ def interaction_energy(x, kind, amplitudes=None, bandwidths=None, want_grad=Fals
   the energy does not depend on the want_ flags.  ValueError before any device work for what the C ABI refuses."""
   x3 = _sets("interaction", x, "x")
   interaction_check_shapes(x3.shape)
-  spec = interaction_spec(kind, amplitudes, bandwidths)
+  spec = interaction_spec(kind, amplitudes, bandwidths, exponents)
   N = x3.shape[1]
   dev, one, (x3, _) = _stage(x, x3, x3[:, :0])
   sums, pot, force = _call(spec, x3, None, want_field, want_grad)
@@ -124,7 +197,7 @@ def interaction_energy(x, kind, amplitudes=None, bandwidths=None, want_grad=Fals
   return out
 
 
-def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, want_force=True) -> dict:
+def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, want_force=True, exponents=None) -> dict:
   """The field of the sources [N, D] or [S, N, D] at the points [Q, D] or [S, Q, D] (set s against set s), ONE fused
   cnf_interaction call in query mode (nothing is skipped): potential [S, Q] (float32; [Q] for 2-D points) =
   (W * rho)(q_i) = mean_j W(q_i - x_j), with want_force force [S, Q, D] = grad (W * rho)(q_i) -- what a particle method
@@ -132,7 +205,7 @@ def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, w
   work for what the C ABI refuses and for points and sources that differ in S or D."""
   q3, x3 = _sets("interaction", points, "points"), _sets("interaction", sources, "sources")
   interaction_check_shapes(x3.shape, tuple(q3.shape))
-  spec = interaction_spec(kind, amplitudes, bandwidths)
+  spec = interaction_spec(kind, amplitudes, bandwidths, exponents)
   dev, one, (q3, x3) = _stage(points, q3, x3)
   sums, pot, force = _call(spec, x3, q3, True, want_force)
   out = {"potential": _unstack(pot, one), "sums": sums}
@@ -145,8 +218,17 @@ def interaction_field(points, sources, kind, amplitudes=None, bandwidths=None, w
 
 def interaction_vjp_check_spec(spec):
   """ValueError for what cnf_interaction_vjp refuses in a spec that `interaction_spec` accepted: a pair-Hessian
-  coefficient amp / bw^4 (Gaussian) or amp / bw^2 (exponential) outside float32's range."""
+  coefficient amp / bw^4 (Gaussian), amp / bw^2 (exponential) or amp (p - 2) eps^(p - 4) (power; none for p = 2) outside
+  float32's range."""
   if spec.kind == _capi.INTERACTION_KINDS["quadratic"]:
+    return spec
+  if spec.kind == _capi.INTERACTION_KINDS["power"]:
+    eps = float(spec.bw[0])
+    for b in range(spec.n_terms):
+      a, p = float(spec.amp[b]), float(spec.pw[b])
+      if p != 2.0 and not (_fits(a * (p - 2.0) * _pow(eps, p - 4.0)) and _fits(a * (p - 2.0))):
+        raise ValueError(f"interaction: amp (p - 2) eps^(p - 4) (the pair Hessian's coefficient) leaves float32's range: "
+                         f"{a}, {p}, eps {eps}")
     return spec
   power = 4 if spec.kind == _capi.INTERACTION_KINDS["gaussian"] else 2
   for b in range(spec.n_terms):
@@ -182,7 +264,7 @@ def force_vjp_of_sets(spec, x3, g3):
   return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def interaction_force_vjp(x, g, kind, amplitudes=None, bandwidths=None):
+def interaction_force_vjp(x, g, kind, amplitudes=None, bandwidths=None, exponents=None):
   """The vector-Jacobian product of the self-mode force f_i = (1 / (N - 1)) sum_{j != i} grad W(x_i - x_j) of the point
   sets x [N, D] or [S, N, D] (what utils.interaction_energy's grad is, times N) with the adjoint g of the same shape:
     xbar_k = (1 / (N - 1)) sum_{j != k} H(x_k - x_j) (g_k - g_j),   H the pair Hessian of W,
@@ -195,6 +277,6 @@ def interaction_force_vjp(x, g, kind, amplitudes=None, bandwidths=None):
   interaction_check_shapes((min(x3.shape[0], _capi.MMD_MAX_SETS),) + tuple(x3.shape[1:]))
   if tuple(g3.shape) != tuple(x3.shape):
     raise ValueError(f"interaction: the force's adjoint must have the points' shape {tuple(x3.shape)}, not {tuple(g3.shape)}")
-  spec = interaction_vjp_check_spec(interaction_spec(kind, amplitudes, bandwidths))
+  spec = interaction_vjp_check_spec(interaction_spec(kind, amplitudes, bandwidths, exponents))
   dev, one, (x3, g3) = _stage(x, x3, g3)
   return _unstack(force_vjp_of_sets(spec, x3, g3), one)

@@ -34,7 +34,8 @@ DEFAULT_CONFIG: Dict[str, Dict[str, Any]] = {
   "cnf": {"flow_num_layers": 2, "mlp_num_layers": 2, "hidden_size": 16, "num_bins": 5},
   "train": {"epochs": 30000, "lr": 0.001, "_lambda": 5000.0, "batch_size": 2048, "eval_frequency": 100},
   # not in the reference: a nonlocal running cost strength * int_0^T F(rho_t) dt for ot and rwpo, F the interaction energy
-  # of utils.interaction_energy (kind "none": no such cost; "gaussian", "exponential", "quadratic": utils.interaction_spec).
+  # of utils.interaction_energy (kind "none": no such cost; "gaussian", "exponential", "quadratic", "power": utils.interaction_spec;
+  # "power" reads the optional key `exponents` and takes `bandwidths` as its one softening length).
   # An optional key `role` (absent: "cost"): "drift" puts -strength grad (W * rho) into fp's drift instead (bind_loss)
   "interaction": {"kind": "none", "strength": 1.0, "amplitudes": [1.0], "bandwidths": [1.0]},
 }
@@ -111,8 +112,11 @@ def _interaction_kind(config) -> str:
 def _interaction_kwargs(config) -> Dict[str, Any]:
   """utils.interaction_spec's arguments from the config's `interaction` section"""
   i = config["interaction"]
-  return {"kind": i["kind"], "amplitudes": i.get("amplitudes"),
-          "bandwidths": None if i["kind"] == "quadratic" else i.get("bandwidths")}
+  kw = {"kind": i["kind"], "amplitudes": i.get("amplitudes"),
+        "bandwidths": None if i["kind"] == "quadratic" else i.get("bandwidths")}
+  if i.get("exponents") is not None:       # (the power kind's; utils.interaction_spec refuses it for the others)
+    kw["exponents"] = i["exponents"]
+  return kw
 
 
 @dataclass
@@ -685,7 +689,8 @@ def print_interaction(res: Dict[str, Any]) -> None:
 # ---- the particle reference of an fp problem with an interaction: what the interacting training term is held to ------
 
 MV_REFERENCE_KEYS = ("times", "mean", "trace_cov", "free_mean", "free_trace_cov", "trace_cov_floor", "energy",
-                     "energy_floor", "bad", "trace_cov_exact", "kind", "strength", "n", "replicas")
+                     "energy_floor", "bad", "trace_cov_exact", "second_moment", "second_moment_exact", "kind", "strength",
+                     "n", "replicas")
 
 
 def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1e-3, seed=0) -> Dict[str, Any]:
@@ -705,6 +710,10 @@ def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1
     bad                        particles that were not finite
     trace_cov_exact            drift ou with the quadratic kernel: dim * applications.mv_quadratic_ou_variance, the
                                mean-field limit (the ensemble's h-bias and 1 / N are not in it); else None
+    second_moment_exact        the power kind with a single log term (exponent 0) and no drift (ou with a = 0):
+                               applications.mv_log_second_moment, E mean |x|^2 of the UNSOFTENED kernel, exact for every
+                               N (the softening lowers the force's share by the pair mean of eps^2 / (d^2 + eps^2));
+                               beside it second_moment = tr cov + |mean|^2 of the ensemble; else both None
   and kind, strength, n (particles per replica), replicas.  ValueError, before any device work, for what _fp_prelude
   refuses, an interaction kind "none", fewer than 2 replicas and what mv_reference_particles refuses."""
   name = "evaluate_mv_reference"
@@ -725,7 +734,14 @@ def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1
     amp = float(np.float32(kw["amplitudes"][0] if kw["amplitudes"] is not None else 1.0))
     var0 = applications.fp_initial_variance(T)
     exact = [dim * applications.mv_quadratic_ou_variance(float(t), a, sigma, strength, amp, var0) for t in ts]
-  return {"times": [float(t) for t in ts],
+  m2 = m2_exact = None
+  pws = kw.get("exponents")
+  if sub == "ou" and float(a) == 0.0 and kind == "power" and pws is not None and [float(p) for p in np.ravel(pws)] == [0.0]:
+    amp = float(np.float32(np.ravel(kw["amplitudes"])[0] if kw["amplitudes"] is not None else 1.0))
+    m0 = dim * applications.fp_initial_variance(T)
+    m2_exact = [applications.mv_log_second_moment(float(t), dim, sigma, strength, amp, m0) for t in ts]
+    m2 = (tr(mv["cov"]) + (mv["mean"] ** 2).sum(-1)).tolist()      # (cov is the population's: sum x x^T / n - mean mean^T)
+  return {"times": [float(t) for t in ts], "second_moment": m2, "second_moment_exact": m2_exact,
           "mean": mv["mean"].tolist(), "trace_cov": tr(mv["cov"]).tolist(),
           "free_mean": free["mean"].tolist(), "free_trace_cov": tr(free["cov"]).tolist(),
           "trace_cov_floor": (rep_tr.max(1).values - rep_tr.min(1).values).tolist(),
@@ -737,14 +753,17 @@ def evaluate_mv_reference(config, times=None, n_particles=16384, replicas=2, h=1
 def print_mv_reference(res: Dict[str, Any]) -> None:
   """evaluate_mv_reference's table, one line per time"""
   exact = res["trace_cov_exact"] is not None
+  virial = res.get("second_moment_exact") is not None
   print("interacting particle reference ({} kernel, strength {}, {} replicas of {}):  t | |mean| | tr cov | floor | "
-        "tr cov without the force | F | floor | bad{}".format(res["kind"], res["strength"], res["replicas"], res["n"],
-                                                              " | tr cov, mean-field limit" if exact else ""))
+        "tr cov without the force | F | floor | bad{}{}".format(
+          res["kind"], res["strength"], res["replicas"], res["n"], " | tr cov, mean-field limit" if exact else "",
+          " | mean |x|^2 | log kernel's closed form (no softening)" if virial else ""))
   for i, t in enumerate(res["times"]):
     print("  {:.4f} | {:.3e} | {:.6f} | {:.2e} | {:.6f} | {:.6e} | {:.2e} | {:.0f}".format(
       t, float(np.linalg.norm(res["mean"][i])), res["trace_cov"][i], res["trace_cov_floor"][i],
       res["free_trace_cov"][i], res["energy"][i], res["energy_floor"][i], res["bad"][i])
-      + (" | {:.6f}".format(res["trace_cov_exact"][i]) if exact else ""))
+      + (" | {:.6f}".format(res["trace_cov_exact"][i]) if exact else "")
+      + (" | {:.6f} | {:.6f}".format(res["second_moment"][i], res["second_moment_exact"][i]) if virial else ""))
 
 
 # ---- a flow trained on the interacting fp problem beside the particle reference ---------------------------------------

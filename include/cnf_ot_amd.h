@@ -929,6 +929,15 @@ int cnf_knn(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int
  *   kind CNF_INTERACTION_EXPONENTIAL:  W = sum_b amp_b exp(-r / bw_b)           (Morse: n_terms = 2, amp = (C_r, -C_a));
  *                                      grad W is 0 at a coincident pair (r^2 <= 1e-30)
  *   kind CNF_INTERACTION_QUADRATIC:    W = amp_0 r^2 / 2                        (n_terms and bw are ignored)
+ *   kind CNF_INTERACTION_POWER:        W = sum_b amp_b u^(pw_b / 2) / pw_b (pw_b != 0) + sum_b amp_b ln(u) / 2 (pw_b == 0),
+ *                                      u = r^2 + eps^2, eps = bw[0] ONE softening length (Plummer; bw[1..] are ignored), so
+ *                                      grad W = (x - y) sum_b amp_b u^(pw_b / 2 - 1): softened power laws and the log kernel,
+ *                                      which the force passes through continuously at pw = 0.  pw = 2 - D: Newtonian /
+ *                                      Coulomb; pw = 0: log (Keller-Segel, log-gases); two terms of opposite sign: an
+ *                                      attractive-repulsive power law r^a / a - r^b / b; pw = 2, eps = 0: the quadratic
+ *                                      kind.  eps = 0 only with every pw_b >= 2; a coincident pair then contributes
+ *                                      W(0) = 0 and a zero force.  u is clamped below at 1e-30, the unit's rule for
+ *                                      a coincident pair: an eps below 1e-15 acts as that clamp at r = 0
  * For S independent sets x [S, N, D] (device, float32), one entry with two modes:
  *   self mode  (q == NULL, Q == 0): the rows are the particles themselves; the pair i == j is skipped by INDEX (a
  *              duplicate of x_i at another index does interact); n = N - 1;
@@ -951,17 +960,23 @@ int cnf_knn(int32_t S, const float *x, int64_t N, const float *y, int64_t M, int
  * given with Q == 0; S outside 1..64; D outside 1..14; N outside 2..2^20; Q outside 1..2^20 and not 0; an unknown
  * kind; n_terms outside 1..4; an amp that is zero or not finite; a bw that is not positive and finite, whose 1 / bw^2
  * leaves float32's range or for which amp / bw^2 (Gaussian) or amp / bw (exponential) does; a workspace smaller than
- * cnf_interaction_workspace says.
- * Out of scope: weighted particles, kernels singular at 0 (Coulomb, log), more than one rank, D > 14, N > 2^20. */
+ * cnf_interaction_workspace says.  For the power kind: a pw that is not finite or has |pw| > 16; an eps = bw[0] that is
+ * negative or not finite, or 0 unless every pw_b >= 2; a force coefficient amp_b eps^(pw_b - 2) or a value coefficient
+ * amp_b eps^pw_b / pw_b (pw_b = 0: amp_b ln eps; also amp_b eps^(pw_b - 2) / pw_b, the value's sum before its factor u)
+ * outside float32's range.
+ * Out of scope: weighted particles, truly singular kernels (eps = 0 with a pw < 2), per-term softening lengths, more
+ * than one rank, D > 14, N > 2^20. */
 #define CNF_INTERACTION_MAX_TERMS 4
 typedef enum {
-  CNF_INTERACTION_GAUSSIAN = 0, CNF_INTERACTION_EXPONENTIAL = 1, CNF_INTERACTION_QUADRATIC = 2
+  CNF_INTERACTION_GAUSSIAN = 0, CNF_INTERACTION_EXPONENTIAL = 1, CNF_INTERACTION_QUADRATIC = 2,
+  CNF_INTERACTION_POWER = 4     /* (3 is not a kind) */
 } CnfInteractionKind;
 typedef struct CnfInteractionSpec {
   int32_t kind;                 /* CnfInteractionKind                                     */
   int32_t n_terms;              /* 1 .. CNF_INTERACTION_MAX_TERMS; quadratic: ignored     */
   float amp[CNF_INTERACTION_MAX_TERMS];
-  float bw[CNF_INTERACTION_MAX_TERMS];
+  float bw[CNF_INTERACTION_MAX_TERMS];   /* power: bw[0] = the softening length eps          */
+  float pw[CNF_INTERACTION_MAX_TERMS];   /* power: the exponents; the other kinds ignore it  */
 } CnfInteractionSpec;
 int cnf_interaction_workspace(int32_t S, int64_t N, int64_t Q, int32_t D, int32_t want_rows,
                               int64_t *bytes);
@@ -980,6 +995,7 @@ int cnf_interaction(const CnfInteractionSpec *spec, int32_t S, const float *x, i
  *   exponential:  c1 = w / r,  c2 = w' / r^2 - w / r^3,  w = sum_b (-amp_b / bw_b) e_b,  w' = sum_b (amp_b / bw_b^2) e_b;
  *                 both 0 at a coincident pair (r^2 <= 1e-30), the force's own rule
  *   quadratic:    c1 = amp_0,  c2 = 0
+ *   power:        c1 = sum_b amp_b u^(pw_b / 2 - 1),  c2 = sum_b amp_b (pw_b - 2) u^(pw_b / 2 - 2),  u = r^2 + eps^2
  * the exact gradient of sum_i g_i . f_i in x for fixed g.  (For the exponential kind in dimension 1 it does not contain
  * the delta term of the kink of W at 0: the discrete objective has none.)  The pair j == k contributes 0 by itself.
  * Built as cnf_interaction's pair pass: the same workgroup geometry and cnf_interaction_splits(S, N, 0, D) column
@@ -988,8 +1004,9 @@ int cnf_interaction(const CnfInteractionSpec *spec, int32_t S, const float *x, i
  * argument; the workspace (cnf_interaction_vjp_workspace bytes, 8-byte aligned) is the caller's: no allocation, no
  * synchronisation (legal inside a stream capture).
  * Checks come first.  CNF_ERR_INVALID, nothing enqueued: everything cnf_interaction refuses in self mode (spec, S, N,
- * D), a NULL g or xbar, a Hessian coefficient amp / bw^4 (Gaussian) or amp / bw^2 (exponential) outside float32's
- * range, a workspace smaller than cnf_interaction_vjp_workspace says.
+ * D), a NULL g or xbar, a Hessian coefficient amp / bw^4 (Gaussian), amp / bw^2 (exponential) or amp_b (pw_b - 2)
+ * eps^(pw_b - 4) (power; none for pw_b = 2) outside float32's range, a workspace smaller than
+ * cnf_interaction_vjp_workspace says.
  * Out of scope: query mode, more than one rank. */
 int cnf_interaction_vjp_workspace(int32_t S, int64_t N, int32_t D, int64_t *bytes);
 int cnf_interaction_vjp(const CnfInteractionSpec *spec, int32_t S, const float *x, const float *g,
@@ -1030,7 +1047,8 @@ int cnf_interaction_vjp(const CnfInteractionSpec *spec, int32_t S, const float *
  * cnf_interaction (a NULL or bad spec, D outside 1..14, N outside 2..2^20, R outside 1..64); a kappa that is not
  * finite; a NULL state, sums or workspace or a workspace that is too small; a stream element index
  * (first_particle + R N) (n_steps + 1) D, rounded up, that would not fit in 63 bits.
- * Out of scope: more than one rank, weighted particles, kernels singular at 0, float64 pair forces, N > 2^20. */
+ * Out of scope: more than one rank, weighted particles, truly singular kernels (the power kind with eps = 0 and a
+ * pw < 2), per-term softening lengths, float64 pair forces, the captured step, N > 2^20. */
 int cnf_mv_particles_workspace(int32_t R, int64_t N, int32_t D, int32_t S, int64_t *bytes);
 int cnf_mv_particles(const CnfInteractionSpec *spec, double kappa, int32_t drift, int32_t D, float a,
                      double sigma, double h, int64_t n_steps, double var0, uint64_t seed,

@@ -1,8 +1,8 @@
 """cnf_interaction (the interaction energy of all sets, its field and its force: one pair launch and a merge launch)
 against its torch composition -- per set a pair matrix from direct differences in float32, reduced in float64, which is
 what utils.interaction_energy replaces -- and beside cnf_mmd2 (Gaussian, the same number of terms, with its gradient) on
-the same clouds, whose pair loop this one is built from.  Shapes, at D = 2 and D = 10 and for the three kinds (Gaussian
-and exponential with two signed terms):
+the same clouds, whose pair loop this one is built from.  Shapes, at D = 2 and D = 10 and for the kinds of KINDS (Gaussian
+and exponential with two signed terms, quadratic, and the power kind: exponents 4 and 1, and the log kernel):
   config3   S = 32 sets of N = 4 096 (batch 131 072 // 32 at 32 time slices), with the force: the training term's call
   default   S = 1, N = 64 (batch 2 048 // 32 at one slice), with the force: this measures launch overheads, not pairs
   eval      S = 9, N = 32 768: solvers.evaluate_interaction's shape at n = 65 536; the energy alone
@@ -36,7 +36,28 @@ from cnf_ot_amd.flows import _stream_ptr
 SHAPES = {"config3": (32, 4096, True), "default": (1, 64, True), "eval": (9, 32768, False), "config3x2": (64, 4096, True),
           "eval_force": (9, 32768, True)}
 DEFAULT_SHAPES = ["config3", "default", "eval"]
-KINDS = {"gaussian": ([1.0, -0.5], [1.0, 2.0]), "exponential": ([1.0, -0.5], [0.5, 2.0]), "quadratic": ([1.0], None)}
+# kind -> (amplitudes, bandwidths); "power" and "power_log" are the spec kind "power" with POWER_EXPONENTS and ONE
+# softening length: an attractive-repulsive pair r^4 / 4 - r and the log kernel
+KINDS = {"gaussian": ([1.0, -0.5], [1.0, 2.0]), "exponential": ([1.0, -0.5], [0.5, 2.0]), "quadratic": ([1.0], None),
+         "power": ([1.0, -1.0], [0.05]), "power_log": ([1.0], [0.1])}
+POWER_EXPONENTS = {"power": [4.0, 1.0], "power_log": [0.0]}
+
+
+def spec_kwargs(kind, amps, bws):
+  """utils.interaction_spec's arguments for a kind of KINDS"""
+  if kind in POWER_EXPONENTS:
+    return dict(kind="power", amplitudes=amps, bandwidths=bws, exponents=POWER_EXPONENTS[kind])
+  return dict(kind=kind, amplitudes=amps, bandwidths=bws)
+
+
+def power_terms(d2, kind, amps, bws):
+  """(W, w) of a power kind at the squared distances d2 (torch, float32): grad W = diff w"""
+  u = d2 + bws[0] * bws[0]
+  W, w = torch.zeros_like(d2), torch.zeros_like(d2)
+  for a, p in zip(amps, POWER_EXPONENTS[kind]):
+    W = W + (0.5 * a * torch.log(u) if p == 0.0 else (a / p) * u ** (0.5 * p))
+    w = w + a * u ** (0.5 * p - 1.0)
+  return W, w
 
 
 def interleaved_ms(fns, runs, warmup):
@@ -58,7 +79,7 @@ def interleaved_ms(fns, runs, warmup):
 
 
 def fused_call(dev, x, kind, amps, bws, want_force):
-  spec = utils.interaction_spec(kind, amps, bws)
+  spec = utils.interaction_spec(**spec_kwargs(kind, amps, bws))
   S, N, D = x.shape
   lib = _capi.lib()
   nbytes = ctypes.c_int64(0)
@@ -103,6 +124,8 @@ def composed_set(x, kind, amps, bws, want_force, rows):
     d2 = (diff * diff).sum(-1)
     if kind == "quadratic":
       W, w = (0.5 * amps[0]) * d2, None
+    elif kind in POWER_EXPONENTS:
+      W, w = power_terms(d2, kind, amps, bws)
     else:
       W, w = torch.zeros_like(d2), torch.zeros_like(d2)
       r = torch.sqrt(d2) if kind == "exponential" else None

@@ -2,7 +2,7 @@
 the force on the same clouds, whose pair loop it is built from, and against its torch composition: per set the force as
 the autograd gradient of the float32 pair energy (create_graph) and a second backward of sum g . f through it -- a double
 backward through the N x N x D pair tensor, which is what utils.interaction_force_vjp replaces.  Shapes, at D = 2 and 10
-and for the three kinds (Gaussian and exponential with two signed terms):
+and for interaction_probe's kinds (Gaussian and exponential with two signed terms, quadratic, the power kind):
   config3   S = 32 sets of N = 4 096 (batch 131 072 // 32 at 32 time slices)
   eval      S = 9, N = 32 768
 Then (--steps) value_and_grad of the interacting fp step, beside the same configuration without the interaction and
@@ -27,7 +27,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from interaction_probe import KINDS, fused_call, interleaved_ms
+from interaction_probe import KINDS, POWER_EXPONENTS, fused_call, interleaved_ms, power_terms, spec_kwargs
 from cnf_ot_amd import _capi, applications as app, interaction as ia, utils
 from cnf_ot_amd.flows import _stream_ptr
 
@@ -35,7 +35,7 @@ SHAPES = {"config3": (32, 4096), "eval": (9, 32768)}
 
 
 def vjp_call(dev, x, g, kind, amps, bws):
-  spec = utils.interaction_spec(kind, amps, bws)
+  spec = ia.interaction_vjp_check_spec(utils.interaction_spec(**spec_kwargs(kind, amps, bws)))
   S, N, D = x.shape
   lib = _capi.lib()
   nbytes = ctypes.c_int64(0)
@@ -56,6 +56,11 @@ def _pair_energy(a, b, kind, amps, bws, skip0):
   d2 = (diff * diff).sum(-1)
   if kind == "quadratic":
     W = (0.5 * amps[0]) * d2
+  elif kind in POWER_EXPONENTS:            # (eps > 0: the pair i == i is smooth, and masked like the others)
+    idx = torch.arange(len(a), device=a.device)
+    mask = torch.ones_like(d2, dtype=torch.bool)
+    mask[idx, skip0 + idx] = False
+    W = torch.where(mask, power_terms(d2, kind, amps, bws)[0], torch.zeros_like(d2))
   else:
     idx = torch.arange(len(a), device=a.device)
     mask = torch.ones_like(d2, dtype=torch.bool)
@@ -133,7 +138,7 @@ def step_cases(dev, args, rows_out):
     model, params = FlowModel(cfg), Params.random(cfg, scale, seed=42, device=dev)
     for kind in args.kinds:
       amps, bws = KINDS[kind]
-      kw = {"kind": kind, "amplitudes": amps, "bandwidths": bws}
+      kw = spec_kwargs(kind, amps, bws)
       rows = max(1, min(B // 32, args.chunk_mb * (1 << 20) // (4 * (B // 32) * D * 8)))
       loss = lambda p, rng, **k: app.fp_loss_fn(model, D, 1.0, 1.0, 0.5, 0.01, 0.01, tbs, sub, p, rng, 5000.0, B, **k)
       vg = app.value_and_grad(loss)

@@ -6,7 +6,7 @@ against what it replaces and against what it is built from, in one run:
                 fused stepper is that call with the finish launch replaced by the step launch, so it should cost about
                 one such call
 Shape: R = 2 replicas of N = 16 384, D = 2 and D = 10, 1 000 steps of h = 1e-3, drift ou, a Gaussian kernel with two
-signed terms; the fused call takes ONE snapshot, at the last step (sums alone).
+signed terms (--kernel log: the softened log kernel of the power kind); the fused call takes ONE snapshot, at the last step (sums alone).
 
 Timing: HIP events around the whole of each route (all its steps), after --warmup rounds (default 1); the three routes
 are timed INTERLEAVED (one run of each in turn, --runs of them, default 5); medians with min and max; buffers are
@@ -30,7 +30,9 @@ from interaction_probe import interleaved_ms
 from cnf_ot_amd import _capi, utils
 from cnf_ot_amd.flows import _stream_ptr
 
-KERNEL = dict(kind="gaussian", amplitudes=[1.0, -0.5], bandwidths=[1.0, 2.0])
+KERNELS = {"gaussian": dict(kind="gaussian", amplitudes=[1.0, -0.5], bandwidths=[1.0, 2.0]),
+           "log": dict(kind="power", amplitudes=[1.0], bandwidths=0.1, exponents=[0.0])}
+KERNEL = KERNELS["gaussian"]             # (--kernel replaces it)
 A, SIGMA, KAPPA, VAR0 = 1.0, 0.5, 1.5, 1.0
 
 
@@ -90,12 +92,15 @@ def main():
   ap.add_argument("--particles", type=int, default=16384)
   ap.add_argument("--steps", type=int, default=1000)
   ap.add_argument("--h", type=float, default=1e-3)
+  ap.add_argument("--kernel", default="gaussian", choices=list(KERNELS))
   ap.add_argument("--runs", type=int, default=5)
   ap.add_argument("--warmup", type=int, default=1)
   ap.add_argument("--out", default=None)
   args = ap.parse_args()
   assert torch.cuda.is_available(), "mv_particles_probe measures on the GPU; there is no fall-back"
   dev = torch.device("cuda", 0)
+  global KERNEL
+  KERNEL = KERNELS[args.kernel]
   R, N, steps = args.replicas, args.particles, args.steps
   rows = []
   for D in args.dims:
