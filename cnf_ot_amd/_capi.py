@@ -84,6 +84,17 @@ class CnfInteractionSpec(ctypes.Structure):
               ("bw", ctypes.c_float * INTERACTION_MAX_TERMS), ("pw", ctypes.c_float * INTERACTION_MAX_TERMS)]
 
 
+STEIN_MAX_TERMS = 4
+STEIN_KINDS = {"imq": 1, "gaussian": 2}
+
+
+class CnfSteinSpec(ctypes.Structure):
+  """The base kernel of cnf_stein (include/cnf_ot_amd.h): kind 1 = a sum of inverse multiquadrics w_b (bw_b^2 + r^2)^beta,
+  2 = a sum of Gaussians w_b exp(-r^2 / (2 bw_b^2))."""
+  _fields_ = [("kind", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("w", ctypes.c_float * STEIN_MAX_TERMS),
+              ("bw", ctypes.c_float * STEIN_MAX_TERMS), ("beta", ctypes.c_float)]
+
+
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
 TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
@@ -217,6 +228,12 @@ SYMBOLS = {
   "cnf_interaction_vjp_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),
   "cnf_interaction_vjp": (ctypes.c_int, [ctypes.POINTER(CnfInteractionSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P,
                                          _P, _I64, _P]),
+  # the kernel Stein discrepancy of x [S, N, D] against the score [S, N, D]: sums [S, 2] doubles, rows [S, N] or NULL,
+  # grad_x and grad_s [S, N, D], both or neither
+  "cnf_stein_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_stein_splits": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32]),
+  "cnf_stein": (ctypes.c_int, [ctypes.POINTER(CnfSteinSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P, _P, _P, _P,
+                               _P, _I64, _P]),
   # the interacting (McKean-Vlasov) particle reference: R replicas of N particles (snap_step: a host array); state
   # [R, N, D], sums [S, R, 3 + D + D D] doubles, pos [S, R, N, D] and hist [S, ny, nx] each or NULL
   "cnf_mv_particles_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),

@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _capi, two_sample
+from . import _capi, stein, two_sample
 from . import interaction as ia      # (the composites take a keyword of that name)
 from .distributed import Shard, all_reduce_sums, current_shard, shard_range
 from .flows import DeviceRng, FlowEngine, _OnDevice, _stream_ptr, seed_to_u64
@@ -1080,6 +1080,33 @@ def mv_reference_particles(dim, T, a, sigma, subtype, interaction, strength, tim
   return out
 
 
+def mv_stationary_score(x, a, sigma, subtype, interaction, strength):
+  """The score a stationary law of the interacting fp equation has at its own points x [N, D] or [S, N, D]: zero
+  current, sigma grad log rho = drift - strength grad (W * rho), with the empirical measure of x for rho:
+    (drift(x_i) - strength mean_{j != i} grad W(x_i - x_j)) / sigma,
+  the drift "ou" (-a x), the force by autograd.interaction_force (self mode, the pair kernel of `interaction`: the
+  keyword arguments of utils.interaction_spec), so the result is differentiable in x.  float32 on x's device.  The KSD
+  of x against it (utils.ksd) is a stationarity residual of an ensemble, or of the flow's samples at a large time.
+  ValueError before any device work for an unknown drift, a drift other than "ou" (the zero-current identity needs a
+  gradient drift; the other drifts' stationary laws carry a current), a sigma that is not positive and finite, an a or a
+  strength that is not finite and what utils.interaction_spec refuses."""
+  from . import autograd
+  name = "mv_stationary_score"
+  if subtype not in _capi.DRIFTS:
+    raise ValueError(f"unknown drift {subtype!r}")
+  if subtype != "ou":
+    raise ValueError(f"{name}: only the drift 'ou': the zero-current identity needs a gradient drift, not {subtype!r}")
+  if not (float(sigma) > 0.0 and math.isfinite(float(sigma))) or not math.isfinite(float(a)):
+    raise ValueError(f"{name}: needs sigma > 0 and a finite a, not {sigma}, {a}")
+  if not math.isfinite(float(strength)):
+    raise ValueError(f"{name}: the strength must be finite, not {strength}")
+  kw = dict(interaction)
+  ia.interaction_vjp_check_spec(ia.interaction_spec(**kw))
+  x = torch.as_tensor(x)
+  force = autograd.interaction_force(x, **kw)
+  return (-float(a) * x.to(device=force.device, dtype=torch.float32) - float(strength) * force) * (1.0 / float(sigma))
+
+
 # ---- importance-sampling diagnostics against the densities known in closed form -------------------------------------
 # The reference's kl_ess (tests/test_fit_prob.py:50-56, "metrics used in the tori paper"): draw y from the flow, weight
 # w = p_target(y) / q_flow(y), report Z = mean w, KL = mean(log q - log p) + log Z, ESS = (sum w)^2 / sum w^2.  It
@@ -1142,6 +1169,20 @@ class GaussianMixtureTarget:
         s.W[i][j] = W[i, j]
     s.log_det_W = self.log_det_W
     s.scale = None
+
+  def score(self, x, scale=None):
+    """grad log p at the points x [..., D], in torch and differentiable in x, in x's dtype and on its device: with the
+    responsibilities r_m(x) of the components, -sum_m r_m cov^-1 (x - means[m]) / scale (scale: the covariance's factor,
+    None = 1).  What `ksd` compares a point set against."""
+    x = torch.as_tensor(x)
+    if x.shape[-1] != self.dim:
+      raise ValueError(f"GaussianMixtureTarget.score: points of dimension {self.dim}, not {tuple(x.shape)}")
+    kw = dict(dtype=x.dtype, device=x.device)
+    inv = 1.0 if scale is None else 1.0 / float(scale)
+    W, mu = torch.as_tensor(self.W, **kw), torch.as_tensor(self.means, **kw)
+    y = (x[..., None, :] - mu) @ W.T                                    # [..., n_comp, D]: W (x - mu_m)
+    r = torch.softmax(torch.as_tensor(self.log_weights, **kw) - 0.5 * inv * (y * y).sum(-1), dim=-1)
+    return -inv * ((r[..., None] * y).sum(-2) @ W)
 
 
 # the times of the fp figure (solvers.FIGURE_SETTINGS[("fp", None, 2)]): where fp / ou reports its fit along the path
@@ -1371,6 +1412,53 @@ def interaction_loss_fn(model, dim, params, cond, rng, batch_size, kind, amplitu
     return ia.energy_of_sets(spec, samples, want_grad)
   return _sample_term("interaction_loss_fn", "pairs across ranks need", model, params, None, cond, rng, batch_size, shard,
                       grad, refuse, stat)
+
+
+# ---- a target known through its score alone: the kernel Stein discrepancy of the flow's own samples -------------------
+
+def ksd_loss_fn(model, dim, params, target, cond, rng, batch_size, kind="imq", bandwidths=None, beta=-0.5, weights=None,
+                scale=None, shard=None, grad=None):
+  """The mean over the times of `cond` of the kernel Stein discrepancy KSD^2_U (utils.ksd: kind, bandwidths, beta and
+  weights are utils.stein_spec's; bandwidths=None: utils.median_bandwidths of the first time's samples) of batch_size
+  flow samples at that time -- the same base draw of `rng` for every time, as the other sample terms -- against the law
+  whose score `target` gives: an object with .score(x, scale) (GaussianMixtureTarget; `scale` is passed on) or a
+  callable x [S, B, D] -> the score at x, built from torch ops where it depends on x.  A fitting term for a target
+  known up to its constant, from no samples of it.  With `grad` (the convention of the other term functions;
+  `value_and_grad` supplies it) the sample gradient is cnf_stein's grad_x plus the score's vector-Jacobian product of
+  its grad_score, taken by torch autograd, and the parameter gradient is accumulated by ONE cnf_stein call per 64 times
+  and ONE cnf_pass_vjp call.  Single rank: the pairs across ranks would need an all-gather of the samples, so a shard
+  (or a torch.distributed world) of more than one rank raises ValueError, as do a DeviceRng (the captured step) and a
+  terms backend that is not the HIP engine."""
+  name = "ksd_loss_fn"
+  if isinstance(rng, DeviceRng):
+    raise ValueError(f"{name}: for the eager update only (the captured step draws on the device)")
+  if hasattr(target, "score"):
+    score_fn = lambda x: target.score(x, scale)
+  elif callable(target):
+    score_fn = target
+  else:
+    raise ValueError(f"{name}: target must have a .score(x, scale) or be a callable x -> score, not {type(target).__name__}")
+
+  def refuse(S, _):      # -> the spec, or None while the bandwidths wait for the samples
+    stein.stein_check_shapes((min(S, _capi.MMD_MAX_SETS), int(batch_size), int(dim)))
+    # (kind, beta and the weights are checked either way: the median heuristic gives STEIN_MAX_TERMS bandwidths)
+    spec = stein.stein_spec(kind, [1.0] * stein.STEIN_MAX_TERMS if bandwidths is None else bandwidths, beta, weights)
+    return None if bandwidths is None else spec
+
+  def stat(samples, _, spec, want_grad):
+    if spec is None:
+      spec = stein.stein_spec(kind, two_sample.median_bandwidths(samples)[:stein.STEIN_MAX_TERMS], beta, weights)
+    xs = samples.detach().requires_grad_(want_grad)
+    with torch.enable_grad():
+      sc = score_fn(xs)
+    if tuple(sc.shape) != tuple(xs.shape):
+      raise ValueError(f"{name}: the score must have the samples' shape {tuple(xs.shape)}, not {tuple(sc.shape)}")
+    s3 = sc.detach().to(dtype=torch.float32).contiguous()
+    values, gx, gs = stein.ksd_of_sets(spec, samples.detach().contiguous(), s3, want_grad)
+    if want_grad and sc.requires_grad:
+      gx = gx + torch.autograd.grad(sc, xs, gs.to(sc.dtype))[0]
+    return values, gx
+  return _sample_term(name, "pairs across ranks need", model, params, None, cond, rng, batch_size, shard, grad, refuse, stat)
 
 
 def _interaction_refuse(name, given, rng, shard, sub, dim):

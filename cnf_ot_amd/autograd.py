@@ -15,7 +15,7 @@ the parameters only; its time derivatives are finite differences).
 """
 import torch
 
-from . import _capi, interaction, two_sample
+from . import _capi, interaction, stein, two_sample
 from .flows import FlowEngine, _stream_ptr
 
 
@@ -171,6 +171,35 @@ def interaction_energy(x: torch.Tensor, kind: str, amplitudes=None, bandwidths=N
   the incoming scalar.  The kernel's amplitudes, bandwidths and exponents are constants.  With `flow_forward` a flow
   trains on the energy through ordinary autograd (applications.interaction_loss_fn is the hand-written fast path)."""
   return _InteractionEnergy.apply(x, kind, amplitudes, bandwidths, exponents)
+
+
+class _Ksd(torch.autograd.Function):
+  """The kernel Stein discrepancy of point sets against a score: the forward call stores both gradients, backward is
+  each times the incoming scalar."""
+
+  @staticmethod
+  def forward(ctx, x, score, kind, bandwidths, beta, weights):
+    need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    res = stein.ksd(x.detach(), score.detach(), kind, bandwidths, beta, weights, want_grad=need)
+    ctx.save_for_backward(res["grad_x"], res["grad_score"])
+    return res["ksd2"]
+
+  @staticmethod
+  def backward(ctx, gbar):
+    gx, gs = ctx.saved_tensors
+    w = gbar.to(torch.float32)
+    scale = lambda g, need: None if g is None or not need else (g * w[:, None, None] if g.dim() == 3 else g * w[0])
+    return scale(gx, ctx.needs_input_grad[0]), scale(gs, ctx.needs_input_grad[1]), None, None, None, None
+
+
+def ksd(x: torch.Tensor, score: torch.Tensor, kind: str = "imq", bandwidths=None, beta: float = -0.5, weights=None):
+  """The kernel Stein discrepancy KSD^2_U (utils.ksd) of the sample sets x [N, D] or [S, N, D] against the law whose
+  score at those points is `score`, [S] float64 ([1] for 2-D inputs), differentiable in x AND in score: with
+  score = f(x) built from torch ops the chain rule runs through both, so a target known up to its constant trains a
+  flow through ordinary autograd (applications.ksd_loss_fn is the hand-written fast path).  Backward is the gradients
+  cnf_stein stored times the incoming scalar.  The kernel's bandwidths (None: utils.median_bandwidths(x), held
+  constant), beta and weights are constants."""
+  return _Ksd.apply(x, score, kind, bandwidths, beta, weights)
 
 
 class _InteractionForce(torch.autograd.Function):

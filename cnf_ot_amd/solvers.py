@@ -9,7 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
-                               [--path-errors] [--fit] [--interaction] [--mv-path]
+                               [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd]
 """
 import argparse
 import sys
@@ -937,6 +937,94 @@ def print_fit(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:+.4e} | {:.4e} | {:.2f} | {:.3f}".format(*row))
 
 
+# ---- sample sets against a score: the kernel Stein discrepancy in the full dimension, with no binning ----------------
+
+KSD_KEYS = ("times", "flow", "floor", "ensemble", "ensemble_flow", "flow_own", "stationary", "kind", "n")
+
+
+def target_draws(target, scale, n, seed):
+  """n exact draws of a GaussianMixtureTarget with its covariance times `scale` (None: 1), [n, D] float32 on the host:
+  numpy's default_rng(seed), the components by their weights."""
+  rng = np.random.default_rng(int(seed))
+  comp = rng.choice(target.n_comp, size=int(n), p=np.exp(target.log_weights))
+  L = np.linalg.inv(target.W) * float(np.sqrt(1.0 if scale is None else float(scale)))
+  return torch.from_numpy((target.means[comp] + rng.standard_normal((int(n), target.dim)) @ L.T).astype(np.float32))
+
+
+def evaluate_ksd(config, model: FlowModel, params: Params, n=8192, seed=0, kind="imq", h=1e-3) -> Dict[str, Any]:
+  """The kernel Stein discrepancy KSD^2_U (utils.ksd, `kind`; the bandwidths are utils.median_bandwidths of the set
+  named first below, one choice per line) of sample sets against scores.  Lists with one entry per (t, target, scale) of
+  applications.known_densities:
+    times
+    flow            n flow samples (model.apply.sample of `seed`) against the closed-form score
+    floor           n exact draws of the target (target_draws of `seed`) against it: two numbers of one size say the
+                    flow's samples are as close to the target as the target's own
+  for fp also, at those times, from the n particles of applications.fp_reference_particles (step h, `seed`):
+    ensemble        the ensemble against the closed-form score (ou: the exact density along the path; else the initial
+                    condition at 0)
+    ensemble_flow   the ensemble against the flow's exact score model.apply.score at the ensemble's points
+    flow_own        the flow's samples against the flow's score at them: the floor of ensemble_flow
+  (None for the other types), and, for fp with an `interaction` section of `role: drift` and the ou drift,
+    stationary      {"flow": ..., "particles": [...]}: the stationarity residual at T, the KSD of the flow's samples and
+                    of every replica of applications.mv_reference_particles (2 replicas of n) against
+                    applications.mv_stationary_score at their own points; else None
+  and kind, n.  ValueError, before any device work, for what utils.stein_check_shapes refuses at n and an unknown kind."""
+  n = int(n)
+  g = config["general"]
+  _type, dim = g["type"], g["dim"]
+  utils.stein_check_shapes((2, n, dim))
+  utils.stein_spec(kind, [1.0])
+  entries = applications.known_densities(config)
+  ts = [float(e[0]) for e in entries]
+  dev = params.flat.device
+  flow = [model.apply.sample(params, cond=t, seed=seed, sample_shape=(n,)).float() for t in ts]
+  one = lambda x, s, bw: float(utils.ksd(x, s, kind, bw)["ksd2"][0])
+  out: Dict[str, Any] = {"times": ts, "flow": [], "floor": [], "ensemble": None, "ensemble_flow": None, "flow_own": None,
+                         "stationary": None, "kind": kind, "n": n}
+  for x, (t, target, scale) in zip(flow, entries):
+    exact = target_draws(target, scale, n, seed).to(dev)
+    bw = utils.median_bandwidths(exact)[:utils.STEIN_MAX_TERMS]
+    both = utils.ksd(torch.stack([x, exact]), torch.stack([target.score(x, scale), target.score(exact, scale)]), kind, bw)
+    out["flow"].append(float(both["ksd2"][0]))
+    out["floor"].append(float(both["ksd2"][1]))
+  if _type != "fp":
+    return out
+  f = config["fp"]
+  T, a, sigma, sub = float(f["T"]), f["a"], f["sigma"], f["velocity_field_type"]
+  pos = applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n, h, seed, positions=True)["pos"].float()
+  out["ensemble"], out["ensemble_flow"], out["flow_own"] = [], [], []
+  for i, (x, (t, target, scale)) in enumerate(zip(flow, entries)):
+    bw = utils.median_bandwidths(pos[i])[:utils.STEIN_MAX_TERMS]
+    out["ensemble"].append(one(pos[i], target.score(pos[i], scale), bw))
+    both = utils.ksd(torch.stack([pos[i], x]), torch.stack([model.apply.score(params, pos[i].contiguous(), cond=t),
+                                                            model.apply.score(params, x.contiguous(), cond=t)]), kind, bw)
+    out["ensemble_flow"].append(float(both["ksd2"][0]))
+    out["flow_own"].append(float(both["ksd2"][1]))
+  if _interaction_kind(config) != "none" and _interaction_role(config) == "drift" and sub == "ou":
+    kw, strength = _interaction_kwargs(config), float(config["interaction"]["strength"])
+    mv = applications.mv_reference_particles(dim, T, a, sigma, sub, kw, strength, [T], n, 2, h, seed, positions=True)["pos"][0]
+    xT = model.apply.sample(params, cond=T, seed=seed, sample_shape=(n,)).float()
+    sets = torch.cat([xT[None], mv.float()])
+    bw = utils.median_bandwidths(sets[1])[:utils.STEIN_MAX_TERMS]
+    res = utils.ksd(sets, applications.mv_stationary_score(sets, a, sigma, sub, kw, strength), kind, bw)["ksd2"].tolist()
+    out["stationary"] = {"flow": res[0], "particles": res[1:]}
+  return out
+
+
+def print_ksd(res: Dict[str, Any]) -> None:
+  """evaluate_ksd's tables, one line per time"""
+  fp = res["ensemble"] is not None
+  print("kernel Stein discrepancy KSD^2_U ({} kernel, {} points per set):  t | flow against the closed-form score | exact "
+        "draws against it{}".format(res["kind"], res["n"], " | ensemble against it | ensemble against the flow's score | "
+                                    "flow against its own score" if fp else ""))
+  for i, t in enumerate(res["times"]):
+    print("  {:.4f} | {:+.4e} | {:+.4e}".format(t, res["flow"][i], res["floor"][i])
+          + (" | {:+.4e} | {:+.4e} | {:+.4e}".format(res["ensemble"][i], res["ensemble_flow"][i], res["flow_own"][i]) if fp else ""))
+  if res["stationary"] is not None:
+    print("stationarity residual at T (KSD^2_U against the zero-current score): flow {:+.4e} | particle replicas {}".format(
+      res["stationary"]["flow"], " ".join("{:+.4e}".format(v) for v in res["stationary"]["particles"])))
+
+
 # ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
 # The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
 # by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
@@ -1026,14 +1114,14 @@ def _eval_rng(seed, step):
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
-         interaction: bool = False, mv_path: bool = False) -> Dict[str, Any]:
+         interaction: bool = False, mv_path: bool = False, ksd: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
-  `interaction` section whose role is drift): print evaluate_mv_path's table."""
+  `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -1112,6 +1200,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_interaction(evaluate_interaction(config, model, params))
   if mv_path:
     print_mv_path(evaluate_mv_path(config, model, params))
+  if ksd:
+    print_ksd(evaluate_ksd(config, model, params))
   return res
 
 
@@ -1147,6 +1237,10 @@ def _parse(argv):
   p.add_argument("--mv-path", action="store_true",
                  help="print the mean, tr cov and interaction energy of the flow's samples beside the interacting particle "
                       "reference and its replica floors (fp with an `interaction` section whose role is drift)")
+  p.add_argument("--ksd", action="store_true",
+                 help="print the kernel Stein discrepancy of the flow's samples against every closed-form score of the "
+                      "problem beside its floor, for fp the particle ensemble against that score and against the flow's "
+                      "exact score, and with an interaction in the ou drift the stationarity residual at T")
   return p.parse_args(argv)
 
 
@@ -1154,4 +1248,4 @@ if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
-       sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path)
+       sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd)

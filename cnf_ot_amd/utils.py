@@ -4,7 +4,8 @@
     loop; here a chunk of slices is ONE fused launch (grid over (slice, sample tile)) that returns one sum per slice;
   - the arrays under its figures (:598-798): density, velocity and score fields, trajectories, and `point_stats`;
   - the distances between two point clouds (mmd2, sinkhorn, sliced_wasserstein and their helpers), which live in
-    `two_sample` and are re-exported here, as is the interaction energy of one cloud (`interaction`).
+    `two_sample` and are re-exported here, as are the interaction energy of one cloud (`interaction`) and the kernel
+    Stein discrepancy of a cloud against a score (`stein`).
 """
 from typing import Optional
 
@@ -24,6 +25,8 @@ from .two_sample import (  # noqa: F401
 from .interaction import (  # noqa: F401
     INTERACTION_KINDS, INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS, interaction_spec, interaction_check_shapes,
     interaction_energy, interaction_field, interaction_force_vjp)
+from .stein import (  # noqa: F401
+    STEIN_KINDS, STEIN_MAX_TERMS, STEIN_MAX_POINTS, stein_spec, stein_check_shapes, ksd)
 
 
 def _model_of(fn_or_model):

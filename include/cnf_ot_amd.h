@@ -1013,6 +1013,50 @@ int cnf_interaction_vjp(const CnfInteractionSpec *spec, int32_t S, const float *
                         int64_t N, int32_t D, float *xbar, void *workspace, int64_t workspace_bytes,
                         void *stream);
 
+/* ---- the kernel Stein discrepancy of point sets against a score ------------------------------------------------------
+ * For S sets x [S, N, D] and the score s [S, N, D] = grad log p at those points (p known through s alone), with the
+ * base kernel k(x, y) = phi(r^2), r^2 = |d|^2, d = x - y, and phi', phi'', phi''' its derivatives in r^2, the Stein kernel
+ *   k_p(x, y) = phi (s_x . s_y) + 2 phi' d . (s_y - s_x) - 4 phi'' r^2 - 2 D phi'
+ *   k_p(x, x) = phi(0) |s_x|^2 - 2 D phi'(0)
+ *   kind CNF_STEIN_IMQ:       phi = sum_b w_b (bw_b^2 + r^2)^beta,  -1 < beta < 0,  b < n_terms <= 4
+ *   kind CNF_STEIN_GAUSSIAN:  phi = sum_b w_b exp(-r^2 / (2 bw_b^2))           (beta is ignored)
+ * cnf_stein writes
+ *   sums [S, 2] (device, doubles):  sum_{i != j} k_p(x_i, x_j)  and  sum_i k_p(x_i, x_i)
+ *       (KSD^2_U = sums[0] / (N (N - 1)),  KSD^2_V = (sums[0] + sums[1]) / N^2)
+ *   rows [S, N] (float32, or NULL):  (1 / (N - 1)) sum_{j != i} k_p(x_i, x_j)
+ *   grad_x, grad_s [S, N, D] (float32, both or neither):  the gradients of KSD^2_U in x_i and in s_i, s held an
+ *       independent input: 2 / (N (N - 1)) times the sum over j != i of
+ *         d / d s_i:  phi s_j - 2 phi' d
+ *         d / d x_i:  (2 phi' s_i . s_j + 4 phi'' d . (s_j - s_i) - 8 phi''' r^2 - (8 + 4 D) phi'') d + 2 phi' (s_j - s_i)
+ * The pair i == j is skipped by index; duplicated points at other indices do interact.  Built as cnf_interaction's pair
+ * pass: blockIdx.y the set, a 256-lane workgroup owning rows held in registers (two per lane for D <= 8, one above) and
+ * one of cnf_stein_splits(S, N, D) column splits, a column's x_j and s_j through the scalar cache, float32 accumulators
+ * for 64 columns, then doubles, a fixed-order merge, no atomics: two calls are bit-identical, sums does not depend on
+ * what else is asked for, and nothing depends on what the workspace held.  The IMQ kind: one v_log_f32, one v_exp_f32
+ * and one v_rcp_f32 per pair and term give all four of phi .. phi'''; the Gaussian kind: one v_exp_f32.  The spec is a
+ * HOST argument; the workspace (cnf_stein_workspace bytes, 8-byte aligned) is the caller's: no allocation, no
+ * synchronisation (legal inside a stream capture).  Non-finite inputs propagate to the outputs of their own set.
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x, score, sums or workspace; S outside 1..64, N
+ * outside 2..2^20, D outside 1..14; an unknown kind; n_terms outside 1..4; a w_b that is not positive and finite; a
+ * bw_b that is not positive and finite; (IMQ) beta outside (-1, 0) or a w_b bw_b^(2 beta - 6), bw_b^2 or 1 / bw_b^2
+ * outside float32's range; (Gaussian) a w_b / bw_b^6 outside float32's range; one of grad_x, grad_s without the other; a
+ * workspace smaller than cnf_stein_workspace says (want_grad != 0: a call that asks for the gradients).
+ * Out of scope: weighted points, D > 14, N > 2^20, more than one rank, other kernels. */
+#define CNF_STEIN_MAX_TERMS 4
+enum { CNF_STEIN_IMQ = 1, CNF_STEIN_GAUSSIAN = 2 };
+typedef struct CnfSteinSpec {
+  int32_t kind;                 /* CNF_STEIN_IMQ or CNF_STEIN_GAUSSIAN */
+  int32_t n_terms;              /* 1 .. CNF_STEIN_MAX_TERMS            */
+  float w[CNF_STEIN_MAX_TERMS];
+  float bw[CNF_STEIN_MAX_TERMS];         /* IMQ: c_b; Gaussian: h_b    */
+  float beta;                   /* IMQ: the exponent, in (-1, 0)       */
+} CnfSteinSpec;
+int cnf_stein_workspace(int32_t S, int64_t N, int32_t D, int32_t want_grad, int64_t *bytes);
+int cnf_stein_splits(int32_t S, int64_t N, int32_t D);
+int cnf_stein(const CnfSteinSpec *spec, int32_t S, const float *x, const float *score, int64_t N, int32_t D,
+              double *sums, float *rows, float *grad_x, float *grad_s, void *workspace, int64_t workspace_bytes,
+              void *stream);
+
 /* ---- a particle reference for the interacting (McKean-Vlasov) Fokker-Planck equation --------------------------------
  *   d rho / dt = -div(rho (drift - kappa grad (W * rho))) + sigma lap rho
  * (aggregation-diffusion, crowd aversion, swarming: the forward half of a mean-field game).  It replaces a loop of one
