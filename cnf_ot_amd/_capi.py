@@ -95,6 +95,14 @@ class CnfSteinSpec(ctypes.Structure):
               ("bw", ctypes.c_float * STEIN_MAX_TERMS), ("beta", ctypes.c_float)]
 
 
+KDE_MAX_BW = 4
+
+
+class CnfKdeSpec(ctypes.Structure):
+  """The bandwidths of cnf_kde (include/cnf_ot_amd.h) and whether the pair j == i is left out (self mode only)."""
+  _fields_ = [("n_bw", ctypes.c_int32), ("loo", ctypes.c_int32), ("bw", ctypes.c_float * KDE_MAX_BW)]
+
+
 TERM_KINETIC, TERM_KINETIC_SCORE, TERM_FLOW_MATCHING, TERM_POTENTIAL, TERM_REVERSE_KL, TERM_NEG_LOGPROB = range(6)
 TERM_DENSITY_L2, TERM_DENSITY_L2_DATA = 6, 7      # evaluation terms (no gradient entry accepts them)
 POTENTIALS = {"quadratic": 0, "double_well": 1, "obstacle": 2}
@@ -234,6 +242,13 @@ SYMBOLS = {
   "cnf_stein_splits": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32]),
   "cnf_stein": (ctypes.c_int, [ctypes.POINTER(CnfSteinSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P, _P, _P, _P,
                                _P, _I64, _P]),
+  # the kernel density estimate of x [S, N, D] at q [S, Q, D] (NULL: at x itself): log_rho [S, n_bw, Q], score
+  # [S, n_bw, Q, D], sums [S, n_bw] doubles, each or NULL
+  "cnf_kde_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(_I64)]),
+  "cnf_kde_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_kde": (ctypes.c_int, [ctypes.POINTER(CnfKdeSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, _P, _P, _P,
+                             _I64, _P]),
   # the interacting (McKean-Vlasov) particle reference: R replicas of N particles (snap_step: a host array); state
   # [R, N, D], sums [S, R, 3 + D + D D] doubles, pos [S, R, N, D] and hist [S, ny, nx] each or NULL
   "cnf_mv_particles_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi, stein, two_sample
+from . import kde as kd           # (ensemble_fields returns a key of that name's kind)
 from . import interaction as ia      # (the composites take a keyword of that name)
 from .distributed import Shard, all_reduce_sums, current_shard, shard_range
 from .flows import DeviceRng, FlowEngine, _OnDevice, _stream_ptr, seed_to_u64
@@ -1105,6 +1106,63 @@ def mv_stationary_score(x, a, sigma, subtype, interaction, strength):
   x = torch.as_tensor(x)
   force = autograd.interaction_force(x, **kw)
   return (-float(a) * x.to(device=force.device, dtype=torch.float32) - float(strength) * force) * (1.0 / float(sigma))
+
+
+# ---- an ensemble as fields: density, score and probability-flow velocity at given points ------------------------------
+# The flow trains v_flow + sigma grad log rho = drift (flow_matching_loss_fn).  For the drifts without a closed-form
+# score the only source of the true right-hand side is the particle reference; its kernel density estimate (cnf_kde,
+# DESIGN.md 5.3r) gives log rho_t and grad log rho_t at any points in the full dimension.
+
+_C28_9, _C8_3 = float(np.float32(28.0) / np.float32(9.0)), float(np.float32(8.0) / np.float32(3.0))
+
+
+def fp_drift(x, a, subtype):
+  """The drifts of drift_field (csrc/cnf_terms.h) at x [..., D] in torch, in x's dtype: "ou" -a x at any D, "gradient"
+  (= "smile") and "nongradient" at D = 2, "lorenz" at D = 3; a and the Lorenz constants 28 / 9 and 8 / 3 as float32.
+  ValueError for an unknown drift and for a drift at another dimension."""
+  if subtype not in _capi.DRIFTS:
+    raise ValueError(f"unknown drift {subtype!r}")
+  x = torch.as_tensor(x)
+  D = x.shape[-1]
+  if FP_DRIFT_DIM.get(subtype, D) != D:
+    raise ValueError(f"fp_drift: drift {subtype!r} is not defined at dim {D}")
+  a = float(np.float32(a))
+  if subtype == "ou":
+    return x * -a
+  if subtype in ("gradient", "smile"):
+    X, Y = x[..., 0], x[..., 1]
+    q = X * X + Y * Y - 4.0
+    return torch.stack([(-q * X) * a, (-q * Y - (Y - 1.0) * 2.0) * a], -1)
+  if subtype == "nongradient":
+    X, Y = x[..., 0], x[..., 1]
+    return torch.stack([X * -a - Y * 0.5, Y * -a + X * 0.5], -1)
+  X, Y, Z = x[..., 0], x[..., 1], x[..., 2]
+  return torch.stack([(Y - X) * 10.0, X * 9.0 * (_C28_9 - Z) - Y, X * 9.0 * Y - Z * _C8_3], -1)
+
+
+def ensemble_fields(points, particles, sigma, a, subtype, bandwidths=None, interaction=None, strength=0.0) -> dict:
+  """What an ensemble `particles` ([N, D] or [S, N, D]) of the fp problem (drift `subtype` with parameter a, diffusion
+  sigma) says at `points` ([Q, D] or [S, Q, D]), by its kernel density estimate (utils.kde, ONE cnf_kde call):
+    log_density [S, B, Q], score [S, B, Q, D]   the estimate's, per bandwidth (None: kde_bandwidths(particles))
+    velocity [S, B, Q, D]  the probability-flow velocity drift(q) - sigma score [- strength force], with `interaction`
+                           (the keyword arguments of utils.interaction_spec) force = grad (W * rho)(q) from
+                           utils.interaction_field(points, particles, ...): the mean over ALL particles
+    bandwidths
+  float32 on the device; the leading axis is dropped for 2-D points.  ValueError before any device work for what
+  fp_drift, utils.kde and utils.interaction_field refuse and for a sigma or strength that is not finite."""
+  if not math.isfinite(float(sigma)) or not math.isfinite(float(strength)):
+    raise ValueError(f"ensemble_fields: sigma and the strength must be finite, not {sigma}, {strength}")
+  fp_drift(torch.zeros(1, int(np.shape(points)[-1])), a, subtype)      # (its refusals, before any device work)
+  if interaction is not None:
+    ia.interaction_spec(**dict(interaction))
+  est = kd.kde(points, particles, bandwidths, want_score=True, loo=False)
+  score = est["score"]
+  q = torch.as_tensor(points).detach().to(device=score.device, dtype=torch.float32)
+  vel = fp_drift(q, a, subtype).unsqueeze(-3) - float(sigma) * score
+  if interaction is not None:
+    force = ia.interaction_field(points, particles, want_force=True, **dict(interaction))["force"]
+    vel = vel - float(strength) * force.unsqueeze(-3)
+  return {"log_density": est["log_density"], "score": score, "velocity": vel, "bandwidths": est["bandwidths"]}
 
 
 # ---- importance-sampling diagnostics against the densities known in closed form -------------------------------------

@@ -9,7 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
-                               [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd]
+                               [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd] [--field-errors]
 """
 import argparse
 import sys
@@ -436,11 +436,16 @@ def _fp_prelude(name, config, times, n_particles, h, min_particles, start="gauss
 def _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed):
   """(flow, half 0, half 1), [S, n_particles / 2, D] each: the flow's samples of `seed` at the times ts, stacked, and
   the positions of the two halves of the Euler-Maruyama ensemble (fp: the problem, as _fp_prelude returns it)."""
-  dim, T, a, sigma, sub = fp
   flow = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n_particles // 2,)) for t in ts])
-  h0, h1 = (applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
-                                                shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
+  h0, h1 = _fp_halves(fp, ts, n_particles, h, seed)
   return flow, h0, h1
+
+
+def _fp_halves(fp, ts, n_particles, h, seed):
+  """The positions of the two halves of the Euler-Maruyama ensemble at the times ts, [S, n_particles / 2, D] each"""
+  dim, T, a, sigma, sub = fp
+  return tuple(applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n_particles, h, seed, positions=True,
+                                                   shard=Shard(r, 2), all_reduce=False)["pos"].float() for r in (0, 1))
 
 
 def evaluate_fp_path(config, model: FlowModel, params: Params, times=None, n_particles=1 << 20, h=1e-3, seed=0,
@@ -532,6 +537,102 @@ def print_fp_two_sample(res: Dict[str, Any]) -> None:
         + "):  t | mmd2 | mmd2 floor | energy | energy floor")
   for row in zip(res["times"], res["mmd2"], res["mmd2_floor"], res["energy"], res["energy_floor"]):
     print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row))
+
+
+# ---- the flow's fields against the ensemble's: log-density, score and the velocity the flow-matching term trains -------
+
+FP_FIELD_KEYS = ("times", "bandwidth", "logp_rmse", "logp_rmse_floor", "score_rel_err", "score_rel_err_floor",
+                 "velocity_rel_err", "velocity_rel_err_floor", "kde_score_bias", "n", "n_points")
+
+
+def _rel_err(a, b):
+  """sum |a - b|^2 / sum |b|^2 over the points, in float64"""
+  a, b = a.double(), b.double()
+  return float(((a - b) ** 2).sum() / (b ** 2).sum())
+
+
+def _rmse(a, b):
+  return float(((a.double() - b.double()) ** 2).mean().sqrt())
+
+
+def evaluate_fp_fields(config, model: FlowModel, params: Params, times=None, n_particles=1 << 18, n_points=4096, h=1e-3,
+                       seed=0, bandwidth_factor=1.0) -> Dict[str, Any]:
+  """The flow's FIELDS against the particle reference's, in the full dimension and for every drift -- what the
+  flow-matching term trains is the velocity, v_flow + sigma grad log rho = drift, and for the drifts without a
+  closed-form score the only source of the true right-hand side is the ensemble: its kernel density estimate
+  (applications.ensemble_fields, cnf_kde) gives log rho_t, grad log rho_t and the probability-flow velocity
+  drift - sigma grad log rho_t [- strength grad(W * rho_t)] at any points.  `times`, and the refusals, as
+  evaluate_fp_two_sample.  The ensemble is run as its two halves of n_particles / 2 -- with an `interaction` section of
+  `role: drift`, the two replicas of applications.mv_reference_particles(positions=True), the force in the velocity.  Per
+  time: the sources are half 0, the evaluation points the first n_points particles of half 1 (points of the law that are
+  not sources), ONE bandwidth, utils.kde_bandwidths of that time's sources times bandwidth_factor; the flow's side is
+  one utils.eulerian_fields(logp, vel, score with exact_score=True) call.  Lists, one entry per time:
+    times, bandwidth
+    logp_rmse          root mean square of log rho_flow - log rho_ens over the points
+    score_rel_err      sum |s_flow - s_ens|^2 / sum |s_ens|^2
+    velocity_rel_err   sum |v_flow - v_ens|^2 / sum |v_ens|^2
+    logp_rmse_floor, score_rel_err_floor, velocity_rel_err_floor
+                       the same quantities between the ensemble's fields from the two halves of the SOURCE half (one
+                       call on two sets, the same bandwidth): the Monte-Carlo noise at half the sources
+    kde_score_bias     drift ou without an interaction: sum |s_ens - s_t|^2 / sum |s_t|^2 against the closed form s_t =
+                       -x / applications.ou_variance(t, ...): what the bandwidth costs; else None
+  and n (sources), n_points.  Two cnf_kde calls per time (the estimate, its floor).  Single process.  ValueError, before
+  any device work, for what _fp_prelude refuses (n_particles even and >= 8), an n_points outside 1..n_particles / 2, a
+  bandwidth_factor that is not positive and finite and what utils.kde_check_shapes refuses."""
+  name = "evaluate_fp_fields"
+  _, ts, n_particles, fp = _fp_prelude(name, config, times, n_particles, h, 8)
+  dim, T, a, sigma, sub = fp
+  n, n_points = n_particles // 2, int(n_points)
+  if n % 2:
+    raise ValueError(f"{name}: n_particles must be a multiple of 4 (the source half is halved for the floors), not {n_particles}")
+  if not 1 <= n_points <= n:
+    raise ValueError(f"{name}: n_points must lie in 1..n_particles / 2 = {n}, not {n_points}")
+  if not (float(bandwidth_factor) > 0.0 and np.isfinite(float(bandwidth_factor))):
+    raise ValueError(f"{name}: the bandwidth factor must be positive and finite, not {bandwidth_factor}")
+  utils.kde_check_shapes((1, n, dim), (1, n_points, dim))
+  kw, strength = None, 0.0
+  if _interaction_kind(config) != "none" and _interaction_role(config) == "drift":
+    kw, strength = _interaction_kwargs(config), float(config["interaction"]["strength"])
+    utils.interaction_spec(**kw)
+    pos = applications.mv_reference_particles(dim, T, a, sigma, sub, kw, strength, ts, n, 2, h, seed, positions=True)["pos"]
+    h0, h1 = pos[:, 0].float(), pos[:, 1].float()
+  else:
+    h0, h1 = _fp_halves(fp, ts, n_particles, h, seed)
+  out: Dict[str, Any] = {k: [] for k in FP_FIELD_KEYS[:8]}
+  out.update(kde_score_bias=[] if sub == "ou" and kw is None else None, n=n, n_points=n_points)
+  var0 = applications.fp_initial_variance(T)
+  for i, t in enumerate(ts):
+    src, pts = h0[i].contiguous(), h1[i, :n_points].contiguous()
+    bw = [float(bandwidth_factor) * utils.kde_bandwidths(src)[0]]
+    ens = applications.ensemble_fields(pts, src, sigma, a, sub, bw, kw, strength)
+    two = applications.ensemble_fields(torch.stack([pts, pts]), torch.stack([src[:n // 2], src[n // 2:]]), sigma, a, sub, bw,
+                                       kw, strength)
+    flow = utils.eulerian_fields(model, params, pts, [float(t)], logp=True, vel=True, score=True, exact_score=True,
+                                 dt=config["general"]["dt"])
+    out["times"].append(float(t))
+    out["bandwidth"].append(ens["bandwidths"][0])
+    out["logp_rmse"].append(_rmse(flow["logp"][0], ens["log_density"][0]))
+    out["score_rel_err"].append(_rel_err(flow["score"][0], ens["score"][0]))
+    out["velocity_rel_err"].append(_rel_err(flow["vel"][0], ens["velocity"][0]))
+    out["logp_rmse_floor"].append(_rmse(two["log_density"][0, 0], two["log_density"][1, 0]))
+    out["score_rel_err_floor"].append(_rel_err(two["score"][0, 0], two["score"][1, 0]))
+    out["velocity_rel_err_floor"].append(_rel_err(two["velocity"][0, 0], two["velocity"][1, 0]))
+    if out["kde_score_bias"] is not None:
+      exact = pts.double() * (-1.0 / applications.ou_variance(float(t), a, var0, sigma))
+      out["kde_score_bias"].append(_rel_err(ens["score"][0], exact))
+  return out
+
+
+def print_fp_fields(res: Dict[str, Any]) -> None:
+  """evaluate_fp_fields' table, one line per time"""
+  bias = res["kde_score_bias"]
+  print("field errors against the particle reference's kernel density estimate ({} sources, {} points):  t | bandwidth | "
+        "log rho rmse | floor | score rel err | floor | velocity rel err | floor{}"
+        .format(res["n"], res["n_points"], " | kde score bias" if bias is not None else ""))
+  for i, row in enumerate(zip(res["times"], res["bandwidth"], res["logp_rmse"], res["logp_rmse_floor"], res["score_rel_err"],
+                              res["score_rel_err_floor"], res["velocity_rel_err"], res["velocity_rel_err_floor"])):
+    print("  {:.4f} | {:.4g} | {:.3e} | {:.3e} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row)
+          + (" | {:.3e}".format(bias[i]) if bias is not None else ""))
 
 
 # ---- the same comparison in transport units at the full ensemble size: the sliced Wasserstein distance ---------------
@@ -1114,14 +1215,15 @@ def _eval_rng(seed, step):
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
-         interaction: bool = False, mv_path: bool = False, ksd: bool = False) -> Dict[str, Any]:
+         interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
   returned dict is `evaluate`'s either way).  two_sample (fp): print evaluate_fp_two_sample's table.  ot_reference (ot):
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
-  `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables."""
+  `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables.
+  field_errors (fp): print evaluate_fp_fields' table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -1132,6 +1234,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     raise ValueError(f"--sliced compares the flow with the fp particle reference: not defined for {_type}")
   if knn and _type != "fp":
     raise ValueError(f"--knn compares the flow with the fp particle reference: not defined for {_type}")
+  if field_errors and _type != "fp":
+    raise ValueError(f"--field-errors compares the flow's fields with the fp particle reference's: not defined for {_type}")
   if interaction and _interaction_kind(config) == "none":
     raise ValueError("--interaction prints the interaction energy of the config's `interaction` section: its kind is 'none'")
   if mv_path and (_type != "fp" or _interaction_kind(config) == "none" or _interaction_role(config) != "drift"):
@@ -1202,6 +1306,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_mv_path(evaluate_mv_path(config, model, params))
   if ksd:
     print_ksd(evaluate_ksd(config, model, params))
+  if field_errors:
+    print_fp_fields(evaluate_fp_fields(config, model, params))
   return res
 
 
@@ -1241,6 +1347,9 @@ def _parse(argv):
                  help="print the kernel Stein discrepancy of the flow's samples against every closed-form score of the "
                       "problem beside its floor, for fp the particle ensemble against that score and against the flow's "
                       "exact score, and with an interaction in the ou drift the stationarity residual at T")
+  p.add_argument("--field-errors", action="store_true",
+                 help="print the errors of the flow's log-density, score and velocity, in the full dimension, against the "
+                      "kernel density estimate of the particle reference, each beside its Monte-Carlo floor (fp)")
   return p.parse_args(argv)
 
 
@@ -1248,4 +1357,5 @@ if __name__ == "__main__":
   args = _parse(sys.argv[1:])
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
-       sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd)
+       sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd,
+       field_errors=args.field_errors)

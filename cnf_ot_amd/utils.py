@@ -5,7 +5,8 @@
   - the arrays under its figures (:598-798): density, velocity and score fields, trajectories, and `point_stats`;
   - the distances between two point clouds (mmd2, sinkhorn, sliced_wasserstein and their helpers), which live in
     `two_sample` and are re-exported here, as are the interaction energy of one cloud (`interaction`) and the kernel
-    Stein discrepancy of a cloud against a score (`stein`).
+    Stein discrepancy of a cloud against a score (`stein`) and the kernel density estimate of a cloud with its score
+    (`kde`).
 """
 from typing import Optional
 
@@ -27,6 +28,8 @@ from .interaction import (  # noqa: F401
     interaction_energy, interaction_field, interaction_force_vjp)
 from .stein import (  # noqa: F401
     STEIN_KINDS, STEIN_MAX_TERMS, STEIN_MAX_POINTS, stein_spec, stein_check_shapes, ksd)
+from .kde import (  # noqa: F401
+    KDE_MAX_BW, KDE_MAX_POINTS, kde_spec, kde_check_shapes, kde_bandwidths, kde)
 
 
 def _model_of(fn_or_model):

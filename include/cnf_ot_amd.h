@@ -1057,6 +1057,46 @@ int cnf_stein(const CnfSteinSpec *spec, int32_t S, const float *x, const float *
               double *sums, float *rows, float *grad_x, float *grad_s, void *workspace, int64_t workspace_bytes,
               void *stream);
 
+/* ---- a Gaussian kernel density estimate of point sets: log-density and score ----------------------------------------
+ * What turns an ensemble into FIELDS at given points in the full dimension.  For S sets of sources x [S, N, D], queries
+ * q [S, Q, D] and bandwidths h_b, b < n_bw <= 4, per (set, b, query i):
+ *   t_ij     = -|q_i - x_j|^2 / (2 h_b^2)        (the difference first, then the square)
+ *   m        = max_j t_ij,   s = sum_j exp(t_ij - m),   w_ij = exp(t_ij - m) / s
+ *   log_rho  = m + log s - log n_eff - (D / 2) log(2 pi h_b^2)        [S, n_bw, Q]     float32, or NULL
+ *   score_d  = sum_j w_ij (x_jd - q_id) / h_b^2                       [S, n_bw, Q, D]  float32, or NULL
+ *   sums     = sum_i log_rho                                          [S, n_bw]        float64, or NULL
+ * (sums adds the float32 log_rho values in double).  q == NULL is self mode: the queries are the sources and Q must
+ * equal N.  With spec->loo != 0 (self mode only) the pair j == i is skipped by index -- duplicated points at other
+ * indices do interact -- and n_eff = N - 1: the leave-one-out estimate, whose sums / N is the likelihood that bandwidth
+ * selection maximises.  Otherwise n_eff = N.
+ * Where every t_ij of a row is -inf in float32 (no source within reach: a distance that overflows, or one that times
+ * 1 / (2 h_b^2) does): log_rho = -inf and score = 0.  A query with a NaN coordinate gives NaN for that query only; a
+ * set with a NaN source coordinate gives NaN for that set only.
+ * Built as cnf_sinkhorn's pair pass: blockIdx.y the set, a 256-lane workgroup owning query rows held in registers (two
+ * per lane where n_bw (1 + D) <= 16, one above) and one of cnf_kde_splits(S, N, Q, D) column splits, a source through
+ * the scalar cache, float32 pair math with exp2 on the precomputed -log2 e / (2 h_b^2), float32 sums for 64 columns,
+ * then doubles.  All bandwidths share d2_ij and ONE running minimum of it per row, from which each bandwidth's sums are
+ * rescaled.  A merge kernel brings a row's splits together in ascending order; a finish kernel forms sums in a fixed
+ * order.  No float atomics: two calls are bit-identical, no output depends on which others are asked for, and nothing
+ * depends on what the workspace held.  The spec is a HOST argument; the workspace (cnf_kde_workspace bytes, 8-byte
+ * aligned; want_score != 0: a call that asks for the score) is the caller's: no allocation, no synchronisation (legal
+ * inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x or workspace; log_rho, score and sums all NULL;
+ * S outside 1..64, N outside 1..2^20 (2..2^20 with loo), Q outside 1..2^20, D outside 1..14, n_bw outside 1..4; q ==
+ * NULL with Q != N; loo with q != NULL; a bandwidth that is not positive and finite or whose 1 / (2 h^2) is not a
+ * normal float32; a workspace smaller than cnf_kde_workspace says.
+ * Out of scope: gradients in the particles, per-set bandwidths, weighted sources, other kernels, more than one rank. */
+#define CNF_KDE_MAX_BW 4
+typedef struct CnfKdeSpec {
+  int32_t n_bw;                 /* 1 .. CNF_KDE_MAX_BW                              */
+  int32_t loo;                  /* != 0: leave-one-out (self mode only)             */
+  float bw[CNF_KDE_MAX_BW];     /* h_b                                              */
+} CnfKdeSpec;
+int cnf_kde_workspace(int32_t S, int64_t N, int64_t Q, int32_t D, int32_t n_bw, int32_t want_score, int64_t *bytes);
+int cnf_kde_splits(int32_t S, int64_t N, int64_t Q, int32_t D);
+int cnf_kde(const CnfKdeSpec *spec, int32_t S, const float *x, int64_t N, const float *q, int64_t Q, int32_t D,
+            float *log_rho, float *score, double *sums, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- a particle reference for the interacting (McKean-Vlasov) Fokker-Planck equation --------------------------------
  *   d rho / dt = -div(rho (drift - kappa grad (W * rho))) + sigma lap rho
  * (aggregation-diffusion, crowd aversion, swarming: the forward half of a mean-field game).  It replaces a loop of one
