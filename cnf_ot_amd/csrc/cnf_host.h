@@ -46,6 +46,11 @@ int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, c
 // helpers and flow_pass (cnf_flow_tile.h), target_logprob (cnf_terms.h), with_shape and launch (cnf_common.h) -- and
 // stands apart so that the kernels of cnf_flow.hip keep their generated code.
 
+// ---- the pair passes (cnf_mmd, cnf_knn, cnf_sinkhorn, cnf_interaction, cnf_interaction_vjp, cnf_stein, cnf_kde) -------
+// Every row of a point set against every column, in column splits, with a fixed-order finish.  What they decide alike
+// -- the workgroup's geometry, the column splits, a split's tiles, the block tree sum, the dispatch on the dimension --
+// is cnf_pairs.h: a header without kernels, so no unit's kernels depend on another's.
+
 // ---- cnf_mmd.hip ----------------------------------------------------------------------------------------------------
 // mmd_kernel and mmd_finish_kernel behind cnf_mmd_workspace / cnf_mmd_splits / cnf_mmd2 (include/cnf_ot_amd.h).
 // Model-free, like cnf_fp_particles.hip: the unit calls into no other and none calls into it.
@@ -77,5 +82,5 @@ int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x,
 
 // ---- cnf_interaction_vjp.hip ------------------------------------------------------------------------------------------
 // iv_kernel and iv_finish_kernel behind cnf_interaction_vjp_workspace / cnf_interaction_vjp (include/cnf_ot_amd.h).
-// Model-free: the unit calls into no other and none calls into it; it shares cnf_interaction_pairs.h (the workgroup's
-// geometry, the column splits, the spec and shape checks) with cnf_interaction.hip.
+// Model-free: the unit calls into no other and none calls into it; it shares cnf_interaction_pairs.h (the rows per
+// lane, the column splits in the interaction's arguments, the spec and shape checks) with cnf_interaction.hip.

@@ -20,6 +20,8 @@
 // Each (split, row) writes one double (and D doubles of force) to the workspace; ia_finish_kernel adds a row's splits
 // in ascending order -- that is pot and force -- then the rows in a fixed strided order and a fixed tree -- that is
 // sums: bitwise reproducible, and every workspace word it reads was written by this call.  P depends on the sizes alone.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the finish's
+// tree, the dispatch on D -- is cnf_pairs.h's.
 #include "cnf_host.h"
 #include "cnf_interaction_pairs.h"
 #include "cnf_terms.h"
@@ -188,8 +190,7 @@ __global__ __launch_bounds__(IA_THREADS) void ia_kernel(const float* __restrict_
   const bool self = q == nullptr;
   const float* col = x + (int64_t)s * N * D;
   const float* rows_p = self ? col : q + (int64_t)s * n_rows * D;
-  const int64_t tiles = (N + IA_TILE - 1) / IA_TILE, per = (tiles + P - 1) / P;
-  const int64_t t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;
+  const auto [t0, t1] = pair_tile_range<int64_t>(N, P, p);
   float xr[IA_R][D];
 #pragma unroll
   for (int r = 0; r < IA_R; ++r) {
@@ -247,13 +248,8 @@ __global__ __launch_bounds__(IA_THREADS) void ia_finish_kernel(const double* __r
       if (pot) pot[s * n_rows + i] = (float)(cv * v * inv_n);
       acc += v;
     }
-    s_acc[t] = acc;
-    __syncthreads();
-    for (int o = IA_THREADS / 2; o > 0; o >>= 1) {
-      if (t < o) s_acc[t] += s_acc[t + o];
-      __syncthreads();
-    }
-    if (t == 0) sums[s] = cv * s_acc[0];
+    const double total = pair_block_sum<IA_THREADS>(s_acc, t, acc);
+    if (t == 0) sums[s] = cv * total;
     return;
   }
   if (!force) return;
@@ -294,10 +290,6 @@ template <int D> void ia_launch_kind(int kind, const IaLaunch& a) {
   else if (kind == CNF_INTERACTION_POWER) ia_launch_force<D, CNF_INTERACTION_POWER>(a);
   else ia_launch_force<D, CNF_INTERACTION_QUADRATIC>(a);   // (ia_coef has refused every other kind)
 }
-template <int D = 1> void ia_launch_dim(int dim, int kind, const IaLaunch& a) {
-  if (dim == D) ia_launch_kind<D>(kind, a);
-  else if constexpr (D < IA_MAX_D) ia_launch_dim<D + 1>(dim, kind, a);
-}
 
 }  // namespace
 }  // namespace cnf
@@ -336,7 +328,7 @@ int interaction_pairs(const CnfInteractionSpec* spec, int32_t S, const float* x,
   a.st = stream;
   a.x = x; a.q = q; a.N = N;
   a.ws = (double*)workspace;
-  ia_launch_dim(D, spec->kind, a);
+  pair_dispatch_dim(D, [&](auto d) { ia_launch_kind<decltype(d)::value>(spec->kind, a); });
   return hipGetLastError() == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 

@@ -1,25 +1,21 @@
-// cnf_interaction_pairs.h -- what the pair passes over a point cloud share: the geometry of a workgroup, the column
-// splits, the shape and spec checks and the spec as a kernel reads it.  Included by cnf_interaction.hip (the energy, the
-// field and the force) and cnf_interaction_vjp.hip (the force's vector-Jacobian product); host code and constants only,
-// so neither unit's kernels depend on the other's.
+// cnf_interaction_pairs.h -- what the interaction kernels share beyond cnf_pairs.h: their rows per lane, the column
+// splits and the shape check in their arguments, the spec checks and the spec as a kernel reads it.  Included by
+// cnf_interaction.hip (the energy, the field and the force), cnf_interaction_vjp.hip (the force's vector-Jacobian
+// product) and cnf_stein.hip (fits_float and the shape check); host code and constants only, so no unit's kernels
+// depend on another's.
 #pragma once
-#include "cnf_common.h"
+#include "cnf_pairs.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace cnf {
 
-constexpr int IA_THREADS = 256;                // lanes per workgroup
+// The geometry (cnf_pairs.h) the interaction kernels are written for: IA_THREADS = 256; IA_TILE = 64;
+constexpr int IA_THREADS = PAIR_THREADS, IA_TILE = PAIR_TILE;
 constexpr int IA_R = 2;                        // rows per lane
 constexpr int IA_ROWS = IA_THREADS * IA_R;     // rows per workgroup
-constexpr int IA_TILE = 64;                    // columns per float32 accumulation (divides IA_ROWS)
-constexpr int IA_MAX_S = 64;
-constexpr int IA_MAX_D = 14;
+static_assert(IA_THREADS == 256 && IA_TILE == 64 && IA_ROWS % IA_TILE == 0, "the interaction kernels' tile geometry");
 constexpr int IA_MAX_TERMS = CNF_INTERACTION_MAX_TERMS;
-constexpr int IA_MAX_SPLIT = 64;
-constexpr int64_t IA_TARGET_WGS = 2048;        // 256 CUs x 8 workgroups of 4 waves: a constant, not a device query
-constexpr int64_t IA_MAX_N = int64_t(1) << 20;
 
 // Term b of a pair at squared distance d2: e_b = exp2(nc_b a), a = d2 (Gaussian, nc_b = -log2 e / (2 bw_b^2)) or
 // a = r (exponential, nc_b = -log2 e / bw_b); W += amp_b e_b; the force's weight += ga_b e_b with ga_b = -amp_b / bw_b^2
@@ -38,20 +34,15 @@ struct IaPower {
   float cl;                                    // the log terms' value coefficients, added: W += cl log2 u
 };
 
-inline int64_t row_groups(int64_t n) { return (n + IA_ROWS - 1) / IA_ROWS; }
+inline int64_t row_groups(int64_t n) { return pair_row_groups(n, IA_ROWS); }
 
-// Column splits: enough workgroups for the chip, never more splits than the columns have tiles
+// Column splits (pair_splits) over the columns' tiles
 inline int32_t ia_splits(int32_t S, int64_t rows, int64_t N) {
-  const int64_t base = (int64_t)S * row_groups(rows);
-  const int64_t want = (IA_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (N + IA_TILE - 1) / IA_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)IA_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;          // tiles per split; then no split is empty
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * row_groups(rows), pair_tiles(N));
 }
 
 inline bool ia_shape_ok(int32_t S, int64_t N, int64_t Q, int32_t D) {
-  return S >= 1 && S <= IA_MAX_S && N >= 2 && N <= IA_MAX_N && Q >= 0 && Q <= IA_MAX_N && D >= 1 && D <= IA_MAX_D;
+  return pair_dims_ok(S, D) && N >= 2 && N <= PAIR_MAX_N && Q >= 0 && Q <= PAIR_MAX_N;
 }
 
 inline bool finite_nonzero(float v) { return std::isfinite(v) && v != 0.0f; }

@@ -19,6 +19,8 @@
 // IA_TILE = 64 columns and are then added into doubles.  Each (split, row) writes D doubles to the workspace;
 // iv_finish_kernel adds a row's splits in ascending order: no atomics, bitwise reproducible, and every workspace word it
 // reads was written by this call.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the
+// dispatch on D -- is cnf_pairs.h's.
 #include "cnf_host.h"
 #include "cnf_interaction_pairs.h"
 
@@ -146,8 +148,7 @@ __global__ __launch_bounds__(IA_THREADS) void iv_kernel(const float* __restrict_
   const int64_t row0 = rg * IA_ROWS;
   const float* colx = x + (int64_t)s * N * D;
   const float* colg = g + (int64_t)s * N * D;
-  const int64_t tiles = (N + IA_TILE - 1) / IA_TILE, per = (tiles + P - 1) / P;
-  const int64_t t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;
+  const auto [t0, t1] = pair_tile_range<int64_t>(N, P, p);
   float xr[IA_R][D], gr[IA_R][D];
 #pragma unroll
   for (int r = 0; r < IA_R; ++r) {
@@ -214,10 +215,6 @@ template <int D> void iv_launch_kind(int kind, const IvLaunch& a) {
   else                                         // (ia_coef has refused every other kind)
     hipLaunchKernelGGL((iv_kernel<D, CNF_INTERACTION_QUADRATIC>), a.grid, dim3(IA_THREADS), 0, a.st, a.x, a.g, a.N, a.P, a.k, a.ws, a.eps2);
 }
-template <int D = 1> void iv_launch_dim(int dim, int kind, const IvLaunch& a) {
-  if (dim == D) iv_launch_kind<D>(kind, a);
-  else if constexpr (D < IA_MAX_D) iv_launch_dim<D + 1>(dim, kind, a);
-}
 
 // The spec as iv_kernel reads it; false for what cnf_interaction refuses in one and for a Hessian coefficient
 // (amp / bw^4, Gaussian; amp / bw^2, exponential; amp (pw - 2) eps^(pw - 4), power) outside float32's range
@@ -274,7 +271,7 @@ extern "C" int cnf_interaction_vjp(const CnfInteractionSpec* spec, int32_t S, co
   a.st = (hipStream_t)stream;
   a.x = x; a.g = g; a.N = N;
   a.ws = (double*)workspace;
-  iv_launch_dim(D, spec->kind, a);
+  pair_dispatch_dim(D, [&](auto d) { iv_launch_kind<decltype(d)::value>(spec->kind, a); });
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   const int64_t per_set = N * D, total = (int64_t)S * per_set;
   const double cf = spec->kind == CNF_INTERACTION_QUADRATIC ? (double)spec->amp[0] : 1.0;

@@ -21,11 +21,13 @@
 // kd_merge_kernel brings a row's splits to their common minimum in ascending order and writes log_rho and score;
 // kd_finish_kernel adds a (set, bandwidth)'s log_rho in a fixed strided order and a fixed tree.  No atomics, every loop
 // counted: two calls give the same bits, and every workspace word read was written by this call.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the finish's
+// tree, the dispatch on D -- is cnf_pairs.h's.
 #include "cnf_host.h"
+#include "cnf_pairs.h"
 
 #include <math.h>
 
-#include <algorithm>
 #include <cmath>
 
 // Every fused multiply-add below is written as one (fmaf): with the compiler free to contract, the instantiations with
@@ -35,14 +37,10 @@
 namespace cnf {
 namespace {
 
-constexpr int KD_THREADS = 256;                // lanes per workgroup
-constexpr int KD_TILE = 64;                    // columns per float32 sum
-constexpr int KD_MAX_S = 64;
-constexpr int KD_MAX_D = 14;
+// The geometry (cnf_pairs.h) this unit's kernels are written for: KD_THREADS = 256; KD_TILE = 64;
+constexpr int KD_THREADS = PAIR_THREADS, KD_TILE = PAIR_TILE;
+static_assert(KD_THREADS == 256 && KD_TILE == 64, "kd_pair_kernel's tile geometry");
 constexpr int KD_MAX_BW = CNF_KDE_MAX_BW;
-constexpr int KD_MAX_SPLIT = 64;
-constexpr int64_t KD_TARGET_WGS = 2048;        // 256 CUs x 8 workgroups of 4 waves: a constant, not a device query
-constexpr int64_t KD_MAX_N = int64_t(1) << 20;
 constexpr float KD_FAR = 3.4028234663852886e38f;          // where a row's minimum of d2 starts
 
 // Rows per lane: a row holds NB (1 + D) float32 sums and as many doubles.  Two rows up to 16 of them: at 18 and 20 the
@@ -52,20 +50,12 @@ constexpr int kd_rows(int D, int NB) { return NB * (1 + D) <= 16 ? 2 : 1; }
 // Columns per chunk: the minimum moves, and the sums are rescaled, once per chunk (D U coordinates in SGPRs at a time)
 constexpr int kd_chunk_cols(int D) { return D <= 6 ? 4 : 2; }
 
-int64_t kd_row_groups(int64_t Q, int32_t D, int32_t NB) {
-  const int rows = KD_THREADS * kd_rows(D, NB);
-  return (Q + rows - 1) / rows;
-}
+int64_t kd_row_groups(int64_t Q, int32_t D, int32_t NB) { return pair_row_groups(Q, KD_THREADS * kd_rows(D, NB)); }
 
-// Column splits, as ia_splits: enough workgroups for the chip, never more splits than the sources have tiles.  Counted
-// for two rows per lane whatever (D, n_bw) takes: the count does not depend on the bandwidths.
+// Column splits (pair_splits) over the sources' tiles.  The row groups are counted for two rows per lane whatever
+// (D, n_bw) takes: the count does not depend on the bandwidths.
 int32_t kd_splits(int32_t S, int64_t N, int64_t Q) {
-  const int64_t base = (int64_t)S * ((Q + 2 * KD_THREADS - 1) / (2 * KD_THREADS));
-  const int64_t want = (KD_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (N + KD_TILE - 1) / KD_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)KD_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;          // tiles per split; then no split is empty
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * pair_row_groups(Q, 2 * KD_THREADS), pair_tiles(N));
 }
 
 // Workspace: doubles ps [S][P][NB][Q] (a partial's sums), doubles pa [S][P][NB][Q][D] (score: its weighted differences),
@@ -74,7 +64,6 @@ struct KdLayout {
   int64_t ps, pa, lr, pm, bytes;               // byte offsets (8-byte aligned) and the total
 };
 KdLayout kd_layout(int32_t S, int64_t Q, int32_t D, int32_t NB, int32_t P, bool score) {
-  auto up8 = [](int64_t b) { return (b + 7) / 8 * 8; };
   KdLayout l;
   l.ps = 0;
   l.pa = (int64_t)S * P * NB * Q * 8;
@@ -181,8 +170,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_pair_kernel(const float* __rest
   const int row0 = rg * (KD_THREADS * R);
   const float* col = x + (int64_t)s * N * D;
   const float* rows_p = q + (int64_t)s * Q * D;
-  const int tiles = (N + KD_TILE - 1) / KD_TILE, per = (tiles + P - 1) / P;
-  const int t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;
+  const auto [t0, t1] = pair_tile_range<int>(N, P, p);
   float xr[R][D];
   int row[R];
 #pragma unroll
@@ -278,16 +266,16 @@ __global__ __launch_bounds__(KD_THREADS) void kd_merge_kernel(const KdMergeArgs 
   for (int p = 1; p < P; ++p) dmin = fminf(dmin, pm[p * Q]);
   for (int b = 0; b < NB; ++b) {
     const double nc = (double)a.nc[b];
-    double sum = 0.0, A[KD_MAX_D];
+    double sum = 0.0, A[PAIR_MAX_D];
 #pragma unroll
-    for (int d = 0; d < KD_MAX_D; ++d) A[d] = 0.0;
+    for (int d = 0; d < PAIR_MAX_D; ++d) A[d] = 0.0;
     for (int p = 0; p < P; ++p) {
       const int64_t o = ((s * P + p) * NB + b) * Q + i;
       const double f = exp2(nc * ((double)pm[p * Q] - (double)dmin));
       sum += a.ps[o] * f;
       if (a.score) {
 #pragma unroll
-        for (int d = 0; d < KD_MAX_D; ++d)
+        for (int d = 0; d < PAIR_MAX_D; ++d)
           if (d < D) A[d] += a.pa[o * D + d] * f;
       }
     }
@@ -298,7 +286,7 @@ __global__ __launch_bounds__(KD_THREADS) void kd_merge_kernel(const KdMergeArgs 
     a.log_rho[o] = dead ? -INFINITY : (float)lr;
     if (a.score) {
 #pragma unroll
-      for (int d = 0; d < KD_MAX_D; ++d)
+      for (int d = 0; d < PAIR_MAX_D; ++d)
         if (d < D) a.score[o * D + d] = dead ? 0.0f : (float)(-(A[d] / sum) * a.inv_h2[b]);   // (a holds q - x)
     }
   }
@@ -313,13 +301,8 @@ __global__ __launch_bounds__(KD_THREADS) void kd_finish_kernel(const float* __re
   const float* lr = log_rho + (int64_t)blockIdx.x * Q;
   double acc = 0.0;
   for (int64_t i = t; i < Q; i += KD_THREADS) acc += (double)lr[i];
-  s_acc[t] = acc;
-  __syncthreads();
-  for (int o = KD_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) s_acc[t] += s_acc[t + o];
-    __syncthreads();
-  }
-  if (t == 0) sums[blockIdx.x] = s_acc[0];
+  const double total = pair_block_sum<KD_THREADS>(s_acc, t, acc);
+  if (t == 0) sums[blockIdx.x] = total;
 }
 
 struct KdLaunch {
@@ -334,22 +317,17 @@ template <int D, int NB> void kd_launch_score(const KdLaunch& l) {
   if (l.score) hipLaunchKernelGGL((kd_pair_kernel<D, NB, true>), l.grid, dim3(KD_THREADS), 0, l.st, l.x, l.q, l.a);
   else hipLaunchKernelGGL((kd_pair_kernel<D, NB, false>), l.grid, dim3(KD_THREADS), 0, l.st, l.x, l.q, l.a);
 }
-template <int D = 1> void kd_launch_dim(int dim, int nb, const KdLaunch& l) {
-  if (dim == D) {
-    switch (nb) {
-      case 1: kd_launch_score<D, 1>(l); break;
-      case 2: kd_launch_score<D, 2>(l); break;
-      case 3: kd_launch_score<D, 3>(l); break;
-      default: kd_launch_score<D, 4>(l); break;              // (kd_spec_ok has refused every other count)
-    }
-  } else if constexpr (D < KD_MAX_D) {
-    kd_launch_dim<D + 1>(dim, nb, l);
+template <int D> void kd_launch_bw(int nb, const KdLaunch& l) {
+  switch (nb) {
+    case 1: kd_launch_score<D, 1>(l); break;
+    case 2: kd_launch_score<D, 2>(l); break;
+    case 3: kd_launch_score<D, 3>(l); break;
+    default: kd_launch_score<D, 4>(l); break;                // (kd_shape_ok has refused every other count)
   }
 }
 
 bool kd_shape_ok(int32_t S, int64_t N, int64_t Q, int32_t D, int32_t n_bw) {
-  return S >= 1 && S <= KD_MAX_S && N >= 1 && N <= KD_MAX_N && Q >= 1 && Q <= KD_MAX_N && D >= 1 && D <= KD_MAX_D &&
-         n_bw >= 1 && n_bw <= KD_MAX_BW;
+  return pair_dims_ok(S, D) && N >= 1 && N <= PAIR_MAX_N && Q >= 1 && Q <= PAIR_MAX_N && n_bw >= 1 && n_bw <= KD_MAX_BW;
 }
 
 // 1 / (2 h^2) as a normal float32, or 0 for a bandwidth cnf_kde refuses
@@ -411,7 +389,7 @@ extern "C" int cnf_kde(const CnfKdeSpec* spec, int32_t S, const float* x, int64_
   l.a.pa = (double*)(ws + lay.pa);
   l.a.N = (int32_t)N; l.a.Q = (int32_t)Q; l.a.P = P; l.a.loo = loo ? 1 : 0;
   l.grid = dim3((unsigned)(kd_row_groups(Q, D, NB) * P), (unsigned)S);
-  kd_launch_dim(D, NB, l);
+  pair_dispatch_dim(D, [&](auto d) { kd_launch_bw<decltype(d)::value>(NB, l); });
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   ma.pm = l.a.pm; ma.ps = l.a.ps; ma.pa = l.a.pa;
   ma.log_rho = log_rho ? log_rho : (float*)(ws + lay.lr);

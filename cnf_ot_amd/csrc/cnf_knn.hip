@@ -23,6 +23,9 @@
 // d2 in the row's slot of split 0; knn_sum_kernel adds, per (set, block, rank), thread t's rows t, t + 256, ... and the
 // threads' totals in a fixed tree: bitwise reproducible, and every workspace word read was written by this call.  P
 // depends on (S, N, M) alone.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the finish's
+// tree, the dispatch on D -- is cnf_pairs.h's.
+#include "cnf_pairs.h"
 #include "cnf_terms.h"
 
 #include <math.h>
@@ -36,31 +39,22 @@
 namespace cnf {
 namespace {
 
-constexpr int KNN_THREADS = 256;                 // lanes per workgroup
+// The geometry (cnf_pairs.h) this unit's kernels are written for: KNN_THREADS = 256; KNN_TILE = 64;
+constexpr int KNN_THREADS = PAIR_THREADS, KNN_TILE = PAIR_TILE;
 constexpr int KNN_R = 2;                         // rows per lane
 constexpr int KNN_ROWS = KNN_THREADS * KNN_R;    // rows per workgroup
-constexpr int KNN_TILE = 64;                     // columns per tile, the unit a split is counted in (divides KNN_ROWS)
 constexpr int KNN_CAP_SMALL = 4;                 // the compiled list capacities: k <= 4, and k <= CNF_KNN_MAX_K
 constexpr int KNN_CAP_LARGE = 16;
-constexpr int KNN_MAX_S = 64;
-constexpr int KNN_MAX_D = 14;
-constexpr int KNN_MAX_SPLIT = 64;
-constexpr int64_t KNN_TARGET_WGS = 2048;         // 256 CUs x 8 workgroups of 4 waves: a constant, not a device query
-constexpr int64_t KNN_MAX_N = int64_t(1) << 20;
 static_assert(KNN_CAP_LARGE == CNF_KNN_MAX_K, "the large capacity is the largest k");
+static_assert(KNN_THREADS == 256 && KNN_TILE == 64, "knn_kernel's tile geometry");
 static_assert(KNN_ROWS % KNN_TILE == 0, "a tile lies inside a workgroup's rows or outside");
 
-int64_t row_groups(int64_t n) { return (n + KNN_ROWS - 1) / KNN_ROWS; }
+int64_t row_groups(int64_t n) { return pair_row_groups(n, KNN_ROWS); }
 int32_t knn_blocks(int64_t M) { return M > 0 ? 2 : 1; }
 
-// Column splits: enough workgroups for the chip, never more splits than the longer side has tiles
+// Column splits (pair_splits) over the longer side's tiles
 int32_t knn_splits(int32_t S, int64_t N, int64_t M) {
-  const int64_t base = (int64_t)S * knn_blocks(M) * row_groups(N);
-  const int64_t want = (KNN_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (std::max(N, M) + KNN_TILE - 1) / KNN_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)KNN_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;          // tiles per split; then no split of the longer side is empty
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * knn_blocks(M) * row_groups(N), pair_tiles(std::max(N, M)));
 }
 
 // Workspace: candidates [S][blocks][P][N][k], the d2 as floats, then the indices as int32 in the same layout
@@ -135,8 +129,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const float* __restric
   const float* rows_p = x + (int64_t)s * N * D;
   const float* col = b == 0 ? rows_p : y + (int64_t)s * M * D;
   const int64_t n_col = b == 0 ? N : M;
-  const int64_t tiles = (n_col + KNN_TILE - 1) / KNN_TILE, per = (tiles + P - 1) / P;
-  const int64_t t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;   // (may be empty)
+  const auto [t0, t1] = pair_tile_range<int64_t>(n_col, P, p);     // (may be empty)
 
   float xr[KNN_R][D], ld[KNN_R][CAP];
   int32_t li[KNN_R][CAP];
@@ -234,14 +227,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_sum_kernel(const float* __res
   }
   s_log[t] = acc;
   s_zero[t] = zeros;
-  __syncthreads();
-  for (int o = KNN_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      s_log[t] += s_log[t + o];
-      s_zero[t] += s_zero[t + o];
-    }
-    __syncthreads();
-  }
+  pair_block_tree<KNN_THREADS>(t, s_log, s_zero);
   if (t == 0) {
     out[0] = s_log[0];
     out[1] = s_zero[0];
@@ -266,14 +252,10 @@ template <int D> void knn_launch_cap(const KnnLaunch& a) {
     hipLaunchKernelGGL((knn_kernel<D, KNN_CAP_LARGE>), a.grid, dim3(KNN_THREADS), 0, a.st, a.x, a.y, a.N, a.M, a.P, a.k, a.cd,
                        a.ci);
 }
-template <int D = 1> void knn_launch_dim(int dim, const KnnLaunch& a) {
-  if (dim == D) knn_launch_cap<D>(a);
-  else if constexpr (D < KNN_MAX_D) knn_launch_dim<D + 1>(dim, a);
-}
 
 // (the splits need no k; the call and the workspace query check it beside this)
 bool knn_shape_ok(int32_t S, int64_t N, int64_t M, int32_t D) {
-  return S >= 1 && S <= KNN_MAX_S && D >= 1 && D <= KNN_MAX_D && N >= 2 && N <= KNN_MAX_N && M >= 0 && M <= KNN_MAX_N;
+  return pair_dims_ok(S, D) && N >= 2 && N <= PAIR_MAX_N && M >= 0 && M <= PAIR_MAX_N;
 }
 bool knn_sizes_ok(int32_t S, int64_t N, int64_t M, int32_t D, int32_t k) {
   return knn_shape_ok(S, N, M, D) && k >= 1 && k <= CNF_KNN_MAX_K && N >= (int64_t)k + 1 && (M == 0 || M >= k);
@@ -311,7 +293,7 @@ extern "C" int cnf_knn(int32_t S, const float* x, int64_t N, const float* y, int
   a.x = x; a.y = y; a.N = N; a.M = M;
   a.cd = (float*)workspace;
   a.ci = (int32_t*)workspace + entries;
-  knn_launch_dim(D, a);
+  pair_dispatch_dim(D, [&](auto d) { knn_launch_cap<decltype(d)::value>(a); });
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((N + KNN_THREADS - 1) / KNN_THREADS), (unsigned)(nb * S)),
                      dim3(KNN_THREADS), 0, a.st, a.cd, (const int32_t*)a.ci, N, a.P, k, nb, dist_xx, idx_xx, dist_xy, idx_xy);

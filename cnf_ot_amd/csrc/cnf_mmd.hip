@@ -17,6 +17,9 @@
 // Each (split, row) writes one double (and D doubles of gradient) to the workspace; mmd_finish_kernel adds a row's
 // splits in ascending order, then the rows in a fixed strided order and a fixed tree: bitwise reproducible, and every
 // workspace word it reads was written by this call.  P depends on (S, N, M) alone.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the finish's
+// tree, the dispatch on D -- is cnf_pairs.h's.
+#include "cnf_pairs.h"
 #include "cnf_terms.h"
 
 #include <math.h>
@@ -31,15 +34,12 @@
 namespace cnf {
 namespace {
 
-constexpr int MMD_THREADS = 256;                 // lanes per workgroup
+// The geometry (cnf_pairs.h) this unit's kernels are written for: MMD_THREADS = 256; MMD_TILE = 64;
+constexpr int MMD_THREADS = PAIR_THREADS, MMD_TILE = PAIR_TILE;
 constexpr int MMD_R = 2;                         // rows per lane
 constexpr int MMD_ROWS = MMD_THREADS * MMD_R;    // rows per workgroup
-constexpr int MMD_TILE = 64;                     // columns per float32 accumulation (divides MMD_ROWS)
-constexpr int MMD_MAX_S = 64;
-constexpr int MMD_MAX_D = 14;
+static_assert(MMD_THREADS == 256 && MMD_TILE == 64 && MMD_ROWS % MMD_TILE == 0, "mmd_kernel's tile geometry");
 constexpr int MMD_MAX_BW = 8;
-constexpr int MMD_MAX_SPLIT = 64;
-constexpr int64_t MMD_TARGET_WGS = 2048;         // 256 CUs x 8 workgroups of 4 waves: a constant, not a device query
 constexpr int64_t MMD_MAX_N = int64_t(1) << 24;
 enum { MMD_XX = 0, MMD_YY = 1, MMD_XY = 2 };
 
@@ -50,16 +50,11 @@ struct MmdCoef {
 };
 constexpr double MMD_IB_OVER_NC = -2.0 * 0.6931471805599453;
 
-int64_t row_groups(int64_t n) { return (n + MMD_ROWS - 1) / MMD_ROWS; }
+int64_t row_groups(int64_t n) { return pair_row_groups(n, MMD_ROWS); }
 
-// Column splits: enough workgroups for the chip, never more splits than the longer side has tiles
+// Column splits (pair_splits) over the longer side's tiles
 int32_t mmd_splits(int32_t S, int64_t N, int64_t M) {
-  const int64_t base = (int64_t)S * (2 * row_groups(N) + row_groups(M));
-  const int64_t want = (MMD_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (std::max(N, M) + MMD_TILE - 1) / MMD_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)MMD_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;          // tiles per split; then no split of the longer side is empty
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * (2 * row_groups(N) + row_groups(M)), pair_tiles(std::max(N, M)));
 }
 
 // Workspace, in doubles: row partials [S][P][N | M | N] (xx, yy, xy), then gradient partials [S][2][P][N][D] (xx, xy)
@@ -189,8 +184,7 @@ __global__ __launch_bounds__(MMD_THREADS) void mmd_kernel(const float* __restric
   if (row0 >= n_rows) return;
   const float* rows_p = (b == MMD_YY ? y + (int64_t)s * M * D : x + (int64_t)s * N * D);
   const float* col = (b == MMD_XX ? x + (int64_t)s * N * D : y + (int64_t)s * M * D);
-  const int64_t tiles = (n_col + MMD_TILE - 1) / MMD_TILE, per = (tiles + P - 1) / P;
-  const int64_t t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;   // (may be empty: zeros)
+  const auto [t0, t1] = pair_tile_range<int64_t>(n_col, P, p);     // (may be empty: zeros)
   // this block's partials of set s: [P][n_rows]
   double* part = ws + (int64_t)s * P * (2 * N + M) + (b == MMD_XX ? 0 : b == MMD_YY ? P * N : P * (N + M)) + p * n_rows;
   if (GRAD && b != MMD_YY) {
@@ -219,13 +213,8 @@ __global__ __launch_bounds__(MMD_THREADS) void mmd_finish_kernel(const double* _
       for (int p = 1; p < P; ++p) v += part[p * n_rows + i];
       acc += v;
     }
-    s_acc[t] = acc;
-    __syncthreads();
-    for (int o = MMD_THREADS / 2; o > 0; o >>= 1) {
-      if (t < o) s_acc[t] += s_acc[t + o];
-      __syncthreads();
-    }
-    if (t == 0) sums[blockIdx.x] = s_acc[0];
+    const double total = pair_block_sum<MMD_THREADS>(s_acc, t, acc);
+    if (t == 0) sums[blockIdx.x] = total;
     return;
   }
   if (!xgrad) return;
@@ -268,13 +257,9 @@ template <int D, int NB = 0> void mmd_launch_bw(int nb, const MmdLaunch& a) {
   if (nb == NB) mmd_launch_grad<D, NB>(a);
   else if constexpr (NB < MMD_MAX_BW) mmd_launch_bw<D, NB + 1>(nb, a);
 }
-template <int D = 1> void mmd_launch_dim(int dim, int nb, const MmdLaunch& a) {
-  if (dim == D) mmd_launch_bw<D>(nb, a);
-  else if constexpr (D < MMD_MAX_D) mmd_launch_dim<D + 1>(dim, nb, a);
-}
 
 bool mmd_shape_ok(int32_t S, int64_t N, int64_t M, int32_t D) {
-  return S >= 1 && S <= MMD_MAX_S && N >= 2 && M >= 2 && N <= MMD_MAX_N && M <= MMD_MAX_N && D >= 1 && D <= MMD_MAX_D;
+  return pair_dims_ok(S, D) && N >= 2 && M >= 2 && N <= MMD_MAX_N && M <= MMD_MAX_N;
 }
 
 }  // namespace
@@ -317,7 +302,7 @@ extern "C" int cnf_mmd2(const CnfMmdSpec* spec, int32_t S, const float* x, int64
   a.ws = (double*)workspace;
   a.grad_off = mmd_row_doubles(S, N, M, a.P);
   a.grad = grad;
-  mmd_launch_dim(D, nb, a);
+  pair_dispatch_dim(D, [&](auto d) { mmd_launch_bw<decltype(d)::value>(nb, a); });
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   const double dN = (double)N, dM = (double)M, gs = nb > 0 ? MMD_IB_OVER_NC : 1.0;
   const int64_t grad_wgs = grad ? ((int64_t)S * N * D + MMD_THREADS - 1) / MMD_THREADS : 0;

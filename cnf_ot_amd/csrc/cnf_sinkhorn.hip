@@ -34,7 +34,10 @@
 // (the same operations on (m, s): the value does not depend on what else is asked for).  A last kernel adds the final
 // potentials in a fixed strided order and a fixed tree.  No atomics, no waiting between workgroups, every loop counted:
 // two calls give the same bits, a NaN input ends as NaN, and every workspace word read was written by this call.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, the dispatch on D -- is
+// cnf_pairs.h's.
 #include "cnf_host.h"
+#include "cnf_pairs.h"
 
 #include <math.h>
 
@@ -48,28 +51,19 @@
 namespace cnf {
 namespace {
 
-constexpr int SK_THREADS = 256;                // lanes per workgroup
+// The geometry (cnf_pairs.h) this unit's kernels are written for: SK_THREADS = 256; SK_TILE = 64;
+constexpr int SK_THREADS = PAIR_THREADS, SK_TILE = PAIR_TILE;
 constexpr int SK_R = 2;                        // rows per lane
 constexpr int SK_ROWS = SK_THREADS * SK_R;     // rows per workgroup
-constexpr int SK_TILE = 64;                    // columns per float32 sum
-constexpr int SK_MAX_S = 64;
-constexpr int SK_MAX_D = 14;
-constexpr int SK_MAX_SPLIT = 64;
+static_assert(SK_THREADS == 256 && SK_TILE == 64, "sinkhorn_pair_kernel's tile geometry");
 constexpr int SK_MAX_ITERS = 512;
-constexpr int64_t SK_TARGET_WGS = 2048;        // 256 CUs x 8 workgroups of 4 waves: a constant, not a device query
-constexpr int64_t SK_MAX_N = int64_t(1) << 20;
 enum { SK_F = 0, SK_G = 1, SK_P = 2, SK_Q = 3 };
 
-int64_t row_groups(int64_t n) { return (n + SK_ROWS - 1) / SK_ROWS; }
+int64_t row_groups(int64_t n) { return pair_row_groups(n, SK_ROWS); }
 
-// Column splits: enough workgroups for the chip, never more splits than the longer side has tiles
+// Column splits (pair_splits) over the longer side's tiles
 int32_t sk_splits(int32_t S, int64_t N, int64_t M) {
-  const int64_t base = (int64_t)S * 2 * (row_groups(N) + row_groups(M));
-  const int64_t want = (SK_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (std::max(N, M) + SK_TILE - 1) / SK_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)SK_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;          // tiles per split; then no split of the longer side is empty
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * 2 * (row_groups(N) + row_groups(M)), pair_tiles(std::max(N, M)));
 }
 
 // A set's potentials, and a split's row partials, are laid out [f: N | g: M | p: N | q: M]
@@ -85,7 +79,6 @@ struct SkLayout {
 };
 SkLayout sk_layout(int32_t S, int64_t N, int64_t M, int32_t D, int32_t P) {
   const int64_t W = sk_width(N, M);
-  auto up8 = [](int64_t b) { return (b + 7) / 8 * 8; };
   SkLayout l;
   l.pot = 0;
   l.pm = up8(3 * (int64_t)S * W * 4);
@@ -247,6 +240,7 @@ __global__ __launch_bounds__(SK_THREADS) void sinkhorn_pair_kernel(const float* 
   const float* col = x_cols ? x + (int64_t)s * N * D : y + (int64_t)s * M * D;
   // the potential that lives on the columns: g for f's block, f for g's, p and q for their own
   const float* h = pot + (int64_t)s * W + sk_offset(b == SK_F ? SK_G : b == SK_G ? SK_F : b, N, M);
+  // (pair_tile_range's two lines, written out: through the helper this kernel's instructions came out in another order)
   const int64_t tiles = (n_col + SK_TILE - 1) / SK_TILE, per = (tiles + P - 1) / P;
   const int64_t t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;   // (may be empty)
   const int64_t part = ((int64_t)s * P + p) * W + sk_offset(b, N, M);
@@ -383,18 +377,19 @@ __global__ __launch_bounds__(SK_THREADS) void sinkhorn_finish_kernel(const float
 
 // x [S, N, D], y [S, M, D] and the potentials read, pot [S][W], are arguments of their own: __restrict__ pointers, whose
 // wave-uniform loads the compiler may send through the scalar cache
-template <int D = 1>
 int sk_launch_pair(int dim, bool map, int64_t grid, hipStream_t st, const float* x, const float* y, const float* pot,
                    const SkPairArgs& a) {
-  if (dim == D)
-    return map ? launch_plain(sinkhorn_pair_kernel<D, true>, grid, SK_THREADS, 0, st, x, y, pot, a)
-               : launch_plain(sinkhorn_pair_kernel<D, false>, grid, SK_THREADS, 0, st, x, y, pot, a);
-  if constexpr (D < SK_MAX_D) return sk_launch_pair<D + 1>(dim, map, grid, st, x, y, pot, a);
-  return CNF_ERR_INVALID;
+  int rc = CNF_ERR_INVALID;
+  pair_dispatch_dim(dim, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    rc = map ? launch_plain(sinkhorn_pair_kernel<D, true>, grid, SK_THREADS, 0, st, x, y, pot, a)
+             : launch_plain(sinkhorn_pair_kernel<D, false>, grid, SK_THREADS, 0, st, x, y, pot, a);
+  });
+  return rc;
 }
 
 bool sk_shape_ok(int32_t S, int64_t N, int64_t M, int32_t D) {
-  return S >= 1 && S <= SK_MAX_S && N >= 2 && M >= 2 && N <= SK_MAX_N && M <= SK_MAX_N && D >= 1 && D <= SK_MAX_D;
+  return pair_dims_ok(S, D) && N >= 2 && M >= 2 && N <= PAIR_MAX_N && M <= PAIR_MAX_N;
 }
 
 // log2 e / eps as the kernels receive it, or 0 for an eps they refuse

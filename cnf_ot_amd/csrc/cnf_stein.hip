@@ -19,6 +19,8 @@
 // accumulators live for one tile of IA_TILE = 64 columns and are then added into doubles.  Each (split, row) writes one
 // double (and 2 D of the gradients) to the workspace; st_finish_kernel adds a row's splits in ascending order and the
 // rows in a fixed tree: no atomics, bitwise reproducible, and every workspace word it reads was written by this call.
+// What it shares with the other pair passes -- the workgroup's geometry, the split rule, a split's tiles, the finish's
+// tree, the dispatch on D -- is cnf_pairs.h's.
 #include "cnf_host.h"
 #include "cnf_interaction_pairs.h"
 
@@ -43,16 +45,11 @@ struct StCoef {
   int32_t nt;
 };
 
-inline int64_t st_row_groups(int64_t n, int32_t D) { return (n + ST_THREADS * st_rows(D) - 1) / (ST_THREADS * st_rows(D)); }
+inline int64_t st_row_groups(int64_t n, int32_t D) { return pair_row_groups(n, ST_THREADS * st_rows(D)); }
 
-// ia_splits for this unit's row groups: enough workgroups for the chip, never more splits than the columns have tiles
+// Column splits (pair_splits) for this unit's row groups
 inline int32_t st_splits(int32_t S, int64_t N, int32_t D) {
-  const int64_t base = (int64_t)S * st_row_groups(N, D);
-  const int64_t want = (IA_TARGET_WGS + base - 1) / base;
-  const int64_t tiles = (N + IA_TILE - 1) / IA_TILE;
-  const int64_t most = std::max<int64_t>(1, std::min<int64_t>({want, tiles, (int64_t)IA_MAX_SPLIT}));
-  const int64_t per = (tiles + most - 1) / most;
-  return (int32_t)((tiles + per - 1) / per);
+  return pair_splits((int64_t)S * st_row_groups(N, D), pair_tiles(N));
 }
 
 // Workspace, in doubles: the value partials [S][P][N], then (grad) those of grad_x and of grad_s, [S][P][N][D] each
@@ -175,8 +172,7 @@ __global__ __launch_bounds__(ST_THREADS) void st_kernel(const float* __restrict_
   const int row0 = rg * (ST_THREADS * R);
   const float* colx = x + (int64_t)s * N * D;
   const float* cols = score + (int64_t)s * N * D;
-  const int tiles = (N + IA_TILE - 1) / IA_TILE, per = (tiles + P - 1) / P;
-  const int t0 = p * per < tiles ? p * per : tiles, t1 = t0 + per < tiles ? t0 + per : tiles;
+  const auto [t0, t1] = pair_tile_range<int>(N, P, p);
   float xr[R][D], sr[R][D];
   int row[R];
 #pragma unroll
@@ -246,14 +242,7 @@ __global__ __launch_bounds__(ST_THREADS) void st_finish_kernel(const double* __r
     }
     s_acc[t] = acc;
     s_diag[t] = diag;
-    __syncthreads();
-    for (int o = ST_THREADS / 2; o > 0; o >>= 1) {
-      if (t < o) {
-        s_acc[t] += s_acc[t + o];
-        s_diag[t] += s_diag[t + o];
-      }
-      __syncthreads();
-    }
+    pair_block_tree<ST_THREADS>(t, s_acc, s_diag);
     if (t == 0) {
       sums[2 * s] = s_acc[0];
       sums[2 * s + 1] = s_diag[0];
@@ -289,13 +278,9 @@ template <int D, int KIND> void st_launch_grad(const StLaunch& a) {
   else
     hipLaunchKernelGGL((st_kernel<D, KIND, false>), a.grid, dim3(ST_THREADS), 0, a.st, a.x, a.score, a.N, a.P, a.k, a.ws);
 }
-template <int D = 1> void st_launch_dim(int dim, int kind, const StLaunch& a) {
-  if (dim == D) {
-    if (kind == CNF_STEIN_IMQ) st_launch_grad<D, CNF_STEIN_IMQ>(a);
-    else st_launch_grad<D, CNF_STEIN_GAUSSIAN>(a);           // (st_coef has refused every other kind)
-  } else if constexpr (D < IA_MAX_D) {
-    st_launch_dim<D + 1>(dim, kind, a);
-  }
+template <int D> void st_launch_kind(int kind, const StLaunch& a) {
+  if (kind == CNF_STEIN_IMQ) st_launch_grad<D, CNF_STEIN_IMQ>(a);
+  else st_launch_grad<D, CNF_STEIN_GAUSSIAN>(a);             // (st_coef has refused every other kind)
 }
 
 inline bool st_shape_ok(int32_t S, int64_t N, int32_t D) { return ia_shape_ok(S, N, 0, D); }
@@ -367,7 +352,7 @@ extern "C" int cnf_stein(const CnfSteinSpec* spec, int32_t S, const float* x, co
   a.st = (hipStream_t)stream;
   a.x = x; a.score = score; a.N = (int32_t)N;
   a.ws = (double*)workspace;
-  st_launch_dim(D, spec->kind, a);
+  pair_dispatch_dim(D, [&](auto d) { st_launch_kind<decltype(d)::value>(spec->kind, a); });
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   const int64_t grad_wgs = a.grad ? (2 * (int64_t)S * N * D + ST_THREADS - 1) / ST_THREADS : 0;
   hipLaunchKernelGGL(st_finish_kernel, dim3((unsigned)(S + grad_wgs)), dim3(ST_THREADS), 0, a.st, (const double*)workspace,

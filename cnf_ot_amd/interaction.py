@@ -14,7 +14,7 @@ import torch
 
 from . import _capi
 from .flows import _OnDevice, _stream_ptr
-from .two_sample import _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes
+from .two_sample import _fits, _per_64_sets, _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes
 
 INTERACTION_KINDS = tuple(_capi.INTERACTION_KINDS)
 INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS = _capi.INTERACTION_MAX_TERMS, _capi.INTERACTION_MAX_POINTS
@@ -22,9 +22,6 @@ INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS = _capi.INTERACTION_MAX_TERMS, _ca
 
 def _floats(v):
   return [float(b) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
-
-
-_F32_MAX = 3.4028234663852886e38
 
 
 def _pow(eps, e):
@@ -38,10 +35,6 @@ def _pow(eps, e):
     return eps ** e
   except OverflowError:
     return math.inf
-
-
-def _fits(v):
-  return math.isfinite(v) and abs(v) <= _F32_MAX
 
 
 def _power_spec(spec, amplitudes, bandwidths, exponents):
@@ -167,10 +160,7 @@ def energy_of_sets(spec, x3, want_grad):
   """(F [S] float64, dF / dx [S, N, D] or None) of staged sets x3 [S, N, D] with any S: ONE cnf_interaction call per 64
   sets."""
   N = x3.shape[1]
-  parts = [_call(spec, x3[i:i + _capi.MMD_MAX_SETS], None, False, want_grad)
-           for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
-  sums = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
-  force = None if not want_grad else parts[0][2] if len(parts) == 1 else torch.cat([p[2] for p in parts])
+  sums, _, force = _per_64_sets(lambda x: _call(spec, x, None, False, want_grad), x3)
   return sums / (2.0 * N * (N - 1.0)), None if force is None else force * (1.0 / N)
 
 
@@ -253,15 +243,12 @@ def _vjp_call(spec, x3, g3):
 
 def force_of_sets(spec, x3):
   """The self-mode force [S, N, D] of staged sets x3 with any S: ONE cnf_interaction call per 64 sets."""
-  parts = [_call(spec, x3[i:i + _capi.MMD_MAX_SETS], None, False, True)[2] for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
-  return parts[0] if len(parts) == 1 else torch.cat(parts)
+  return _per_64_sets(lambda x: _call(spec, x, None, False, True)[2], x3)
 
 
 def force_vjp_of_sets(spec, x3, g3):
   """xbar [S, N, D] of staged sets x3 and force adjoints g3 with any S: ONE cnf_interaction_vjp call per 64 sets."""
-  parts = [_vjp_call(spec, x3[i:i + _capi.MMD_MAX_SETS], g3[i:i + _capi.MMD_MAX_SETS])
-           for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
-  return parts[0] if len(parts) == 1 else torch.cat(parts)
+  return _per_64_sets(lambda x, g: _vjp_call(spec, x, g), x3, g3)
 
 
 def interaction_force_vjp(x, g, kind, amplitudes=None, bandwidths=None, exponents=None):

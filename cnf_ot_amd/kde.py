@@ -6,25 +6,18 @@ re-exports the public names.
 """
 import math
 
-import numpy as np
 import torch
 
 from . import _capi
 from .flows import _OnDevice, _stream_ptr
-from .two_sample import _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes
+from .two_sample import _F32_MAX, _F32_MIN, _floats32, _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes
 
 KDE_MAX_BW, KDE_MAX_POINTS, KDE_BANDWIDTH_ROWS = _capi.KDE_MAX_BW, 1 << 20, 4096
-_F32_MAX, _F32_MIN = 3.4028234663852886e38, 1.1754943508222875e-38
-
-
-def _floats(v):
-  return [float(np.float32(b)) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
-
 
 def kde_spec(bandwidths, loo=False):
   """The CnfKdeSpec of 1..4 bandwidths -- ValueError for what cnf_kde refuses in a spec: a bandwidth that is not positive
   and finite as float32, or whose 1 / (2 h^2) is not a normal float32."""
-  bws = _floats(bandwidths)
+  bws = _floats32(bandwidths)
   if not 1 <= len(bws) <= KDE_MAX_BW:
     raise ValueError(f"kde: between 1 and {KDE_MAX_BW} bandwidths, not {len(bws)}")
   for b in bws:

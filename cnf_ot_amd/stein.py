@@ -12,19 +12,11 @@ import torch
 
 from . import _capi
 from .flows import _OnDevice, _stream_ptr
-from .two_sample import _ptr, _sets, _stage, _unstack, _workspace, _workspace_bytes, median_bandwidths
+from .two_sample import (_F32_MIN, _fits, _floats32, _per_64_sets, _ptr, _sets, _stage, _unstack, _workspace,
+                         _workspace_bytes, median_bandwidths)
 
 STEIN_KINDS = tuple(_capi.STEIN_KINDS)
 STEIN_MAX_TERMS, STEIN_MAX_POINTS = _capi.STEIN_MAX_TERMS, 1 << 20
-_F32_MAX, _F32_MIN = 3.4028234663852886e38, 1.1754943508222875e-38
-
-
-def _floats(v):
-  return [float(np.float32(b)) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
-
-
-def _fits(v):
-  return math.isfinite(v) and abs(v) <= _F32_MAX
 
 
 def _pow(b, e):
@@ -43,8 +35,8 @@ def stein_spec(kind="imq", bandwidths=(1.0,), beta=-0.5, weights=None):
   the coefficients of phi''' at a coincident pair (w c^(2 beta - 6); w / (8 h^6)) and c^2, 1 / c^2 in float32's range."""
   if kind not in _capi.STEIN_KINDS:
     raise ValueError(f"ksd: kind is one of {STEIN_KINDS}, not {kind!r}")
-  bws = _floats(bandwidths)
-  ws = [1.0] * len(bws) if weights is None else _floats(weights)
+  bws = _floats32(bandwidths)
+  ws = [1.0] * len(bws) if weights is None else _floats32(weights)
   if not 1 <= len(bws) <= STEIN_MAX_TERMS or len(ws) != len(bws):
     raise ValueError(f"ksd: between 1 and {STEIN_MAX_TERMS} terms, a weight and a bandwidth each, not {len(ws)} weights "
                      f"and {len(bws)} bandwidths")
@@ -109,10 +101,8 @@ def _call(spec, x3, s3, want_rows, want_grad):
 def ksd_of_sets(spec, x3, s3, want_grad):
   """(KSD^2_U [S] float64, grad_x, grad_s [S, N, D] or None) of staged sets with any S: ONE cnf_stein call per 64 sets."""
   N = x3.shape[1]
-  parts = [_call(spec, x3[i:i + _capi.MMD_MAX_SETS], s3[i:i + _capi.MMD_MAX_SETS], False, want_grad)
-           for i in range(0, x3.shape[0], _capi.MMD_MAX_SETS)]
-  cat = lambda k: parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts])
-  return cat(0)[:, 0] / (N * (N - 1.0)), cat(2) if want_grad else None, cat(3) if want_grad else None
+  sums, _, gx, gs = _per_64_sets(lambda x, s: _call(spec, x, s, False, want_grad), x3, s3)
+  return sums[:, 0] / (N * (N - 1.0)), gx, gs
 
 
 def ksd(x, score, kind="imq", bandwidths=None, beta=-0.5, weights=None, want_grad=False, want_rows=False) -> dict:

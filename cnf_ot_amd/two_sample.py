@@ -3,8 +3,11 @@ two-sample statistics (cnf_mmd2), the Sinkhorn divergence (cnf_sinkhorn), the sl
 (cnf_sliced_w2) and the nearest-neighbour estimates of entropy and KL (cnf_knn).  The kernels are four units
 (DESIGN.md 5.3h-j, 5.3l); what surrounds a call is stated once here: the sets
 as [S, N, D] (`_sets`), the shape check (`_check_shapes`), the staging on the device (`_stage`), the workspace
-(`_workspace`) and the result of a 2-D x (`_unstack`).  `utils` re-exports the public names.
+(`_workspace`), the result of a 2-D x (`_unstack`), one call per 64 sets (`_per_64_sets`) and a spec's numbers as
+float32 holds them (`_floats32`, `_fits`).  `utils` re-exports the public names.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -70,6 +73,30 @@ def _unstack(t, one):
 
 def _ptr(t):
   return None if t is None else t.data_ptr()
+
+
+def _per_64_sets(call, *sets):
+  """call(*chunks) for every 64 sets of the staged tensors `sets` ([S, ...] each, any S), a tensor or a tuple of tensors
+  and Nones: the chunks' results concatenated (up to 64 sets: the one call's result as it is)."""
+  step = _capi.MMD_MAX_SETS
+  parts = [call(*(t[i:i + step] for t in sets)) for i in range(0, sets[0].shape[0], step)]
+  if len(parts) == 1:
+    return parts[0]
+  if torch.is_tensor(parts[0]):
+    return torch.cat(parts)
+  return tuple(None if p[0] is None else torch.cat(p) for p in zip(*parts))
+
+
+_F32_MAX, _F32_MIN = 3.4028234663852886e38, 1.1754943508222875e-38     # float32's largest and smallest normal number
+
+
+def _fits(v):
+  return math.isfinite(v) and abs(v) <= _F32_MAX
+
+
+def _floats32(v):
+  """The numbers of a list, an array or a tensor as Python floats, each rounded to float32 (as the kernel sees them)"""
+  return [float(np.float32(b)) for b in np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)]
 
 
 # ---- kernel two-sample statistics -------------------------------------------------------------------------------------
