@@ -269,6 +269,9 @@ _INTERNAL = {
   "cnf_model_set_dpar": (ctypes.c_int, [_P, ctypes.c_int]),
   "cnf_model_set_pwl_builder": (ctypes.c_int, [_P, ctypes.c_int]),
   "cnf_model_last_pwl_builder": (ctypes.c_int, [_P]),
+  "cnf_model_set_first_table": (ctypes.c_int, [_P, ctypes.c_int]),
+  "cnf_internal_first_table_floats": (_I64, []),
+  "cnf_internal_first_table": (ctypes.c_int, [_P, _P, _P]),
   "cnf_internal_build_tables_into": (ctypes.c_int, [_P, _P, _P, ctypes.c_float, _I64, _P]),
   "cnf_model_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
   "cnf_model_read_profile": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),

@@ -47,6 +47,12 @@ struct CnfModel {
   int64_t tabd_off;       // offset (in floats, 8-byte aligned) of the float64 table inside prep
   int64_t e2_off;         // offset (in floats, 8-byte aligned) of the 2^(-i/32) table inside prep
   int precise;            // 1 (default): data -> base entry points run the precise position path
+  int64_t ft_off;         // offset (in floats, 16-byte aligned) of the `first` spline's inverse table (cnf_first_table.h)
+                          // inside prep, behind every other section; 0: this model has no kernel that reads one
+  int ft_built;           // the table's builder has been enqueued for the current parameters
+  int ft_wanted;          // a launch has asked for the table: from then on cnf_model_set_params builds it (a model that
+                          // only trains never pays for the builder)
+  int first_table_mode;   // 0 (default): the table where certified; 1: always the closed form
   float* prep;            // device
   int64_t n_params;
   int64_t per_layer;

@@ -393,13 +393,31 @@ template <> struct BinRow<v2f> {
   template <int K> __device__ __forceinline__ v2f get(int f) const { return v2f{px[tab_off(f, K)], py[tab_off(f, K)]}; }
 };
 
+// The linear tails of the `first` spline: (out, ld) of the lanes at or beyond the range's ends, whatever evaluated
+// the inside (table_spline's closed form, or the inverse table of cnf_first_table.h).
+template <int K, bool INV, bool ARG, class T>
+__device__ __forceinline__ void table_spline_tails(const typename Lanes<T>::real* tab, T v,
+                                                   const SplineConstsT<typename Lanes<T>::real> sc, T& out, T& ld) {
+  typedef typename Lanes<T>::real R;
+  const auto below = vle(v, sc.lo);
+  const auto above = vge(v, sc.hi);
+  const R* tl = tab + tab_off(F_TAIL, K);
+  const T lo_out = INV ? vfma(v - sc.lo, splat<T>(tl[T_INV_DLO]), splat<T>(sc.lo))
+                       : vfma(v - sc.lo, splat<T>(tl[T_DLO]), splat<T>(sc.lo));
+  const T hi_out = INV ? vfma(v - sc.hi, splat<T>(tl[T_INV_DHI]), splat<T>(sc.hi))
+                       : vfma(v - sc.hi, splat<T>(tl[T_DHI]), splat<T>(sc.hi));
+  out = vsel(below, lo_out, out);
+  ld = vsel(below, ARG ? splat<T>(tl[T_DLO]) : splat<T>(INV ? -tl[T_LOG_DLO] : tl[T_LOG_DLO]), ld);
+  out = vsel(above, hi_out, out);
+  ld = vsel(above, ARG ? splat<T>(tl[T_DHI]) : splat<T>(INV ? -tl[T_LOG_DHI] : tl[T_LOG_DHI]), ld);
+}
+
 // LEAN (flow_pwl_kernel's sampling direction): the root without its Newton step (rqs_bin_eval NEWTON=false), and
 // the linear tails guarded by the caller's wave-uniform `tails` instead of this spline's own test.
 template <int K, bool INV, bool FAST, class T, bool ARG = false, bool LEAN = false>
 __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab, T v,
                                              const SplineConstsT<typename Lanes<T>::real> sc, T& out, T& ld,
                                              bool tails = true) {
-  typedef typename Lanes<T>::real R;
   typename Lanes<T>::index k;
   if constexpr (std::is_same<T, v2f>::value) k = bin_of_pairs<K>(tab + tab_off(INV ? F_YKB : F_XKB, K), v);
   else k = bin_of<K>(tab + tab_off(INV ? F_YK : F_XK, K), v);
@@ -423,19 +441,8 @@ __device__ __forceinline__ void table_spline(const typename Lanes<T>::real* tab,
                                row.template get<K>(F_BH), ibw,
                                row.template get<K>(F_S), row.template get<K>(F_ST), row.template get<K>(F_D0),
                                row.template get<K>(F_D1), row.template get<K>(F_L2S), out, ld);
-  if (LEAN ? tails : maybe_outside(v, sc.lo, sc.hi)) {   // linear tails (rare: |v| >= 10)
-    const auto below = vle(v, sc.lo);
-    const auto above = vge(v, sc.hi);
-    const R* tl = tab + tab_off(F_TAIL, K);
-    const T lo_out = INV ? vfma(v - sc.lo, splat<T>(tl[T_INV_DLO]), splat<T>(sc.lo))
-                         : vfma(v - sc.lo, splat<T>(tl[T_DLO]), splat<T>(sc.lo));
-    const T hi_out = INV ? vfma(v - sc.hi, splat<T>(tl[T_INV_DHI]), splat<T>(sc.hi))
-                         : vfma(v - sc.hi, splat<T>(tl[T_DHI]), splat<T>(sc.hi));
-    out = vsel(below, lo_out, out);
-    ld = vsel(below, ARG ? splat<T>(tl[T_DLO]) : splat<T>(INV ? -tl[T_LOG_DLO] : tl[T_LOG_DLO]), ld);
-    out = vsel(above, hi_out, out);
-    ld = vsel(above, ARG ? splat<T>(tl[T_DHI]) : splat<T>(INV ? -tl[T_LOG_DHI] : tl[T_LOG_DHI]), ld);
-  }
+  if (LEAN ? tails : maybe_outside(v, sc.lo, sc.hi))     // linear tails (rare: |v| >= 10)
+    table_spline_tails<K, INV, ARG, T>(tab, v, sc, out, ld);
 }
 
 // ---------------------------------------------------------------------------

@@ -53,7 +53,8 @@ __global__ void circular_slopes_kernel(const float* __restrict__ params, float* 
 __global__ void prepare_kernel(const float* __restrict__ params, float* __restrict__ prep,
                                int K, int64_t n_params, double lo, double hi, double min_bin,
                                double min_slope, int D, int L, int M, int64_t per_layer,
-                               int64_t per_layer_q, int64_t mfma_off, int64_t tabd_off, int H, int periodic) {
+                               int64_t per_layer_q, int64_t mfma_off, int64_t tabd_off, int H, int periodic,
+                               int64_t ft_off) {
   const int P = 3 * K + 1;
   const int hdr = hdr_floats(K);
   constexpr int MAXK = 64;
@@ -96,6 +97,8 @@ __global__ void prepare_kernel(const float* __restrict__ params, float* __restri
   }
 
   __shared__ double ex[2][MAXK], dl[MAXK + 1], mxs[2];
+  // new parameters: the `first` spline's inverse table (cnf_first_table.h) is stale until its builder has certified it
+  if (ft_off > 0 && threadIdx.x < FT_WORDS) reinterpret_cast<uint32_t*>(prep + ft_off)[threadIdx.x] = 0u;
   if (threadIdx.x < 2) {
     const float* u = params + threadIdx.x * K;
     double mx = u[0];
@@ -346,7 +349,9 @@ struct PwlArgs {
   uint64_t seed;
   int64_t first_sample, slice_stride;
   int32_t in_shared;         // the slices share ONE set of input points in[slice_len, 2] (the same base draw pushed to
-};                           // several times: cnf_kinetic_potential_vjp)
+                             // several times: cnf_kinetic_potential_vjp)
+  const float* ft;           // the `first` spline's inverse table (cnf_first_table.h) with its status words, or null:
+};                           // the closed form.  Read only by the instantiations that have the table path (FTAB).
 
 // Every reference call site hands the flow one time broadcast to cond[B,1] (applications.py:153,226,231):
 // per-sample in form, uniform in content.  For launches large enough for the table path this kernel checks it on
@@ -383,6 +388,21 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     tabd = e2tab + EXP2_N;
     for (int i = tid; i < EXP2_N; i += PWL_THREADS) e2tab[i] = a.m.e2tab[i];
     for (int i = tid; i < hdr_floats(K); i += PWL_THREADS) tabd[i] = a.m.tabd[i];
+  }
+  // The sampling direction at L = 2: the `first` spline from its inverse table where the builder has certified it.
+  // The model-wide word is read once, as a scalar; the table is staged once per workgroup (it does not depend on the
+  // slice; the first tile's barrier covers it).  Not certified, or switched off by the host: the closed form.
+  constexpr bool FTAB = !TO_BASE && FAST && !PRECISE && LFIX == 2 && LROWS >= PWL_NPIECE && K == FT_K;
+  [[maybe_unused]] bool use_ft = false;
+  [[maybe_unused]] FtConsts fc{};
+  if constexpr (FTAB) {
+    if (a.ft)
+      use_ft = __builtin_amdgcn_readfirstlane((int)reinterpret_cast<const uint32_t*>(a.ft)[FT_W_CERT]) == (int)FT_CERTIFIED;
+    if (use_ft) {
+      float* ftl = lds_raw + pwl_flow_lds_floats(K, LFIX, LROWS, false);
+      ft_stage(ftl, a.ft, tid, PWL_THREADS);
+      fc = ft_consts(ftl, sc);
+    }
   }
 
   const int total = a.n_slices * a.tiles_per_slice;
@@ -476,7 +496,11 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     const int slice = tl.slice;
     if (slice != cur) {
       __syncthreads();
-      pwl_stage<LROWS>(tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, tid, PWL_THREADS);
+      // (FTAB: the staging addresses are formed here, once per slice, from a lane index the compiler cannot see
+      // through: hoisted out of the tile loop they are two registers the seeded instantiation has to spill)
+      int stid = tid;
+      if constexpr (FTAB) asm volatile("" : "+v"(stid));
+      pwl_stage<LROWS>(tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, stid, PWL_THREADS);
       cur = slice;
       __syncthreads();
     }
@@ -493,8 +517,13 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void flow_pwl_kernel(const PwlArgs
     if (!TO_BASE && lp && a.aux) base = (u0 * u0 + u1 * u1) * -0.5f - (float)(2 * HALF_LOG_2PI);
     if (!TO_BASE) asm volatile("" : "+v"(base));
     BaseAcc<v2f> bacc;
-    const v2f acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX, true>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
-                                                            u0, u1, &a.m.scd, e2tab, tabd, &bacc);
+    v2f acc;
+    if (FTAB && use_ft)      // wave-uniform (a scalar branch): the whole launch takes one side
+      acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX, true, FTAB>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
+                                                              u0, u1, &a.m.scd, e2tab, tabd, &bacc, fc);
+    else
+      acc = flow2_tables<K, TO_BASE, FAST, PRECISE, true, LROWS, LFIX, true>(tab, tbl, a.tables + (int64_t)slice * L * PWL_TBL, L, sc,
+                                                              u0, u1, &a.m.scd, e2tab, tabd, &bacc);
     // The next tile's points are taken BEFORE this tile's stores are issued: stores count in vmcnt, and a wait for
     // the points behind them is a wait for the stores' acknowledgement -- once per tile, with nothing to overlap it.
     // In front of them only the load and the previous tile's stores are outstanding; these stores drain under the
@@ -973,6 +1002,14 @@ __global__ __launch_bounds__(PWL_MAX_THREADS) void loss_pwl_kernel(const LossPwl
 // ===========================================================================
 using namespace cnf;
 
+void first_table_enqueue(CnfModel* m, hipStream_t stream) {
+  hipLaunchKernelGGL(first_table_kernel<FT_K>, dim3(FT_BLOCKS), dim3(32 * FT_PPB), 0, stream,
+                     reinterpret_cast<const double*>(m->prep + m->tabd_off), m->prep + m->ft_off,
+                     (double)m->cfg.range_min, (double)m->cfg.range_max);
+  m->ft_built = 1;
+  m->ft_wanted = 1;
+}
+
 extern "C" int cnf_model_set_params(CnfModel* m, const float* params, void* stream) {
   if (!m || !params) return CNF_ERR_INVALID;
   const int K = m->cfg.num_bins;
@@ -985,11 +1022,20 @@ extern "C" int cnf_model_set_params(CnfModel* m, const float* params, void* stre
                      m->n_params, (double)m->cfg.range_min, (double)m->cfg.range_max,
                      (double)m->cfg.min_bin_size, (double)m->cfg.min_knot_slope, m->cfg.dim,
                      m->cfg.num_layers, m->cfg.mlp_num_layers, m->per_layer, m->per_layer_q, m->mfma_off,
-                     m->tabd_off, m->cfg.hidden_size, m->cfg.periodized);
+                     m->tabd_off, m->cfg.hidden_size, m->cfg.periodized, m->ft_off);
   if (m->cfg.periodized && m->cfg.dim > 1)
     hipLaunchKernelGGL(circular_slopes_kernel, dim3((unsigned)(m->cfg.num_layers * (m->cfg.dim - 1))), dim3(64), 0,
                        (hipStream_t)stream, params, m->prep, K, m->cfg.hidden_size, m->cfg.dim, m->cfg.num_layers,
                        m->cfg.mlp_num_layers, m->per_layer);
+  // The `first` spline's inverse table (cnf_first_table.h), behind prepare_kernel, which has cleared its status words,
+  // and in front of the event: wait_for_params covers it.  Only for a model whose launches have asked for the table
+  // (run_flow_pwl builds the first one itself): the captured default training step is 0.076 ms of kernels, and a
+  // 9 us builder behind every parameter load of a model that never samples through the table kernel would be a
+  // tenth of it.
+  if (m->ft_off > 0) {
+    m->ft_built = 0;
+    if (m->ft_wanted && pwl_config_ok(m)) first_table_enqueue(m, (hipStream_t)stream);
+  }
   if (hipGetLastError() != hipSuccess) return CNF_ERR_HIP;
   // (inside a stream capture the record would become a graph node and leave the event unusable outside the graph:
   //  a captured step is ordered by its own stream)
@@ -1192,12 +1238,16 @@ static int run_flow_pwl(CnfModel* m, bool to_base, const float* in, const float*
   const int L = m->cfg.num_layers;
   const bool precise = to_base && m->precise;
   // every row of the L tables in LDS if that fits (L <= 3), else the first PWL_LROWS rows
-  auto lds_for = [&](int lrows) {
-    return (size_t)(((cnf::hdr_floats(5) + 3) & ~3) + L * cnf::pwl_ltbl(lrows)) * sizeof(float) +
-           (precise ? precise_lds_bytes(5) : 0);
+  auto lds_for = [&](int lrows, bool first_table) {
+    return (size_t)cnf::pwl_flow_lds_floats(5, L, lrows, first_table) * sizeof(float) + (precise ? precise_lds_bytes(5) : 0);
   };
-  const bool full = lds_for(cnf::PWL_NPIECE) <= 160 * 1024;
-  size_t lds = lds_for(full ? cnf::PWL_NPIECE : cnf::PWL_LROWS);
+  const bool full = lds_for(cnf::PWL_NPIECE, false) <= 160 * 1024;
+  // the `first` spline's inverse table: the sampling direction's L = 2 instantiations, unless the knob asks for the
+  // closed form (the kernel then asks the table's certified word).  The model's first such launch enqueues the builder
+  // here, on its own stream and behind the parameters it has waited for; cnf_model_set_params does from then on.
+  const float* ft = !to_base && full && L == 2 && m->ft_off > 0 && m->first_table_mode == 0 ? m->prep + m->ft_off : nullptr;
+  if (ft && !m->ft_built) first_table_enqueue(m, stream);
+  size_t lds = lds_for(full ? cnf::PWL_NPIECE : cnf::PWL_LROWS, ft != nullptr);
   if (lds > 160 * 1024) return CNF_ERR_UNSUPPORTED;
   const int64_t slice_len = c_block < B ? c_block : B;
   const int64_t n_slices = (B + slice_len - 1) / slice_len;
@@ -1242,7 +1292,7 @@ static int run_flow_pwl(CnfModel* m, bool to_base, const float* in, const float*
     a.in = in ? in + (in_shared ? 0 : first * 2) : nullptr; a.out = out ? out + first * 2 : nullptr; a.aux = aux ? aux + first : nullptr;
     a.seed = noise ? noise->seed : 0; a.slice_stride = noise ? noise->slice_stride : 0;
     a.first_sample = noise ? noise->first_sample + s0 * noise->slice_stride : 0;
-    a.tables = tables;
+    a.tables = tables; a.ft = ft;
     a.B = (B - first) < ns * slice_len ? (B - first) : ns * slice_len;
     a.slice_len = slice_len;
     a.n_slices = (int32_t)ns; a.tiles_per_slice = (int32_t)tps; a.aux_mode = aux_mode;

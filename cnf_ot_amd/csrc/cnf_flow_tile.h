@@ -5,6 +5,7 @@
 #pragma once
 #include "cnf_common.h"
 #include "cnf_pwl.h"
+#include "cnf_first_table.h"
 
 namespace cnf {
 
@@ -298,6 +299,14 @@ __device__ __forceinline__ void tile_store_n(R* __restrict__ g, const R* U, int 
 
 constexpr int PWL_MAX_THREADS = 1024;
 
+// flow_pwl_kernel's dynamic LDS in floats: [header][L tables of `lrows` rows][the `first` spline's inverse table]; the
+// precise path's float64 tables (data -> base) follow the L tables and are counted by the launch site.
+constexpr int pwl_flow_lds_floats(int K, int L, int lrows, bool first_table) {
+  return ((hdr_floats(K) + 3) & ~3) + L * pwl_ltbl(lrows) + (first_table ? FT_LDS_FLOATS : 0);
+}
+static_assert(pwl_flow_lds_floats(FT_K, 2, PWL_NPIECE, true) * sizeof(float) <= 160 * 1024,
+              "the L = 2 kernel holds both conditioner tables and the inverse table");
+
 // The dim-2 flow on one sample pair held in registers, conditioner from the tables (`tbl`: the L
 // tables in LDS, `gtbl`: the same in global memory for rows past the LDS window).  In place;
 // returns the accumulated log|det J| of the direction.
@@ -309,14 +318,19 @@ constexpr int PWL_MAX_THREADS = 1024;
 // LEAN_OK (flow_pwl_kernel): the sampling direction takes the shorter instruction stream of DESIGN 5.1d -- the
 // quadratic's root without a Newton step (the `first` spline everywhere, the conditioned one in shift-free waves),
 // one logarithm per layer, one tail test per layer.  The loss kernel keeps its arithmetic.
+// FTAB (LEAN only): the `first` spline from its certified inverse table `ft` (cnf_first_table.h) instead of the closed
+// form: (out, ld) by lookup, ld added to the sum directly, and the layer's logarithm takes the conditioned spline's
+// argument alone.  The caller chooses between the two instantiations with one wave-uniform branch.
 template <int K, bool TO_BASE, bool FAST, bool PRECISE = false, bool SHIFT_FREE_OK = false, int LROWS = PWL_LROWS, int LFIX = 0,
-          bool LEAN_OK = false>
+          bool LEAN_OK = false, bool FTAB = false>
 __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, const float* __restrict__ gtbl,
                                             int L, const SplineConsts sc, v2f& u0, v2f& u1,
                                             const PreciseConsts* pc = nullptr, const double* e2tab = nullptr,
-                                            const double* tabd = nullptr, BaseAcc<v2f>* bacc = nullptr) {
+                                            const double* tabd = nullptr, BaseAcc<v2f>* bacc = nullptr,
+                                            const FtConsts ft = FtConsts{}) {
   constexpr bool INV = !TO_BASE;
   constexpr bool LEAN = LEAN_OK && INV && FAST;
+  static_assert(!FTAB || LEAN, "the inverse table: the lean sampling direction");
   static_assert(!PRECISE || TO_BASE, "precise path: data -> base");
   v2f acc = splat<v2f>(0.0f);
   [[maybe_unused]] v2f lo0 = splat<v2f>(0.0f), lo1 = lo0;      // precise path: what rounding u0 / u1 to fp32 dropped
@@ -345,6 +359,9 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       // dependent LDS round trips) are issued first and complete under the arithmetic of the `first` spline
       PwlRows rr;
       v2f qa[K], qb[K];
+      // (the inverse table's lookup goes first: its two LDS round trips and ten packed FMAs leave little for the
+      // conditioner's reads to hide under, and a row of each in flight at once costs registers the kernel does not have)
+      if constexpr (FTAB) ft_eval(ft, uf, of, ld);
       if (!TO_BASE) {
         pwl_find<LROWS>(tl, uf, rr, general);
         rr.dua = pwl_logit_pairs<LROWS>(rr.ra, gl, rr.pa, uf.x, qa);
@@ -362,7 +379,10 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       bool tails = true;
       if constexpr (LEAN) tails = __builtin_amdgcn_ballot_w64(maybe_outside(uf, uo, sc.lo, sc.hi)) != 0;
       v2f larg = splat<v2f>(1.0f);
-      if constexpr (LOGPROD) {
+      if constexpr (FTAB) {
+        if (tails) table_spline_tails<K, INV, false, v2f>(tab, uf, sc, of, ld);
+        acc += ld;
+      } else if constexpr (LOGPROD) {
         table_spline<K, INV, FAST, v2f, true, LEAN>(tab, uf, sc, of, larg, tails);
       } else {
         table_spline<K, INV, FAST, v2f, false, LEAN>(tab, uf, sc, of, ld, tails);
@@ -380,10 +400,10 @@ __device__ __forceinline__ v2f flow2_tables(const float* tab, const float* tbl, 
       if (!SHIFT_FREE_OK || __builtin_amdgcn_ballot_w64(general) != 0)      // wave-uniform: a lane's cell is marked
       {       // marked cells (ill-conditioned pieces, far-out inputs): the general form, and its own logarithm
         cond_spline_rows<K, INV, FAST, false, false, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
-        if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg); ld += INV ? -lg : lg; }
+        if constexpr (LOGPROD && !FTAB) { const v2f lg = Math<FAST>::log(larg); ld += INV ? -lg : lg; }
       } else {
         cond_spline_rows<K, INV, FAST, true, LOGPROD, LEAN>(qa, qb, slopes, uo, sc, oo, ld, tails);
-        if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(larg * ld); ld = INV ? -lg : lg; }
+        if constexpr (LOGPROD) { const v2f lg = Math<FAST>::log(FTAB ? ld : larg * ld); ld = INV ? -lg : lg; }
       }
     }
     acc += ld;

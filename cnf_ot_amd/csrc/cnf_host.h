@@ -40,6 +40,10 @@ int cnf_internal_build_tables(CnfModel* m, hipStream_t stream, const float* c, i
 int cnf_internal_flow_shared(CnfModel* m, hipStream_t stream, const float* in, const float* c, int64_t slice_len,
                              int64_t n_slices, const float* tables, float* out);
 
+// Enqueues first_table_kernel (cnf_first_table.h) for the model's current parameters on `stream`, which must be ordered
+// behind the last cnf_model_set_params, and marks the table built and wanted.  A kernel enqueue only.
+void first_table_enqueue(CnfModel* m, hipStream_t stream);
+
 // ---- cnf_importance.hip ---------------------------------------------------------------------------------------------
 // importance_kernel and importance_finish_kernel behind cnf_importance_workspace / cnf_importance_stats(_seeded)
 // (include/cnf_ot_amd.h).  The unit calls into no other and none calls into it: it shares the headers -- the tile

@@ -4,6 +4,7 @@
 // cnf_flow.hip.  Declarations: include/cnf_ot_amd.h.
 #include "cnf_host.h"
 #include "cnf_pwl.h"
+#include "cnf_first_table.h"
 
 #include <math.h>
 #include <new>
@@ -105,7 +106,14 @@ extern "C" int cnf_model_create(const CnfConfig* cfg, CnfModel** out) {
   // 2^(-i/32), i = 0 .. 1024, float64: the table of the precise position path (cnf_device.h)
   m->e2_off = m->tabd_off + 2 * hdr_floats(K);
   m->precise = 1;
-  const size_t bytes = (size_t)(m->e2_off + 2 * cnf::EXP2_N) * sizeof(float) + 64;
+  // the `first` spline's inverse table (cnf_first_table.h), behind everything else: only for the models whose kernels
+  // read one (the dim-2 table path at L = 2)
+  int64_t n_floats = m->e2_off + 2 * cnf::EXP2_N;
+  if (pwl_network(*cfg) && cfg->num_layers == 2 && K == cnf::FT_K) {
+    m->ft_off = (n_floats + 3) & ~(int64_t)3;
+    n_floats = m->ft_off + cnf::FT_FLOATS;
+  }
+  const size_t bytes = (size_t)n_floats * sizeof(float) + 64;
   m->scd.lo = (double)cfg->range_min; m->scd.hi = (double)cfg->range_max;
   m->scd.min_bin = (double)cfg->min_bin_size; m->scd.min_slope = (double)cfg->min_knot_slope;
   m->scd.span_eff = (m->scd.hi - m->scd.lo) - (double)K * m->scd.min_bin;
@@ -206,6 +214,29 @@ extern "C" int cnf_model_set_pwl(CnfModel* m, int mode) {
   if (!m || mode < 0 || mode > 2) return CNF_ERR_INVALID;
   m->use_pwl = mode;
   return CNF_OK;
+}
+
+/* Internal knob: the `first` spline of the sampling direction's L = 2 table kernels -- 0 (default) = from its inverse
+ * table where the builder has certified it (cnf_first_table.h), 1 = always the closed form. */
+extern "C" int cnf_model_set_first_table(CnfModel* m, int mode) {
+  if (!m || mode < 0 || mode > 1) return CNF_ERR_INVALID;
+  m->first_table_mode = mode;
+  return CNF_OK;
+}
+
+extern "C" int64_t cnf_internal_first_table_floats(void) { return cnf::FT_FLOATS; }
+
+/* Test entry point: the inverse table as the last cnf_model_set_params left it -- status words, grid, rows
+ * (cnf_first_table.h) -- copied to the host buffer out[cnf_internal_first_table_floats()]; waits for the copy.
+ * Builds the table first if no launch has asked for it yet.  CNF_ERR_UNSUPPORTED: the model has no table path. */
+extern "C" int cnf_internal_first_table(CnfModel* m, void* stream, float* out) {
+  if (!m || !out || !m->params_set) return CNF_ERR_INVALID;
+  if (m->ft_off <= 0 || !pwl_config_ok(m)) return CNF_ERR_UNSUPPORTED;
+  if (wait_for_params(m, (hipStream_t)stream) != CNF_OK) return CNF_ERR_HIP;
+  if (!m->ft_built) first_table_enqueue(m, (hipStream_t)stream);      // (as the model's first table launch would)
+  if (hipMemcpyAsync(out, m->prep + m->ft_off, sizeof(float) * (size_t)cnf::FT_FLOATS, hipMemcpyDeviceToHost,
+                     (hipStream_t)stream) != hipSuccess) return CNF_ERR_HIP;
+  return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? CNF_OK : CNF_ERR_HIP;
 }
 
 /* Internal knob: which kernel builds the dim-2 tables -- 0 = by table count (default; build_tables in cnf_flow.hip),

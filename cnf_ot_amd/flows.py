@@ -255,6 +255,27 @@ class FlowEngine:
     reference builder, 2 = the lean one (one wave per table)."""
     _capi.check(self.lib.cnf_model_set_pwl_builder(self._h, int(mode)), "cnf_model_set_pwl_builder")
 
+  def set_first_table(self, mode: int) -> None:
+    """The `first` spline of the sampling direction's L = 2 table kernels: 0 = from its certified inverse table where
+    the builder has certified it (default), 1 = always the closed form."""
+    _capi.check(self.lib.cnf_model_set_first_table(self._h, int(mode)), "cnf_model_set_first_table")
+
+  def first_table(self):
+    """(certified, grid float32 [FT_CELLS, 4], rows float32 [FT_CELLS + FT_K - 1, FT_ROW]) of the inverse table the
+    last load() built, on the host (tests only: waits for the copy).  Grid column 2 holds a row's byte offset as
+    integer bits.  The layout is first_table.py's (cnf_first_table.h)."""
+    from . import first_table as ft
+    n_grid, n_rows = 4 * ft.FT_CELLS, (ft.FT_CELLS + ft.FT_K - 1) * ft.FT_ROW
+    n = int(self.lib.cnf_internal_first_table_floats())
+    if n != ft.FT_WORDS + n_grid + n_rows:
+      raise RuntimeError(f"the library's inverse table has {n} floats, first_table.py describes {ft.FT_WORDS + n_grid + n_rows}")
+    buf = np.empty(n, dtype=np.float32)
+    with _OnDevice(self.device):
+      _capi.check(self.lib.cnf_internal_first_table(self._h, _stream_ptr(self.device), buf.ctypes.data), "cnf_internal_first_table")
+    words = buf[:ft.FT_WORDS].view(np.uint32)
+    grid = buf[ft.FT_WORDS:ft.FT_WORDS + n_grid].reshape(ft.FT_CELLS, 4)
+    return bool(words[0] == ft.FT_CERTIFIED), grid, buf[ft.FT_WORDS + n_grid:].reshape(-1, ft.FT_ROW)
+
   def last_pwl_builder(self) -> int:
     """The builder the most recent table build ran (0: none yet)."""
     return self.lib.cnf_model_last_pwl_builder(self._h)

@@ -39,6 +39,19 @@ int cnf_model_last_pwl_builder(const CnfModel *m);
  * Nothing else shows table bytes: the builder tests compare them. */
 int cnf_internal_build_tables_into(CnfModel *m, void *stream, const float *c, float c_offset, int64_t n, float *out);
 
+/* The `first` spline of the sampling direction's L = 2 table kernels: 0 (default) from its certified inverse table
+ * (built on the device by the model's first such launch and by every cnf_model_set_params after it;
+ * csrc/cnf_first_table.h) where the builder has certified it, 1 always
+ * the closed form -- the arithmetic the other kernels keep, and what tests and A/B runs compare against. */
+int cnf_model_set_first_table(CnfModel *m, int mode);
+
+/* The inverse table as the last cnf_model_set_params left it, copied to the host buffer
+ * out[cnf_internal_first_table_floats()]: 4 status words (word 0: 0x31305446 where certified, else 0), 1024 grid
+ * entries of 4 floats, 1028 rows of 12.  Builds the table first if no launch has asked for it yet.  Waits for the copy:
+ * not for use inside a stream capture.  CNF_ERR_UNSUPPORTED: the model has no table path. */
+int64_t cnf_internal_first_table_floats(void);
+int cnf_internal_first_table(CnfModel *m, void *stream, float *out);
+
 /* wave-per-dimension kernel (base -> data, dim >= 3): 1 (default) by batch size, 2 always, 0 never. */
 int cnf_model_set_dpar(CnfModel *m, int mode);
 
