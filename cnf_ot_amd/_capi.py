@@ -206,6 +206,12 @@ SYMBOLS = {
   "cnf_mmd_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
   "cnf_mmd2": (ctypes.c_int, [ctypes.POINTER(CnfMmdSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P, _P, _P,
                               _I64, _P]),
+  # the permutation test of the same statistic: labels [N + M, P / 32] words, stats [S, P] doubles, raw [S, P, 2] doubles
+  # (q, r) followed by t [S], or NULL
+  "cnf_mmd_perm_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_mmd_perm_splits": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32]),
+  "cnf_mmd_perm": (ctypes.c_int, [ctypes.POINTER(CnfMmdSpec), ctypes.c_int32, _P, _I64, _P, _I64, ctypes.c_int32, _P,
+                                  ctypes.c_int32, _P, _P, _P, _I64, _P]),
   # the Sinkhorn divergence of point clouds (eps: a host array of doubles): sums [S, 6] doubles, potentials
   # [S, 2 N + 2 M], xgrad and xmap [S, N, D]
   "cnf_sinkhorn_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),

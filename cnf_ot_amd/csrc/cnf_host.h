@@ -59,6 +59,11 @@ void first_table_enqueue(CnfModel* m, hipStream_t stream);
 // mmd_kernel and mmd_finish_kernel behind cnf_mmd_workspace / cnf_mmd_splits / cnf_mmd2 (include/cnf_ot_amd.h).
 // Model-free, like cnf_fp_particles.hip: the unit calls into no other and none calls into it.
 
+// ---- cnf_mmd_perm.hip -----------------------------------------------------------------------------------------------
+// perm_counts_kernel, perm_kernel and perm_finish_kernel behind cnf_mmd_perm_workspace / cnf_mmd_perm_splits /
+// cnf_mmd_perm (include/cnf_ot_amd.h): the first pair pass on the matrix cores.  It restates cnf_mmd.hip's pair value
+// and calls into no other unit.
+
 // ---- cnf_sinkhorn.hip -----------------------------------------------------------------------------------------------
 // sinkhorn_pair_kernel, sinkhorn_merge_kernel and sinkhorn_finish_kernel behind cnf_sinkhorn_workspace /
 // cnf_sinkhorn_splits / cnf_sinkhorn (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).

@@ -539,6 +539,50 @@ def print_fp_two_sample(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | {:.3e}".format(*row))
 
 
+def evaluate_fp_permutation(config, model: FlowModel, params: Params, times=None, n_particles=16384, h=1e-3, seed=0,
+                            n_perm=255, bandwidths=None) -> Dict[str, Any]:
+  """evaluate_fp_two_sample's values as p-values: per time of `times` (default, refusals, halves and bandwidth rule as
+  evaluate_fp_two_sample), the permutation test of n_particles / 2 flow samples against half 0 of the Euler-Maruyama
+  ensemble, and of half 1 against half 0, under n_perm relabellings of the pooled sample
+  (utils.permutation_labels(n_particles / 2, n_particles / 2, n_perm, seed): the same label vectors at every time and
+  for both pairs).  Lists of floats, one per time:
+    times
+    mmd2, p_mmd2                  the unbiased Gaussian MMD^2 of flow against half 0 and its p-value
+                                  (1 + #{null >= mmd2}) / (1 + n_perm): can the two samples be told apart, at what level
+    energy, p_energy              the same for the energy distance
+    mmd2_halves, p_mmd2_halves, energy_halves, p_energy_halves
+                                  the same four of half 1 against half 0: two samples of one law, so these p-values are
+                                  uniform on (0, 1] -- what shows that the test is calibrated
+    bandwidths, n_perm            the bandwidths and the number of relabellings used
+  One cnf_mmd_perm call per kind and pair over all times (utils.mmd_permutation_test).  ValueError unless n_perm + 1 is
+  a multiple of 32 within 32..1024.  Single process."""
+  _, ts, n_particles, fp = _fp_prelude("evaluate_fp_permutation", config, times, n_particles, h, 4)
+  if bandwidths is not None:
+    utils.mmd_spec(bandwidths, "gaussian")
+  labels = utils.permutation_labels(n_particles // 2, n_particles // 2, n_perm, seed)
+  flow, h0, h1 = _fp_flow_and_halves(model, params, fp, ts, n_particles, h, seed)
+  bws = utils.median_bandwidths(h0) if bandwidths is None else bandwidths
+  out: Dict[str, Any] = {"times": [float(t) for t in ts], "n_perm": int(n_perm)}
+  for kind, key in (("gaussian", "mmd2"), ("energy", "energy")):
+    for first, tail in ((flow, ""), (h1, "_halves")):
+      res = utils.mmd_permutation_test(first, h0, bws, kind, labels=labels)
+      out[key + tail] = res["mmd2"].tolist()
+      out["p_" + key + tail] = res["p_value"].tolist()
+      if kind == "gaussian":
+        out["bandwidths"] = res["bandwidths"]
+  return out
+
+
+def print_fp_permutation(res: Dict[str, Any]) -> None:
+  """evaluate_fp_permutation's table, one line per time"""
+  print(f"permutation tests against the particle reference ({res['n_perm']} relabellings, bandwidths "
+        + " ".join(f"{b:.3g}" for b in res["bandwidths"])
+        + "):  t | mmd2 (p) | energy (p) | halves: mmd2 (p) | halves: energy (p)")
+  for row in zip(res["times"], res["mmd2"], res["p_mmd2"], res["energy"], res["p_energy"], res["mmd2_halves"],
+                 res["p_mmd2_halves"], res["energy_halves"], res["p_energy_halves"]):
+    print("  {:.4f} | {:.3e} ({:.4f}) | {:.3e} ({:.4f}) | {:.3e} ({:.4f}) | {:.3e} ({:.4f})".format(*row))
+
+
 # ---- the flow's fields against the ensemble's: log-density, score and the velocity the flow-matching term trains -------
 
 FP_FIELD_KEYS = ("times", "bandwidth", "logp_rmse", "logp_rmse_floor", "score_rel_err", "score_rel_err_floor",
@@ -1215,7 +1259,8 @@ def _eval_rng(seed, step):
 def main(config, epochs: Optional[int] = None, capture: bool = False, save: Optional[str] = None,
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
-         interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False) -> Dict[str, Any]:
+         interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False,
+         permutation_test: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
@@ -1223,13 +1268,15 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
   `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables.
-  field_errors (fp): print evaluate_fp_fields' table."""
+  field_errors (fp): print evaluate_fp_fields' table.  permutation_test (fp): print evaluate_fp_permutation's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
     raise Exception(f"Unknown problem type: {_type}...")
   if two_sample and _type != "fp":      # (before the training run, not after it)
     raise ValueError(f"--two-sample compares the flow with the fp particle reference: not defined for {_type}")
+  if permutation_test and _type != "fp":
+    raise ValueError(f"--permutation-test compares the flow with the fp particle reference: not defined for {_type}")
   if sliced and _type != "fp":
     raise ValueError(f"--sliced compares the flow with the fp particle reference: not defined for {_type}")
   if knn and _type != "fp":
@@ -1308,6 +1355,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_ksd(evaluate_ksd(config, model, params))
   if field_errors:
     print_fp_fields(evaluate_fp_fields(config, model, params))
+  if permutation_test:
+    print_fp_permutation(evaluate_fp_permutation(config, model, params))
   return res
 
 
@@ -1350,6 +1399,10 @@ def _parse(argv):
   p.add_argument("--field-errors", action="store_true",
                  help="print the errors of the flow's log-density, score and velocity, in the full dimension, against the "
                       "kernel density estimate of the particle reference, each beside its Monte-Carlo floor (fp)")
+  p.add_argument("--permutation-test", action="store_true",
+                 help="print MMD^2 and the energy distance between the flow's samples and the particle reference with "
+                      "their permutation p-values (255 relabellings), beside the same test between the reference's two "
+                      "halves (fp)")
   return p.parse_args(argv)
 
 
@@ -1358,4 +1411,4 @@ if __name__ == "__main__":
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
        sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd,
-       field_errors=args.field_errors)
+       field_errors=args.field_errors, permutation_test=args.permutation_test)

@@ -1,7 +1,7 @@
 """Distances between two point clouds -- what compares a flow with a target that exists only as samples: the kernel
-two-sample statistics (cnf_mmd2), the Sinkhorn divergence (cnf_sinkhorn), the sliced Wasserstein distance
-(cnf_sliced_w2) and the nearest-neighbour estimates of entropy and KL (cnf_knn).  The kernels are four units
-(DESIGN.md 5.3h-j, 5.3l); what surrounds a call is stated once here: the sets
+two-sample statistics (cnf_mmd2) and their permutation test (cnf_mmd_perm), the Sinkhorn divergence (cnf_sinkhorn), the
+sliced Wasserstein distance (cnf_sliced_w2) and the nearest-neighbour estimates of entropy and KL (cnf_knn).  The
+kernels are five units; what surrounds a call is stated once here: the sets
 as [S, N, D] (`_sets`), the shape check (`_check_shapes`), the staging on the device (`_stage`), the workspace
 (`_workspace`), the result of a 2-D x (`_unstack`), one call per 64 sets (`_per_64_sets`) and a spec's numbers as
 float32 holds them (`_floats32`, `_fits`).  `utils` re-exports the public names.
@@ -182,6 +182,115 @@ def mmd2(x, y, bandwidths=None, kind="gaussian", want_grad=False) -> dict:
   if want_grad:
     out["grad"] = _unstack(grad, one)
   return out
+
+
+# ---- the permutation test of the kernel two-sample statistics: a value of MMD^2 as a p-value --------------------------
+# The statistic is recomputed under relabellings of the pooled sample and the observed value is ranked among them.  One
+# cnf_mmd_perm call forms every pair kernel value once and uses it for all label vectors, on the
+# matrix cores; as calls of mmd2 on shuffled copies the same test evaluates every pair value once per vector.
+
+PERM_MIN_VECTORS, PERM_MAX_VECTORS, PERM_MAX_POINTS = 32, 1024, 1 << 20
+
+
+def permutation_labels(N, M, n_perm, seed=0):
+  """The label words of a permutation test of N against M points, an int32 CPU tensor [N + M, (n_perm + 1) / 32]: bit b
+  of word w of pooled point j (j < N: x_j, else y_{j - N}) is set where j belongs to the first sample under label
+  vector 32 w + b.  Vector 0 is the identity labelling (the first N points); vectors 1..n_perm are uniform random
+  subsets of size N, drawn by numpy's default_rng(seed) -- a fixed function of (N, M, n_perm, seed).  ValueError unless
+  n_perm + 1 is a multiple of 32 within 32..1024 and N, M >= 1."""
+  N, M, P = int(N), int(M), int(n_perm) + 1
+  if P % 32 or not PERM_MIN_VECTORS <= P <= PERM_MAX_VECTORS:
+    raise ValueError(f"permutation_labels: n_perm + 1 must be a multiple of 32 within {PERM_MIN_VECTORS}.."
+                     f"{PERM_MAX_VECTORS}, not {P}")
+  if N < 1 or M < 1:
+    raise ValueError(f"permutation_labels: needs N, M >= 1, not {N}, {M}")
+  rng = np.random.default_rng(int(seed))
+  member = np.zeros((N + M, P), dtype=bool)
+  member[:N, 0] = True
+  for p in range(1, P):
+    member[rng.choice(N + M, size=N, replace=False, shuffle=False), p] = True
+  return pack_labels(member)
+
+
+def pack_labels(member):
+  """Label words [n, P / 32] (int32 CPU tensor) of a membership matrix [n, P] (True: first sample), P a multiple of 32"""
+  member = np.asarray(member, dtype=bool)
+  n, P = member.shape
+  if P % 32:
+    raise ValueError(f"pack_labels: the number of label vectors must be a multiple of 32, not {P}")
+  words = (member.reshape(n, P // 32, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(-1, dtype=np.uint32)
+  return torch.from_numpy(words.view(np.int32).copy())
+
+
+def mmd_perm_check_shapes(x_shape, y_shape, labels_shape=None):
+  """ValueError for what cnf_mmd_perm refuses: ([S, N, D], [S, M, D], [N + M, W]) with S in 1..64, N, M >= 2, N + M <=
+  2^20, D in 1..14 and W = P / 32 words in 1..32."""
+  _check_shapes("mmd_perm", x_shape, y_shape, 2, PERM_MAX_POINTS)
+  n = x_shape[1] + y_shape[1]
+  if n > PERM_MAX_POINTS:
+    raise ValueError(f"mmd_perm: the pooled sample has at most 2^20 points, not {n}")
+  if labels_shape is not None and (len(labels_shape) != 2 or labels_shape[0] != n
+                                   or not 1 <= labels_shape[1] <= PERM_MAX_VECTORS // 32):
+    raise ValueError(f"mmd_perm: labels must be [{n}, P / 32] words with P in {PERM_MIN_VECTORS}..{PERM_MAX_VECTORS}, not "
+                     f"{tuple(labels_shape)}")
+
+
+def permutation_p_value(observed, null):
+  """(1 + #{null >= observed}) / (1 + n_perm) for observed [S] and null [S, n_perm]: the usual estimate, never 0; a
+  tie counts."""
+  return (1.0 + (null >= observed[:, None]).sum(1).double()) / (1.0 + null.shape[1])
+
+
+def mmd_permutation_test(x, y, bandwidths=None, kind="gaussian", n_perm=255, seed=0, labels=None) -> dict:
+  """The permutation test of the unbiased kernel two-sample statistic between the point sets x [N, D] or [S, N, D] and
+  y [M, D] or [S, M, D] (set s of x against set s of y; kind and bandwidths as `mmd2`, None: median_bandwidths(y)): the
+  statistic under n_perm relabellings of the pooled sample, ONE cnf_mmd_perm call per 64 sets.  labels: the label words
+  [N + M, P / 32] (None: permutation_labels(N, M, n_perm, seed)); with labels given, n_perm = P - 1 and vector 0 is
+  taken as the observed labelling.  The same label vectors serve all sets.  float32 on the device.  Returns a dict:
+    mmd2 [S]          label vector 0's statistic (float64)
+    null [S, n_perm]  the statistic under vectors 1..n_perm
+    p_value [S]       (1 + #{null >= mmd2}) / (1 + n_perm)
+    counts [P]        the first sample's size under every vector (int64, CPU)
+    bandwidths        a list; empty for energy
+    raw               {"q": [S, P], "r": [S, P], "t": [S]}: s' K s, 1' K s and 1' K 1 of the pooled zero-diagonal kernel
+                      matrix, from which every value can be audited
+  Evaluation only: no gradient.  Two calls give the same bits.  ValueError before any device work for what the C ABI
+  refuses and for x, y and labels that do not fit together."""
+  x3, y3 = _sets("mmd_perm", x, "x"), _sets("mmd_perm", y, "y")
+  (S, N, D), M = x3.shape, y3.shape[1]
+  if S != y3.shape[0]:
+    raise ValueError(f"mmd_perm: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in the number of sets")
+  one_call = [(min(S, _capi.MMD_MAX_SETS),) + tuple(t.shape[1:]) for t in (x3, y3)]      # (any S: 64 sets per call)
+  mmd_perm_check_shapes(*one_call)
+  if labels is None:
+    labels = permutation_labels(N, M, n_perm, seed)
+  labels = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+  mmd_perm_check_shapes(*one_call, tuple(labels.shape))
+  if labels.dtype != torch.int32:
+    raise ValueError(f"mmd_perm: labels are int32 words, not {labels.dtype}")
+  P = 32 * labels.shape[1]
+  if kind == "gaussian" and bandwidths is None:
+    bandwidths = median_bandwidths(y3)
+  spec, bws = mmd_spec(bandwidths, kind)
+  dev, one, (x3, y3) = _stage(x, x3, y3)
+  words = labels.detach().to(device=dev).contiguous()
+
+  def call(xc, yc):
+    Sc = xc.shape[0]
+    ws = _workspace(dev, _workspace_bytes("cnf_mmd_perm_workspace", Sc, N, M, D, P))
+    stats = torch.empty(Sc, P, dtype=torch.float64, device=dev)
+    raw = torch.empty(Sc * (2 * P + 1), dtype=torch.float64, device=dev)
+    with _OnDevice(dev):
+      _capi.check(_capi.lib().cnf_mmd_perm(_capi.ctypes.byref(spec), Sc, xc.data_ptr(), N, yc.data_ptr(), M, D,
+                                           words.data_ptr(), P, stats.data_ptr(), raw.data_ptr(), ws.data_ptr(),
+                                           ws.numel() * 8, _stream_ptr(dev)), "cnf_mmd_perm")
+    return stats, raw[:Sc * 2 * P].view(Sc, P, 2), raw[Sc * 2 * P:]
+
+  stats, qr, t = _per_64_sets(call, x3, y3)
+  bits = (labels.cpu().numpy().view(np.uint32)[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
+  return {"mmd2": stats[:, 0], "null": stats[:, 1:], "p_value": permutation_p_value(stats[:, 0], stats[:, 1:]),
+          "counts": torch.from_numpy(bits.reshape(N + M, P).sum(0, dtype=np.int64)), "bandwidths": bws,
+          "raw": {"q": qr[..., 0], "r": qr[..., 1], "t": t}}
 
 
 # ---- the Sinkhorn divergence: an optimal-transport estimate between point clouds, in transport units -----------------

@@ -3,7 +3,7 @@
     65 536 samples.  The reference issues 2-3 jitted sample calls (+ 2*dim log_prob calls) per slice from a Python
     loop; here a chunk of slices is ONE fused launch (grid over (slice, sample tile)) that returns one sum per slice;
   - the arrays under its figures (:598-798): density, velocity and score fields, trajectories, and `point_stats`;
-  - the distances between two point clouds (mmd2, sinkhorn, sliced_wasserstein and their helpers), which live in
+  - the distances between two point clouds (mmd2, mmd_permutation_test, sinkhorn, sliced_wasserstein and their helpers), which live in
     `two_sample` and are re-exported here, as are the interaction energy of one cloud (`interaction`) and the kernel
     Stein discrepancy of a cloud against a score (`stein`) and the kernel density estimate of a cloud with its score
     (`kde`).
@@ -19,6 +19,8 @@ from .distributed import Shard, all_reduce_sums, current_shard, shard_range
 from .flows import _OnDevice, _stream_ptr
 from .two_sample import (  # noqa: F401
     MEDIAN_BANDWIDTH_FACTORS, median_bandwidths, mmd_spec, mmd_check_shapes, mmd2_from_sums, mmd2,
+    PERM_MIN_VECTORS, PERM_MAX_VECTORS, PERM_MAX_POINTS, permutation_labels, pack_labels, mmd_perm_check_shapes,
+    permutation_p_value, mmd_permutation_test,
     SINKHORN_MAX_ITERS, SINKHORN_MAX_POINTS, sinkhorn_check_shapes, sinkhorn_check_schedule, sinkhorn_schedule, sinkhorn,
     SLICED_MAX_PROJ, SLICED_MAX_POINTS, SLICED_WORKSPACE_BYTES, sliced_directions, sliced_check_shapes, sliced_group,
     sliced_wasserstein,

@@ -803,6 +803,37 @@ int cnf_mmd2(const CnfMmdSpec *spec, int32_t S, const float *x, int64_t N, const
              int64_t M, int32_t D, double *sums, float *xgrad, void *workspace,
              int64_t workspace_bytes, void *stream);
 
+/* ---- the permutation test of the kernel two-sample statistic: P relabellings of the pooled sample at once -----------
+ * What turns a value of MMD^2 into a p-value.  With the pooled sample z = (x, y) of set s, n = N + M points (pooled
+ * index i < N: x_i, otherwise y_{i - N}), its zero-diagonal kernel matrix K (cnf_mmd2's kernel value, in the same
+ * float32 operations and order) and a label vector s in {+1, -1}^n (+1: "first sample"),
+ *   q = s' K s,   r = 1' K s,   t = 1' K 1,
+ *   sum_xx = (t + 2 r + q) / 4,   sum_yy = (t - 2 r + q) / 4,   sum_xy = (t - q) / 4,
+ *   MMD^2 = sum_xx / (N_s (N_s - 1)) + sum_yy / (M_s (M_s - 1)) - 2 sum_xy / (N_s M_s),
+ * N_s the number of +1 labels and M_s = n - N_s.  For P label vectors C = K S' is a matrix product whose left factor is
+ * generated on the fly and never stored: each kernel value is formed once and used P times, on the exact-fp32 MFMA.
+ * labels [n, P / 32] (device, uint32, shared by all S sets): bit b of word w of point j is label vector 32 w + b, set
+ * where point j belongs to the first sample under that vector.  The counts N_p, M_p are read from the labels; any
+ * split with N_p >= 2 and M_p >= 2 is legal, and for a vector outside that range stats is NaN for that vector alone.
+ * cnf_mmd_perm writes stats [S, P] (device, double, overwritten): MMD^2_u (with the energy kernel, the energy
+ * distance) per set and label vector; and, with raw (device, double, optional, overwritten), raw [S, P, 2] = (q, r)
+ * followed by t [S] -- what a rank or a call is audited from.  t is computed by the call, not taken from the labels.
+ * No float32 accumulator holds more than 64 pair terms before it is added into a double; the column splits are
+ * cnf_mmd_perm_splits(S, N, M, D) (a function of the sizes alone); the partial sums are added in a fixed ascending
+ * order: no atomics, two calls are bit-identical, the result does not depend on what the workspace held, and a label
+ * vector's q and r do not depend on P, on its position among the vectors or on the other vectors.  The spec is a HOST
+ * argument.  cnf_mmd_perm_workspace: the bytes of device workspace (8-byte aligned) such a call needs; no HIP call.
+ * cnf_mmd_perm neither allocates nor synchronises (legal inside a stream capture).
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x, y, labels, stats or workspace; D outside
+ * 1..14; S outside 1..64; N or M < 2; N + M > 2^20; P not a multiple of 32 or outside 32..1024; what cnf_mmd2 refuses
+ * in a spec; a workspace smaller than cnf_mmd_perm_workspace says. */
+int cnf_mmd_perm_workspace(int32_t S, int64_t N, int64_t M, int32_t D, int32_t P, int64_t *bytes);
+/* the column splits of the pooled sample at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_mmd_perm_splits(int32_t S, int64_t N, int64_t M, int32_t D);
+int cnf_mmd_perm(const CnfMmdSpec *spec, int32_t S, const float *x, int64_t N, const float *y,
+                 int64_t M, int32_t D, const uint32_t *labels, int32_t P, double *stats, double *raw,
+                 void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the Sinkhorn divergence between point clouds: the optimal-transport reference of the ot problems ---------------
  * Debiased entropic optimal transport with the cost C(x, y) = |x - y|^2 / 2 and uniform weights, in the log domain.
  * Model-free.  For S independent sets, x [S, N, D] against y [S, M, D] (device, float32) and a HOST array
