@@ -248,6 +248,12 @@ SYMBOLS = {
   "cnf_stein_splits": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32]),
   "cnf_stein": (ctypes.c_int, [ctypes.POINTER(CnfSteinSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P, _P, _P, _P,
                                _P, _I64, _P]),
+  # the wild bootstrap of the same statistic: signs [N, P / 32] words, stats [S, P] doubles, raw = q [S, P], t [S] and
+  # the diagonal sum [S] doubles, or NULL
+  "cnf_stein_boot_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_stein_boot_splits": (ctypes.c_int, [ctypes.c_int32, _I64, ctypes.c_int32]),
+  "cnf_stein_boot": (ctypes.c_int, [ctypes.POINTER(CnfSteinSpec), ctypes.c_int32, _P, _P, _I64, ctypes.c_int32, _P,
+                                    ctypes.c_int32, _P, _P, _P, _I64, _P]),
   # the kernel density estimate of x [S, N, D] at q [S, Q, D] (NULL: at x itself): log_rho [S, n_bw, Q], score
   # [S, n_bw, Q, D], sums [S, n_bw] doubles, each or NULL
   "cnf_kde_workspace": (ctypes.c_int, [ctypes.c_int32, _I64, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

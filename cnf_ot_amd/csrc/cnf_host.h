@@ -64,6 +64,11 @@ void first_table_enqueue(CnfModel* m, hipStream_t stream);
 // cnf_mmd_perm (include/cnf_ot_amd.h): the first pair pass on the matrix cores.  It restates cnf_mmd.hip's pair value
 // and calls into no other unit.
 
+// ---- cnf_stein_boot.hip ---------------------------------------------------------------------------------------------
+// boot_kernel and boot_finish_kernel behind cnf_stein_boot_workspace / cnf_stein_boot_splits / cnf_stein_boot
+// (include/cnf_ot_amd.h): the second pair pass on the matrix cores.  It restates cnf_stein.hip's pair value and spec
+// checks and cnf_mmd_perm.hip's skeleton, and calls into no other unit.
+
 // ---- cnf_sinkhorn.hip -----------------------------------------------------------------------------------------------
 // sinkhorn_pair_kernel, sinkhorn_merge_kernel and sinkhorn_finish_kernel behind cnf_sinkhorn_workspace /
 // cnf_sinkhorn_splits / cnf_sinkhorn (include/cnf_ot_amd.h).  Model-free as well; it shares launch_plain (cnf_common.h).

@@ -1,5 +1,5 @@
 // cnf_pairs.h -- what the pair passes share: every row of a point set against every column, in column splits, with a
-// fixed-order finish (cnf_mmd, cnf_mmd_perm, cnf_knn, cnf_sinkhorn, cnf_interaction, cnf_interaction_vjp, cnf_stein, cnf_kde).  The
+// fixed-order finish (cnf_mmd, cnf_mmd_perm, cnf_knn, cnf_sinkhorn, cnf_interaction, cnf_interaction_vjp, cnf_stein, cnf_stein_boot, cnf_kde).  The
 // geometry of a workgroup, the column splits and a split's tiles, the block tree sum, the dispatch on the dimension and
 // the shared part of the shape checks.  Host code, constants and __device__ __forceinline__ helpers only: no kernel, so
 // no unit's kernels depend on another's.

@@ -9,7 +9,7 @@ density-vs-interpolator comparison (:178-188, 222-231) reads data files
 the exact solution computed on the device (rwpo_quadrature_terms).
 
   python -m cnf_ot_amd.solvers [--config mfc.yaml] [--epochs N] [--capture] [--save params.npz] [--fields out.npz]
-                               [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd] [--field-errors]
+                               [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd] [--ksd-test] [--field-errors]
 """
 import argparse
 import sys
@@ -1170,6 +1170,76 @@ def print_ksd(res: Dict[str, Any]) -> None:
       res["stationary"]["flow"], " ".join("{:+.4e}".format(v) for v in res["stationary"]["particles"])))
 
 
+KSD_TEST_ROWS = ("flow", "floor", "ensemble", "ensemble_flow", "flow_own")
+
+
+def evaluate_ksd_test(config, model: FlowModel, params: Params, n=8192, seed=0, kind="imq", h=1e-3,
+                      n_boot=255) -> Dict[str, Any]:
+  """evaluate_ksd's sets against evaluate_ksd's scores, each value of KSD^2_U read as a p-value: the wild-bootstrap test
+  (utils.ksd_bootstrap_test, n_boot vectors of fair signs, utils.rademacher_signs(n, n_boot, seed): the same sign vectors
+  for every set and time).  The samples, the scores and the bandwidths are evaluate_ksd's at the same arguments.  Lists
+  with one entry per (t, target, scale) of applications.known_densities:
+    times
+    flow, p_flow            n flow samples against the closed-form score: the value and its p-value
+    floor, p_floor          n exact draws of the target against it: the null holds, so these p-values are uniform --
+                            the printed calibration check
+  for fp also (None for the other types), from the n particles of applications.fp_reference_particles:
+    ensemble, p_ensemble            the ensemble against the closed-form score
+    ensemble_flow, p_ensemble_flow  the ensemble against the flow's exact score at the ensemble's points
+    flow_own, p_flow_own            the flow's samples against the flow's own score: the null holds here as well
+  and kind, n, n_boot.  evaluate_ksd's `stationary` row is left out: the particles of an interacting ensemble are
+  exchangeable, not independent, and the i.i.d. wild bootstrap does not apply to them (a dependent bootstrap is out of
+  scope).  ValueError, before any device work, for what utils.stein_boot_check_shapes refuses at n, an
+  unknown kind and an n_boot that utils.rademacher_signs refuses."""
+  n = int(n)
+  g = config["general"]
+  _type, dim = g["type"], g["dim"]
+  utils.stein_boot_check_shapes((2, n, dim))
+  utils.stein_spec(kind, [1.0])
+  signs = utils.rademacher_signs(n, n_boot, seed)
+  entries = applications.known_densities(config)
+  ts = [float(e[0]) for e in entries]
+  dev = params.flat.device
+  flow = [model.apply.sample(params, cond=t, seed=seed, sample_shape=(n,)).float() for t in ts]
+  out: Dict[str, Any] = {"times": ts, "kind": kind, "n": n, "n_boot": int(n_boot)}
+  for k in KSD_TEST_ROWS:
+    out[k], out["p_" + k] = ([], []) if _type == "fp" or k in ("flow", "floor") else (None, None)
+
+  def test(names, sets, scores, bw):
+    res = utils.ksd_bootstrap_test(torch.stack(sets), torch.stack(scores), kind, bw, signs=signs)
+    for i, k in enumerate(names):
+      out[k].append(float(res["ksd2"][i]))
+      out["p_" + k].append(float(res["p_value"][i]))
+
+  for x, (t, target, scale) in zip(flow, entries):
+    exact = target_draws(target, scale, n, seed).to(dev)
+    bw = utils.median_bandwidths(exact)[:utils.STEIN_MAX_TERMS]
+    test(("flow", "floor"), [x, exact], [target.score(x, scale), target.score(exact, scale)], bw)
+  if _type != "fp":
+    return out
+  f = config["fp"]
+  T, a, sigma, sub = float(f["T"]), f["a"], f["sigma"], f["velocity_field_type"]
+  pos = applications.fp_reference_particles(dim, T, a, sigma, sub, ts, n, h, seed, positions=True)["pos"].float()
+  for i, (x, (t, target, scale)) in enumerate(zip(flow, entries)):
+    bw = utils.median_bandwidths(pos[i])[:utils.STEIN_MAX_TERMS]
+    test(("ensemble",), [pos[i]], [target.score(pos[i], scale)], bw)
+    test(("ensemble_flow", "flow_own"), [pos[i], x], [model.apply.score(params, pos[i].contiguous(), cond=t),
+                                                      model.apply.score(params, x.contiguous(), cond=t)], bw)
+  return out
+
+
+def print_ksd_test(res: Dict[str, Any]) -> None:
+  """evaluate_ksd_test's table, one line per time: every value with its p-value"""
+  fp = res["ensemble"] is not None
+  print("wild-bootstrap test of KSD^2_U ({} kernel, {} points per set, {} sign vectors), value (p):  t | flow against the "
+        "closed-form score | exact draws against it (uniform p: the calibration){}".format(
+          res["kind"], res["n"], res["n_boot"], " | ensemble against it | ensemble against the flow's score | flow "
+          "against its own score" if fp else ""))
+  for i, t in enumerate(res["times"]):
+    print("  {:.4f}".format(t) + "".join(" | {:+.4e} ({:.4f})".format(res[k][i], res["p_" + k][i])
+                                         for k in KSD_TEST_ROWS if res[k] is not None))
+
+
 # ---- the arrays behind the figures (solvers.py:309-493 through cnf_ot/utils.py:598-751) ---------------------------
 # The reference's seed points r_, domain ranges [x_min, x_max, y_min, y_max] and time arrays, restated as numbers, keyed
 # by (type, subtype or None = any, dim).  times: ("linspace", n) = linspace(0, T, n), or the literal list.
@@ -1260,7 +1330,7 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
          interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False,
-         permutation_test: bool = False) -> Dict[str, Any]:
+         permutation_test: bool = False, ksd_test: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
@@ -1268,7 +1338,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
   print evaluate_ot_reference's lines.  sliced (fp): print evaluate_fp_sliced's table.  knn (fp): print evaluate_fp_knn's
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
   `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables.
-  field_errors (fp): print evaluate_fp_fields' table.  permutation_test (fp): print evaluate_fp_permutation's table."""
+  field_errors (fp): print evaluate_fp_fields' table.  permutation_test (fp): print evaluate_fp_permutation's table.
+  ksd_test: print evaluate_ksd_test's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -1353,6 +1424,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_mv_path(evaluate_mv_path(config, model, params))
   if ksd:
     print_ksd(evaluate_ksd(config, model, params))
+  if ksd_test:
+    print_ksd_test(evaluate_ksd_test(config, model, params))
   if field_errors:
     print_fp_fields(evaluate_fp_fields(config, model, params))
   if permutation_test:
@@ -1396,6 +1469,9 @@ def _parse(argv):
                  help="print the kernel Stein discrepancy of the flow's samples against every closed-form score of the "
                       "problem beside its floor, for fp the particle ensemble against that score and against the flow's "
                       "exact score, and with an interaction in the ou drift the stationarity residual at T")
+  p.add_argument("--ksd-test", action="store_true",
+                 help="print the same discrepancies (without the stationarity residual) with their wild-bootstrap p-values "
+                      "(255 sign vectors): the exact draws' p-values are uniform, the calibration check")
   p.add_argument("--field-errors", action="store_true",
                  help="print the errors of the flow's log-density, score and velocity, in the full dimension, against the "
                       "kernel density estimate of the particle reference, each beside its Monte-Carlo floor (fp)")
@@ -1411,4 +1487,4 @@ if __name__ == "__main__":
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
        sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd,
-       field_errors=args.field_errors, permutation_test=args.permutation_test)
+       field_errors=args.field_errors, permutation_test=args.permutation_test, ksd_test=args.ksd_test)

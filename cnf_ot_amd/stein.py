@@ -2,8 +2,9 @@
 compares an ensemble, or the flow's samples, with a target that has no samples and no normalised density: the particle
 references against a closed-form or the flow's exact score, a stationarity residual, a Gibbs law known up to its
 constant.  One fused call over all sets (cnf_stein); composed in torch the same pair sum materialises
-several N x N matrices and their backward.  What surrounds a call is `two_sample`'s.  `utils` re-exports the public
-names.
+several N x N matrices and their backward.  Its wild-bootstrap test (cnf_stein_boot) reads the value
+as a p-value: the statistic under up to 1 024 Rademacher sign vectors in one pass over the pairs, on the matrix cores.
+What surrounds a call is `two_sample`'s.  `utils` re-exports the public names.
 """
 import math
 
@@ -13,10 +14,11 @@ import torch
 from . import _capi
 from .flows import _OnDevice, _stream_ptr
 from .two_sample import (_F32_MIN, _fits, _floats32, _per_64_sets, _ptr, _sets, _stage, _unstack, _workspace,
-                         _workspace_bytes, median_bandwidths)
+                         _workspace_bytes, median_bandwidths, pack_labels, permutation_p_value)
 
 STEIN_KINDS = tuple(_capi.STEIN_KINDS)
 STEIN_MAX_TERMS, STEIN_MAX_POINTS = _capi.STEIN_MAX_TERMS, 1 << 20
+STEIN_BOOT_MIN_VECTORS, STEIN_BOOT_MAX_VECTORS = 32, 1024
 
 
 def _pow(b, e):
@@ -133,3 +135,90 @@ def ksd(x, score, kind="imq", bandwidths=None, beta=-0.5, weights=None, want_gra
   return {"ksd2": sums[:, 0] / (N * (N - 1.0)), "ksd2_v": (sums[:, 0] + sums[:, 1]) / (float(N) * N), "sums": sums,
           "rows": _unstack(rows, one), "grad_x": _unstack(gx, one), "grad_score": _unstack(gs, one),
           "direction": _unstack(direction, one), "bandwidths": [float(spec.bw[i]) for i in range(spec.n_terms)]}
+
+
+# ---- the wild-bootstrap test of the Stein discrepancy ------------------------------------------------------------------
+# With H the zero-diagonal Stein kernel matrix and e a vector of fair signs, e' H e / (N (N - 1)) has, under x ~ p, the
+# law of KSD^2_U itself (the U-statistic is degenerate there): its quantiles are the test's.  One fused pass forms every
+# pair value once for all sign vectors (cnf_stein_boot).
+
+def rademacher_signs(N, n_boot, seed=0):
+  """The sign words of a wild-bootstrap test of N points, an int32 CPU tensor [N, (n_boot + 1) / 32]: bit b of word w of
+  point j is set where e_j = +1 under sign vector 32 w + b.  Vector 0 is all +1 (the observed statistic); vectors
+  1..n_boot are fair bits drawn by numpy's default_rng(seed) -- a fixed function of (N, n_boot, seed).  ValueError unless
+  n_boot + 1 is a multiple of 32 within 32..1024 and N >= 1."""
+  N, P = int(N), int(n_boot) + 1
+  if P % 32 or not STEIN_BOOT_MIN_VECTORS <= P <= STEIN_BOOT_MAX_VECTORS:
+    raise ValueError(f"rademacher_signs: n_boot + 1 must be a multiple of 32 within {STEIN_BOOT_MIN_VECTORS}.."
+                     f"{STEIN_BOOT_MAX_VECTORS}, not {P}")
+  if N < 1:
+    raise ValueError(f"rademacher_signs: needs N >= 1, not {N}")
+  plus = np.random.default_rng(int(seed)).integers(0, 2, size=(N, P), dtype=np.uint8).astype(bool)
+  plus[:, 0] = True
+  return pack_labels(plus)
+
+
+def stein_boot_check_shapes(x_shape, score_shape=None, signs_shape=None):
+  """ValueError for what cnf_stein_boot refuses: ([S, N, D], [S, N, D], [N, W]) with S in 1..64, N in 2..2^20, D in 1..14,
+  a score of the points' shape and W = P / 32 words in 1..32."""
+  stein_check_shapes(x_shape, score_shape)
+  N = x_shape[1]
+  if signs_shape is not None and (len(signs_shape) != 2 or signs_shape[0] != N
+                                  or not 1 <= signs_shape[1] <= STEIN_BOOT_MAX_VECTORS // 32):
+    raise ValueError(f"ksd_bootstrap: signs must be [{N}, P / 32] words with P in {STEIN_BOOT_MIN_VECTORS}.."
+                     f"{STEIN_BOOT_MAX_VECTORS}, not {tuple(signs_shape)}")
+
+
+def ksd_bootstrap_test(x, score, kind="imq", bandwidths=None, beta=-0.5, weights=None, n_boot=255, seed=0,
+                       signs=None) -> dict:
+  """The wild-bootstrap goodness-of-fit test of the point sets x [N, D] or [S, N, D] against the law whose score at those
+  points is `score` (x's shape; kernel as `ksd`, bandwidths=None: median_bandwidths(x), first 4): KSD^2_U under n_boot
+  vectors of fair signs, ONE cnf_stein_boot call per 64 sets.  signs: the sign words [N, P / 32] (None:
+  rademacher_signs(N, n_boot, seed)); with signs given, n_boot = P - 1 and vector 0 is taken as the observed statistic
+  (all +1).  The same sign vectors serve all sets.  The points are taken as independent draws: for exchangeable or
+  correlated points (interacting particles, a chain) this bootstrap does not apply.  float32 on the device.  Returns a
+  dict:
+    ksd2 [S]           sign vector 0's statistic e' H e / (N (N - 1)) (float64): KSD^2_U
+    null [S, n_boot]   the statistic under vectors 1..n_boot
+    p_value [S]        (1 + #{null >= ksd2}) / (1 + n_boot)
+    ksd2_v, null_v, p_value_v   the same for the V-statistic (e' H e + sum_i k_p(x_i, x_i)) / N^2
+    raw                {"q": [S, P], "t": [S], "diag": [S]}: e' H e, 1' H 1 and the diagonal sum, from which every value
+                       can be audited
+    bandwidths         the list used
+  Evaluation only: no gradient.  Two calls give the same bits.  ValueError before any device work for what the C ABI
+  refuses and for x, score and signs that do not fit together."""
+  x3, s3 = _sets("ksd_bootstrap", x, "x"), _sets("ksd_bootstrap", score, "score")
+  S, N, D = x3.shape
+  one_call = (min(S, _capi.MMD_MAX_SETS), N, D)    # (any S: 64 sets per call)
+  stein_boot_check_shapes(one_call, (min(s3.shape[0], _capi.MMD_MAX_SETS),) + tuple(s3.shape[1:]))
+  if s3.shape[0] != S:
+    raise ValueError(f"ksd_bootstrap: the score must have the points' shape {tuple(x3.shape)}, not {tuple(s3.shape)}")
+  if signs is None:
+    signs = rademacher_signs(N, n_boot, seed)
+  signs = signs if torch.is_tensor(signs) else torch.as_tensor(np.asarray(signs))
+  stein_boot_check_shapes(one_call, None, tuple(signs.shape))
+  if signs.dtype != torch.int32:
+    raise ValueError(f"ksd_bootstrap: signs are int32 words, not {signs.dtype}")
+  P = 32 * signs.shape[1]
+  if bandwidths is None:
+    bandwidths = median_bandwidths(x3)[:STEIN_MAX_TERMS]
+  spec = stein_spec(kind, bandwidths, beta, weights)
+  dev, _, (x3, s3) = _stage(x, x3, s3)
+  words = signs.detach().to(device=dev).contiguous()
+
+  def call(xc, sc):
+    Sc = xc.shape[0]
+    ws = _workspace(dev, _workspace_bytes("cnf_stein_boot_workspace", Sc, N, D, P))
+    stats = torch.empty(Sc, P, dtype=torch.float64, device=dev)
+    raw = torch.empty(Sc * (P + 2), dtype=torch.float64, device=dev)
+    with _OnDevice(dev):
+      _capi.check(_capi.lib().cnf_stein_boot(_capi.ctypes.byref(spec), Sc, xc.data_ptr(), sc.data_ptr(), N, D,
+                                             words.data_ptr(), P, stats.data_ptr(), raw.data_ptr(), ws.data_ptr(),
+                                             ws.numel() * 8, _stream_ptr(dev)), "cnf_stein_boot")
+    return stats, raw[:Sc * P].view(Sc, P), raw[Sc * P:Sc * (P + 1)], raw[Sc * (P + 1):]
+
+  stats, q, t, diag = _per_64_sets(call, x3, s3)
+  stats_v = (q + diag[:, None]) / (float(N) * N)
+  return {"ksd2": stats[:, 0], "null": stats[:, 1:], "p_value": permutation_p_value(stats[:, 0], stats[:, 1:]),
+          "ksd2_v": stats_v[:, 0], "null_v": stats_v[:, 1:], "p_value_v": permutation_p_value(stats_v[:, 0], stats_v[:, 1:]),
+          "raw": {"q": q, "t": t, "diag": diag}, "bandwidths": [float(spec.bw[i]) for i in range(spec.n_terms)]}

@@ -5,7 +5,7 @@
   - the arrays under its figures (:598-798): density, velocity and score fields, trajectories, and `point_stats`;
   - the distances between two point clouds (mmd2, mmd_permutation_test, sinkhorn, sliced_wasserstein and their helpers), which live in
     `two_sample` and are re-exported here, as are the interaction energy of one cloud (`interaction`) and the kernel
-    Stein discrepancy of a cloud against a score (`stein`) and the kernel density estimate of a cloud with its score
+    Stein discrepancy of a cloud against a score and its wild-bootstrap test (`stein`) and the kernel density estimate of a cloud with its score
     (`kde`).
 """
 from typing import Optional
@@ -29,7 +29,8 @@ from .interaction import (  # noqa: F401
     INTERACTION_KINDS, INTERACTION_MAX_TERMS, INTERACTION_MAX_POINTS, interaction_spec, interaction_check_shapes,
     interaction_energy, interaction_field, interaction_force_vjp)
 from .stein import (  # noqa: F401
-    STEIN_KINDS, STEIN_MAX_TERMS, STEIN_MAX_POINTS, stein_spec, stein_check_shapes, ksd)
+    STEIN_KINDS, STEIN_MAX_TERMS, STEIN_MAX_POINTS, stein_spec, stein_check_shapes, ksd,
+    STEIN_BOOT_MIN_VECTORS, STEIN_BOOT_MAX_VECTORS, rademacher_signs, stein_boot_check_shapes, ksd_bootstrap_test)
 from .kde import (  # noqa: F401
     KDE_MAX_BW, KDE_MAX_POINTS, kde_spec, kde_check_shapes, kde_bandwidths, kde)
 

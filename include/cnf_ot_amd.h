@@ -1088,6 +1088,38 @@ int cnf_stein(const CnfSteinSpec *spec, int32_t S, const float *x, const float *
               double *sums, float *rows, float *grad_x, float *grad_s, void *workspace, int64_t workspace_bytes,
               void *stream);
 
+/* ---- the wild bootstrap of the kernel Stein discrepancy: P Rademacher sign vectors at once --------------------------
+ * What turns a value of KSD^2_U into a p-value.  With H the Stein kernel matrix of set s with its diagonal zeroed
+ * (cnf_stein's k_p, in the same float32 operations and order, without the gradient's phi''') and a sign vector e in
+ * {+1, -1}^N, the wild bootstrap of the degenerate U-statistic is
+ *   B(e) = e' H e / (N (N - 1)),   KSD^2_U = B(1).
+ * For P sign vectors C = H E' is a matrix product whose left factor is generated on the fly and never stored: each
+ * Stein kernel value is formed once and used P times, on the exact-fp32 MFMA.
+ * signs [N, P / 32] (device, uint32, shared by all S sets): bit b of word w of point j is sign vector 32 w + b, set
+ * where e_j = +1 under that vector.
+ * cnf_stein_boot writes stats [S, P] (device, double, overwritten): e' H e / (N (N - 1)) per set and sign vector; and,
+ * with raw (device, double, optional, overwritten), q [S, P] = e' H e, then t [S] = 1' H 1, then the diagonal sum [S] =
+ * sum_i k_p(x_i, x_i) (cnf_stein's sums[1]) -- what a rank, a call or the V-statistic (q + diagonal) / N^2 is audited
+ * from.  t is computed by the call, not taken from the signs.
+ * No float32 accumulator holds more than 64 pair terms before it is added into a double; the column splits are
+ * cnf_stein_boot_splits(S, N, D) (a function of the sizes alone); the partial sums are added in a fixed ascending
+ * order: no atomics, two calls are bit-identical, the result does not depend on what the workspace held, a sign
+ * vector's q does not depend on P, on its position among the vectors or on the other vectors, and q is unchanged bit
+ * for bit when a vector is complemented.  The spec is a HOST argument.  cnf_stein_boot_workspace: the bytes of device
+ * workspace (8-byte aligned) such a call needs; no HIP call.  cnf_stein_boot neither allocates nor synchronises (legal
+ * inside a stream capture).  Non-finite inputs propagate to the outputs of their own set.
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: a NULL spec, x, score, signs, stats or workspace; S outside
+ * 1..64; N outside 2..2^20; D outside 1..14; P not a multiple of 32 or outside 32..1024; what cnf_stein refuses in a
+ * spec; a workspace smaller than cnf_stein_boot_workspace says.
+ * Out of scope: H's symmetry, other weights than Rademacher signs, dependent or block bootstraps, signs drawn on the
+ * device or per set, gradients, more than one rank, N > 2^20. */
+int cnf_stein_boot_workspace(int32_t S, int64_t N, int32_t D, int32_t P, int64_t *bytes);
+/* the column splits of a set at these sizes (>= 1), or CNF_ERR_INVALID */
+int cnf_stein_boot_splits(int32_t S, int64_t N, int32_t D);
+int cnf_stein_boot(const CnfSteinSpec *spec, int32_t S, const float *x, const float *score, int64_t N, int32_t D,
+                   const uint32_t *signs, int32_t P, double *stats, double *raw,
+                   void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- a Gaussian kernel density estimate of point sets: log-density and score ----------------------------------------
  * What turns an ensemble into FIELDS at given points in the full dimension.  For S sets of sources x [S, N, D], queries
  * q [S, Q, D] and bandwidths h_b, b < n_bw <= 4, per (set, b, query i):
