@@ -268,6 +268,12 @@ SYMBOLS = {
                                       ctypes.c_float, ctypes.c_double, ctypes.c_double, _I64, ctypes.c_double, _U64, _I64,
                                       ctypes.c_int32, _I64, _P, ctypes.POINTER(_I64), ctypes.c_int32,
                                       ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _P, _I64, _P]),
+  # the particle reference of the rwpo problems (centre, times: host arrays): log_h, ess [N], mean_T [N, D], sel [N]
+  # int32, and cnf_fp_particles' pos, sums and hist of the bridge's positions, each or NULL
+  "cnf_rwpo_particles_workspace": (ctypes.c_int, [_I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_rwpo_particles": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float] + [ctypes.c_double] * 5
+                         + [ctypes.POINTER(ctypes.c_double), _I64, _U64, _I64, _I64, _P, ctypes.POINTER(ctypes.c_double),
+                            ctypes.c_int32, ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
   "cnf_strerror": (ctypes.c_char_p, [ctypes.c_int]),
   "cnf_build_arch": (ctypes.c_char_p, []),
   "cnf_config_supported": (ctypes.c_int, [_CFG]),

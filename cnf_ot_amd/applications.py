@@ -976,6 +976,134 @@ def fp_reference_particles(dim, T, a, sigma, subtype, times, n_particles=1 << 20
   return out
 
 
+# ---- the particle reference of the rwpo problems --------------------------------------------------------------------
+# The Hopf-Cole formula read as an expectation (the reference's cost_rwpo, solvers.py:190-220, is its nested Monte-Carlo
+# at dim 2): with eps = 1 / beta the optimal path measure is Brownian motion of variance 2 eps t from rho0, reweighted by
+# exp(-g(X_T) / (2 eps)) / h(X_0).  cnf_rwpo_particles (include/cnf_ot_amd.h) draws the inner ensembles
+# from a two-centre Gaussian proposal, one wave per outer particle, and the Brownian bridges to the selected endpoints.
+RWPO_MAX_INNER = 1 << 20
+
+
+def rwpo_proposal(dim, T, beta, a, subtype) -> dict:
+  """The inner proposal z = shrink y +- centre + sqrt(prop_var) xi of rwpo_reference_particles for a potential:
+  quadratic: the exact posterior of X_T given y (every weight equal); double_well: the Gaussians that the Brownian
+  kernel and the well's curvature beta a^2 dim at +-a 1 give, P = beta a^2 dim + beta / (2 T) their precision;
+  obstacle: the plain Brownian kernel.  dict(shrink, prop_var, centre: [dim] float64 or None)."""
+  if subtype not in _capi.POTENTIALS:
+    raise ValueError(f"unknown potential {subtype!r}")
+  dim, T, beta, a = int(dim), float(T), float(beta), float(a)
+  if subtype == "quadratic":
+    return {"shrink": 1.0 / (1.0 + T), "prop_var": 2.0 * T / (beta * (1.0 + T)), "centre": None}
+  if subtype == "double_well":
+    curv = beta * a * a * dim
+    P = curv + beta / (2.0 * T)
+    return {"shrink": (beta / (2.0 * T)) / P, "prop_var": 1.0 / P, "centre": np.full(dim, a * curv / P)}
+  return {"shrink": 1.0, "prop_var": 2.0 * T / beta, "centre": None}
+
+
+def rwpo_selection_uniforms(n_total, seed) -> np.ndarray:
+  """The float64 uniforms in [0, 1) that pick every outer particle's endpoint among its inner draws, particle p's at
+  index p: a host Philox generator keyed by `seed`.  They are an input of cnf_rwpo_particles, so that a result is a
+  function of its arguments."""
+  u64, off = seed_to_u64(seed)
+  return np.random.Generator(np.random.Philox(key=u64)).random(int(off) + int(n_total))[int(off):]
+
+
+def rwpo_reference_particles(dim, T, beta, a, subtype, times, n_particles=65536, n_inner=4096, seed=0, var0=None,
+                             proposal=None, grid=None, first=0, want_pos=False):
+  """The rwpo problem's optimal value, endpoint law and path density at any dimension from one cnf_rwpo_particles call:
+  n_particles outer particles y ~ N(0, var0 I) (var0 = None: rwpo_initial_variance(T, beta)), n_inner weighted draws of
+  X_T each from `proposal` (None: rwpo_proposal's), one endpoint per particle selected by rwpo_selection_uniforms and a
+  Brownian bridge through `times` (ascending, in [0, T], at most 64).  Global particle first + i depends on (seed,
+  first + i) alone.  Returns a dict of device tensors: stats_from_sums' keys of the bridge's positions (count, bad [S];
+  mean [S, D]; cov [S, D, D]; sums; with `grid` -- a utils.field_grid or (domain_range, n) over axes (0, 1) -- hist and
+  density), times [S], and
+    log_h, ess [N], mean_T [N, D], sel [N]   log h(y_i), the effective sample size, E[X_T | y_i], the selected draw
+    y [N, D], drift0 = (mean_T - y) / T      the outer particles (from the stream) and the optimal control at time 0
+    true_val = -(2 / beta) mean log_h        the optimal energy; true_val_se: its standard error from the sample
+    bias_est = (2 / beta) mean((1 / ess - 1 / K) / 2)   the first-order self-normalisation bias: true_val lies above the
+                                             limit by it; true_val_corrected = true_val - bias_est
+  (0-dim tensors), and with want_pos=True pos [S, N, D].  ValueError before any device work for an unknown potential,
+  sizes or times out of range; the C ABI's other refusals raise CnfError."""
+  if subtype not in _capi.POTENTIALS:
+    raise ValueError(f"unknown potential {subtype!r}")
+  dim, N, K, first = int(dim), int(n_particles), int(n_inner), int(first)
+  ts = np.ascontiguousarray(np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64).reshape(-1))
+  S = ts.size
+  if not 1 <= dim <= 14 or N < 1 or not 1 <= K <= RWPO_MAX_INNER or first < 0:
+    raise ValueError(f"rwpo_reference_particles: needs 1 <= dim <= 14, n_particles >= 1, 1 <= n_inner <= 2^20, first >= 0")
+  if not 1 <= S <= FP_MAX_SNAPSHOTS or not np.isfinite(ts).all() or ts[0] < 0.0 or ts[-1] > T or (np.diff(ts) <= 0).any():
+    raise ValueError(f"rwpo_reference_particles: between 1 and {FP_MAX_SNAPSHOTS} ascending times in [0, T]: {ts.tolist()}")
+  var0 = rwpo_initial_variance(T, beta) if var0 is None else float(var0)
+  prop = rwpo_proposal(dim, T, beta, a, subtype) if proposal is None else proposal
+  centre = prop.get("centre")
+  centre = None if centre is None else np.ascontiguousarray(np.broadcast_to(np.asarray(centre, dtype=np.float64), (dim,)))
+  g = stats_grid(grid, (0, 1), dim)
+  dev = torch.device("cuda", torch.cuda.current_device())
+  u64, off = seed_to_u64(seed)
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_rwpo_particles_workspace(N, dim, S, C.byref(nbytes)), "cnf_rwpo_particles_workspace")
+  f64 = dict(dtype=torch.float64, device=dev)
+  ws = torch.empty(-(-nbytes.value // 8), **f64)
+  u = torch.as_tensor(rwpo_selection_uniforms(first + N, seed)[first:]).to(dev)
+  out = {"log_h": torch.empty(N, **f64), "ess": torch.empty(N, **f64), "mean_T": torch.empty(N, dim, **f64),
+         "sel": torch.empty(N, dtype=torch.int32, device=dev)}
+  sums = torch.empty(S, 2 + dim + dim * dim, **f64)
+  hist = None if g is None else torch.empty(S, g.ny, g.nx, dtype=torch.int32, device=dev)
+  pos = torch.empty(S, N, dim, **f64) if want_pos else None
+  dptr = C.POINTER(C.c_double)
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_rwpo_particles(_capi.POTENTIALS[subtype], dim, float(a), float(T), float(beta), var0,
+                                       float(prop["shrink"]), float(prop["prop_var"]),
+                                       None if centre is None else centre.ctypes.data_as(dptr), K, u64, off + first, N,
+                                       u.data_ptr(), ts.ctypes.data_as(dptr), S, None if g is None else C.byref(g),
+                                       out["log_h"].data_ptr(), out["ess"].data_ptr(), out["mean_T"].data_ptr(),
+                                       out["sel"].data_ptr(), None if pos is None else pos.data_ptr(), sums.data_ptr(),
+                                       None if hist is None else hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                       _stream_ptr(dev)), "cnf_rwpo_particles")
+    # y again from the stream: the first dim elements of each particle's R
+    R = rwpo_stream_stride(dim, K, S)
+    head = -(-dim // 4) * 4
+    y = torch.empty(N, head, dtype=torch.float32, device=dev)
+    if R <= 4096:                             # whole strides, a block of particles at a time
+      block = max(1, (1 << 26) // R)
+      z = torch.empty(min(N, block) * R, dtype=torch.float32, device=dev)
+      for i0 in range(0, N, block):
+        n = min(block, N - i0)
+        _capi.check(lib.cnf_fill_normal(u64, (off + first + i0) * R, n * R, z.data_ptr(), _stream_ptr(dev)),
+                    "cnf_fill_normal")
+        y[i0:i0 + n].copy_(z[:n * R].reshape(n, R)[:, :head])
+    else:                                     # the head of each stride alone
+      for i in range(N):
+        _capi.check(lib.cnf_fill_normal(u64, (off + first + i) * R, head, y.data_ptr() + 4 * head * i, _stream_ptr(dev)),
+                    "cnf_fill_normal")
+    y = y[:, :dim]
+  out.update(stats_from_sums(sums, None if hist is None else hist.to(torch.int64), N, g, dim))
+  out["times"] = torch.as_tensor(ts, device=dev)
+  out["y"] = y.double() * math.sqrt(var0)
+  out["drift0"] = (out["mean_T"] - out["y"]) / float(T)
+  out.update(rwpo_value_of(out["log_h"], out["ess"], beta, K))
+  if want_pos:
+    out["pos"] = pos
+  return out
+
+
+def rwpo_stream_stride(dim, n_inner, n_times) -> int:
+  """R: the elements of the cnf_fill_normal stream that a particle of cnf_rwpo_particles owns"""
+  return 4 * (-(-dim // 4) + n_inner * (-(-(dim + 1) // 4)) + -(-n_times * dim // 4))
+
+
+def rwpo_value_of(log_h, ess, beta, n_inner) -> dict:
+  """true_val, true_val_se, bias_est and true_val_corrected (0-dim tensors) from the outer particles' log_h and ess"""
+  c = 2.0 / float(beta)
+  n = log_h.numel()
+  val = -c * log_h.mean()
+  se = c * (log_h.std(unbiased=True) / math.sqrt(n) if n > 1 else torch.full_like(val, float("nan")))
+  bias = c * ((1.0 / ess - 1.0 / float(n_inner)) / 2.0).mean()
+  return {"true_val": val, "true_val_se": se, "bias_est": bias, "true_val_corrected": val - bias}
+
+
 # ---- the particle reference of the interacting (McKean-Vlasov) fp problem -------------------------------------------
 # d rho / dt = -div(rho (drift - strength grad (W * rho))) + sigma lap rho is the mean-field limit of N particles that
 # feel, beside the drift and the noise, the force of the other N - 1 through the pair kernel W: cnf_mv_particles

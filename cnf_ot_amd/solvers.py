@@ -12,6 +12,7 @@ the exact solution computed on the device (rwpo_quadrature_terms).
                                [--path-errors] [--fit] [--interaction] [--mv-path] [--ksd] [--ksd-test] [--field-errors]
 """
 import argparse
+import math
 import sys
 from dataclasses import dataclass, field
 from functools import partial
@@ -408,6 +409,72 @@ def print_path_errors(res: Dict[str, Any]) -> None:
                               res["mass"])):
     print("  {:.4f} | {:.3e} | {:.3e} | {:.6f} | {:.6f}".format(*row)
           + (" | {:.3e}".format(res["score_rel_err"][i]) if score else ""))
+
+
+def rwpo_particles_domain(config):
+  """The histogram domain of evaluate_rwpo_particles: the figure's where the reference draws one (dim 2), else
+  +-3 standard deviations of the initial condition over axes (0, 1)"""
+  st = figure_settings(config)
+  if st is not None:
+    return [float(v) for v in st["domain_range"]]
+  r = config["rwpo"]
+  half = 3.0 * math.sqrt(applications.rwpo_initial_variance(r["T"], r["beta"]))
+  return [-half, half, -half, half]
+
+
+def evaluate_rwpo_particles(config, model: FlowModel, params: Params, times=None, n_particles=65536, n_inner=4096,
+                            seed=0) -> Dict[str, Any]:
+  """Where along [0, T] the flow of an rwpo configuration departs from the optimal path measure, at any dimension and
+  for every potential (ValueError for another problem type): per time of `times` (default: 5 equally spaced in [0, T]),
+  n_particles flow samples (model.apply.sample of `seed`, through utils.point_stats) against the bridges of
+  applications.rwpo_reference_particles (same count, n_inner draws each, same seed, run as its two halves), histograms
+  of FIGURE_GRID^2 cells on rwpo_particles_domain over axes (0, 1).  Lists of floats, one per time -- times, mean_err,
+  cov_rel_err, tv, tv_floor, bad, formed exactly as evaluate_fp_path forms them -- and the floats
+    true_val, true_val_se, bias_est, true_val_corrected   the optimal energy -(2 / beta) mean log h, its standard error,
+                                                          the self-normalisation bias and the value less the bias
+    ess_median, ess_min                                   the effective sample size over the outer particles (of n_inner)
+  Single process."""
+  g = config["general"]
+  if g["type"] != "rwpo":
+    raise ValueError(f"evaluate_rwpo_particles: defined for rwpo only, not {g['type']}")
+  n_particles = int(n_particles)
+  if n_particles < 2 or n_particles % 2:
+    raise ValueError(f"evaluate_rwpo_particles: n_particles must be even and >= 2 (two halves are compared), not {n_particles}")
+  r, dim = config["rwpo"], g["dim"]
+  T, beta, a, sub = r["T"], r["beta"], r["a"], r["pot_type"]
+  ts = np.linspace(0.0, float(T), 5) if times is None else utils._times_of(times)
+  S, half = len(ts), n_particles // 2
+  grid = utils.field_grid(rwpo_particles_domain(config), FIGURE_GRID, axes=(0, 1))
+  samples = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(n_particles,)) for t in ts])
+  flow = utils.point_stats(samples, grid)
+  halves = [applications.rwpo_reference_particles(dim, T, beta, a, sub, ts, half, n_inner, seed, grid=grid, first=k * half)
+            for k in (0, 1)]
+  ref = applications.stats_from_sums(halves[0]["sums"] + halves[1]["sums"], halves[0]["hist"] + halves[1]["hist"],
+                                     n_particles, applications.stats_grid(grid, None, dim), dim)
+  p, q = flow["hist"].double() / n_particles, ref["hist"].double() / n_particles
+  ha, hb = (hv["hist"].double() / half for hv in halves)
+  ess = torch.cat([hv["ess"] for hv in halves])
+  val = applications.rwpo_value_of(torch.cat([hv["log_h"] for hv in halves]), ess, beta, n_inner)
+  out = {"times": [float(t) for t in ts],
+         "mean_err": torch.linalg.norm(flow["mean"] - ref["mean"], dim=1).tolist(),
+         "cov_rel_err": (torch.linalg.norm((flow["cov"] - ref["cov"]).reshape(S, -1), dim=1)
+                         / torch.linalg.norm(ref["cov"].reshape(S, -1), dim=1)).tolist(),
+         "tv": (0.5 * (p - q).abs().sum((1, 2))).tolist(),
+         "tv_floor": (0.5 * (ha - hb).abs().sum((1, 2))).tolist(),
+         "bad": ref["bad"].tolist()}
+  out.update({k: float(v) for k, v in val.items()})
+  out.update(ess_median=float(ess.median()), ess_min=float(ess.min()))
+  return out
+
+
+def print_rwpo_particles(res: Dict[str, Any]) -> None:
+  """evaluate_rwpo_particles' lines: the value, then one line per time"""
+  print("optimal energy from the particle reference: {:.6f} +- {:.1e} | less the bias {:.1e}: {:.6f} | "
+        "ess median {:.1f} min {:.1f}".format(res["true_val"], res["true_val_se"], res["bias_est"],
+                                              res["true_val_corrected"], res["ess_median"], res["ess_min"]))
+  print("path errors against the particle reference:  t | mean err | cov rel err | tv | tv floor | bad")
+  for row in zip(res["times"], res["mean_err"], res["cov_rel_err"], res["tv"], res["tv_floor"], res["bad"]):
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.4f} | {:.4f} | {:.0f}".format(*row))
 
 
 def _fp_prelude(name, config, times, n_particles, h, min_particles, start="gaussian"):
@@ -1330,7 +1397,7 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
          interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False,
-         permutation_test: bool = False, ksd_test: bool = False) -> Dict[str, Any]:
+         permutation_test: bool = False, ksd_test: bool = False, rwpo_particles: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
@@ -1339,7 +1406,7 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
   `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables.
   field_errors (fp): print evaluate_fp_fields' table.  permutation_test (fp): print evaluate_fp_permutation's table.
-  ksd_test: print evaluate_ksd_test's table."""
+  ksd_test: print evaluate_ksd_test's table.  rwpo_particles (rwpo, any dim): print evaluate_rwpo_particles' lines."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -1359,6 +1426,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
   if mv_path and (_type != "fp" or _interaction_kind(config) == "none" or _interaction_role(config) != "drift"):
     raise ValueError("--mv-path compares an fp flow trained with the interaction in its drift (`role: drift`) with the "
                      "interacting particle reference")
+  if rwpo_particles and _type != "rwpo":
+    raise ValueError(f"--rwpo-particles compares an rwpo flow with the particle reference of its optimal path: not defined for {_type}")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -1430,6 +1499,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_fields(evaluate_fp_fields(config, model, params))
   if permutation_test:
     print_fp_permutation(evaluate_fp_permutation(config, model, params))
+  if rwpo_particles:
+    print_rwpo_particles(evaluate_rwpo_particles(config, model, params))
   return res
 
 
@@ -1479,6 +1550,10 @@ def _parse(argv):
                  help="print MMD^2 and the energy distance between the flow's samples and the particle reference with "
                       "their permutation p-values (255 relabellings), beside the same test between the reference's two "
                       "halves (fp)")
+  p.add_argument("--rwpo-particles", action="store_true",
+                 help="print the optimal energy from the particle reference of the rwpo problem, its standard error, bias "
+                      "and effective sample size, and the flow's mean, covariance and histogram errors against the "
+                      "reference's Brownian bridges along the path, beside their floor (rwpo, any dimension)")
   return p.parse_args(argv)
 
 
@@ -1487,4 +1562,5 @@ if __name__ == "__main__":
   main(load_config(args.config), epochs=args.epochs, capture=args.capture, save=args.save, fields=args.fields,
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
        sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd,
-       field_errors=args.field_errors, permutation_test=args.permutation_test, ksd_test=args.ksd_test)
+       field_errors=args.field_errors, permutation_test=args.permutation_test, ksd_test=args.ksd_test,
+       rwpo_particles=args.rwpo_particles)

@@ -1204,6 +1204,56 @@ int cnf_mv_particles(const CnfInteractionSpec *spec, double kappa, int32_t drift
                      double *pos, double *sums, uint32_t *hist, void *workspace,
                      int64_t workspace_bytes, void *stream);
 
+/* ---- a particle reference for the rwpo problems at any dimension (the reference's cost_rwpo, cnf_ot/mfc/solvers.py:
+ * 190-220, is its nested Monte-Carlo at dim 2) ---------------------------------------------------------------------------
+ * With eps = 1 / beta the optimal path measure of the rwpo problem is Brownian motion of variance 2 eps t started from
+ * rho0 = N(0, var0 I), reweighted by exp(-g(X_T) / (2 eps)) / h(X_0), h(y) = E exp(-g(y + sqrt(2 eps T) xi) / (2 eps)):
+ * the optimal energy is -2 eps E log h, X_T given X_0 = y is the weighted inner ensemble, the path between the endpoints
+ * is a Brownian bridge and the control at time 0 is (E[X_T | y] - y) / T.  Everything is float64; g is CnfPotential
+ * `subtype` with parameter `a` exactly as the loss kernels evaluate it (one definition, a widened).
+ * Outer particle i: y = sqrt(var0) z.  Inner draw k < K from the symmetric two-centre Gaussian proposal:
+ *   z_k = shrink y + sg_k m + sqrt(prop_var) xi_k,   m = centre [D] (HOST; NULL: 0), sg_k = +1 if its normal is >= 0 else -1
+ * and with s^2 = 2 T / beta
+ *   l_k = -beta g(z_k) / 2 - |z_k - y|^2 / (2 s^2) + (D / 2) log(prop_var / s^2)
+ *         - logaddexp(-|z_k - shrink y - m|^2 / (2 prop_var), -|z_k - shrink y + m|^2 / (2 prop_var)) + log 2
+ *   log_h[i] = logsumexp_k l_k - log K,  w_k = exp(l_k - lse),  ess[i] = 1 / sum w_k^2,  mean_T[i] = sum w_k z_k
+ * (shrink = 1, prop_var = s^2, no centre: the plain Brownian proposal, every l_k = -beta g(z_k) / 2).
+ * sel[i] is the smallest k whose cumulative sum of exp(l_j - max_j l_j) over j <= k, ascending, exceeds u[i] times the
+ * total (K - 1 if rounding leaves none); the endpoint is z* = z_sel.  The path runs from (0, y) through the strictly
+ * ascending times [S] (HOST, in [0, T]):
+ *   x <- x + (t - t_prev) / (T - t_prev) (z* - x) + sqrt(2 eps (t - t_prev) (T - t) / (T - t_prev)) zeta
+ * t = 0 gives y and t = T gives z*, both exactly.
+ * Normals: global particle p = first_particle + i owns R = 4 (ceil(D / 4) + K ceil((D + 1) / 4) + ceil(S D / 4))
+ * elements of the cnf_fill_normal(seed, .) stream from p R, widened exactly: D for y (padded to a block); per draw
+ * xi_k [D], then the sign normal (padded to a block); then D per snapshot, used or not.  S enters R: pass the same S
+ * (and times) to look at the same draws.  u [N] (device, in [0, 1)) is an input: a result is a function of its arguments.
+ * Outputs (device), each optional, at least one, overwritten:
+ *   log_h, ess [N]; mean_T [N, D]             double -- without u as with it
+ *   sel [N]                                   int32, needs u
+ *   pos [S, N, D], sums [S, 2 + D + D D], hist [S, ny, nx]: cnf_fp_particles' outputs of the bridge's positions by the
+ *                                             same code, layout and non-finite rule; need u, S >= 1 and the workspace
+ * No output depends on the launch, on N or on first_particle: two calls are bit-identical, a call split at any
+ * first_particle reproduces the per-particle outputs bit for bit and the sums as cnf_fp_particles' split does.  Two
+ * launches (the inner ensembles, one wave per outer particle; the bridges, one particle per lane) and the chunk sum.
+ * `workspace` (cnf_rwpo_particles_workspace(N, D, S) bytes, 8-byte aligned; needed with pos, sums or hist) holds the
+ * chunks' partials and z* [N, D]: no allocation, no synchronisation.
+ * Checks come first.  CNF_ERR_INVALID, nothing enqueued: an unknown potential; D outside 1..14; T, beta, var0 or
+ * prop_var not positive and finite; shrink, a or a centre entry not finite; K < 1 or above 2^20; N < 1 or above 2^31;
+ * first_particle < 0 or a stream element index that would not fit in 63 bits; S outside 0..64, or 0 with pos, sums or
+ * hist; times NULL with S > 0, not ascending, not finite or outside [0, T]; sel, pos, sums or hist without u; no
+ * output at all; cnf_fp_particles' histogram refusals; a workspace that is NULL or too small when it is needed.
+ * Out of scope: the interaction cost (the measure is no longer a reweighted Brownian motion), adaptive or learned
+ * proposals, weighted output clouds, the control at interior times, more than one rank beyond first_particle. */
+int cnf_rwpo_particles_workspace(int64_t N, int32_t D, int32_t S, int64_t *bytes);
+int cnf_rwpo_particles(int32_t subtype, int32_t D, float a, double T, double beta, double var0,
+                       double shrink, double prop_var, const double *centre /* host [D] or NULL */,
+                       int64_t K, uint64_t seed, int64_t first_particle, int64_t N,
+                       const double *u /* device [N] in [0,1), or NULL */,
+                       const double *times /* host [S] */, int32_t S, const CnfFieldGrid *grid,
+                       double *log_h, double *ess, double *mean_T, int32_t *sel,
+                       double *pos, double *sums, uint32_t *hist,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+
 const char *cnf_strerror(int code);
 /* "gfx950" etc.: the offload arch this library was compiled for. */
 const char *cnf_build_arch(void);
