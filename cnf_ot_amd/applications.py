@@ -99,6 +99,8 @@ class _Ctx:
     # the HIP engine, or a stand-in that has `normal`, `loss_terms` and `loss_terms_grad` alone (the CPU tests'): the
     # one place that asks; every route below that needs more than those three reads this flag
     self.hip = isinstance(self.be, FlowEngine)
+    if _CAPTURED_BACKENDS is not None:
+      _CAPTURED_BACKENDS.append(self.be)
     self.rng = rng
     self.shard = shard if shard is not None else current_shard()
     self.grad = grad
@@ -124,9 +126,9 @@ class _Ctx:
     if n_global not in self._noise:
       start, count = shard_range(n_global, self.shard)
       if self.shard.world == 1:      # one rank: a smaller draw is the first rows of a larger one already made
-        for n_have, (z, _, _) in self._noise.items():
+        for n_have, v in self._noise.items():      # (the ("source", ...) entries hold one tensor, not a triple)
           if isinstance(n_have, int) and n_have >= n_global:
-            self._noise[n_global] = (z[:n_global], 0, n_global)
+            self._noise[n_global] = (v[0][:n_global], 0, n_global)
             return self._noise[n_global]
       self._noise[n_global] = (self.be.normal(self.rng, count, first_sample=start), start, count)
     return self._noise[n_global]
@@ -285,6 +287,9 @@ OVERLAP_ALLREDUCE = True
 
 
 _WEIGHTS = {}
+# A list while solvers.CapturedUpdate records its graph: the backends of the loss evaluations made meanwhile (_Ctx), whose
+# cached tensors the recorded kernels read by address
+_CAPTURED_BACKENDS = None
 
 
 # ---- local partial sums of each term ----------------------------------------

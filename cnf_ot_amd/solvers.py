@@ -170,7 +170,23 @@ class CapturedUpdate:
   Same call surface as the eager update: (params, rng, _lambda, opt_state) -> (loss, params, opt_state), with
   `params` / `opt_state` updated in place and `loss` a 0-dim device tensor that the NEXT call overwrites.  The
   graph holds the addresses of `params.flat` and of the optimiser state and the value of `_lambda`: call it with the
-  same objects (checked).  `replay=False` runs the very same body eagerly (what the graph is compared with)."""
+  same objects (checked).  `replay=False` runs the very same body eagerly (what the graph is compared with).
+
+  The step count of Adam's bias correction continues the optimiser state it is first called with (`opt_state.step`,
+  written to the device state once, before the warm-up), and every later call must find `opt_state.step` where this
+  object left it: ValueError for a state that was stepped elsewhere in between.
+
+  The recorded kernels read, by raw address, tensors that were NOT allocated inside the capture and that their owners
+  may drop: the uploads of host condition lists ([0], [T]) in the engine's `_cond_cache` (cleared at 32 keys), the
+  weight vectors of `applications._WEIGHTS` (cleared at 64 keys) and the engine's `_kp_work` (replaced when a larger
+  call arrives).  The object keeps a reference to each of them from the capture on (`_held`), so eager work on the
+  same engine between two replays cannot free what the graph reads.  Everything else the body reads is either
+  allocated inside the capture (the graph's own pool: draws, time batch, sums, gradient), owned by an object this one
+  holds (the device state of `rng`; the model's tables, slabs and statistics, through the loss function), the
+  caller's (`params.flat`, the moments: checked by address on every call), or in a cache that is never emptied
+  (`applications._CHOL_ROWS`, `_CENTERS_DEV`).  After every replay the engine holds the parameters from BEFORE that
+  step's Adam update (the graph loads them first): `mark_updated` follows each replay, so `model.apply.*` reloads even
+  with `assume_unchanged_params`."""
 
   WARMUP = 2       # eager steps before the capture: allocations (gradient slabs, cached weight vectors) happen there
 
@@ -178,6 +194,8 @@ class CapturedUpdate:
     self.vg = applications.value_and_grad(loss_fn)
     self.opt, self.B, self.replay = optimizer, batch_size, replay
     self.rng, self.graph, self.loss, self._key, self._calls = None, None, None, None, 0
+    self._step = None       # opt_state.step as the next call must find it
+    self._held = []         # what the graph reads and did not allocate (class docstring)
     # The warm-up steps run on the stream the graph is captured on: the engine's table workspaces are reserved PER
     # STREAM and cannot grow during a capture (FlowEngine.reserve), so a step warmed up on the caller's stream and
     # captured on torch's side stream found no tables there and recorded the MLP kernels -- correct, and for a
@@ -200,9 +218,15 @@ class CapturedUpdate:
         # (the loss's all-reduce would be recorded into the graph: RCCL can, gloo cannot, and neither has been run here)
         raise NotImplementedError("CapturedUpdate: single rank only -- use the eager update under torch.distributed")
       self.rng = DeviceRng(params.flat.device)
+      # Adam's bias corrections read the count from the device state: it continues the optimiser state handed over
+      self.rng.state[:1].copy_(torch.tensor([int(opt_state.step)], dtype=torch.int64))
+      self._step = int(opt_state.step)
     key = (params.flat.data_ptr(), opt_state.mu.data_ptr(), opt_state.nu.data_ptr(), float(_lambda))
     if self._key is not None and key != self._key:
       raise ValueError("CapturedUpdate was captured for other parameter / optimiser tensors or another _lambda")
+    if opt_state.step != self._step:
+      raise ValueError(f"CapturedUpdate counts step {self._step} on the device, the optimiser state is at step "
+                       f"{opt_state.step}: it was stepped elsewhere in between")
     self._key = key
     self.rng.set_key(rng)
     self._calls += 1
@@ -221,16 +245,29 @@ class CapturedUpdate:
       torch.cuda.synchronize(params.flat.device)
       graph = torch.cuda.CUDAGraph()
       step0 = opt_state.step
-      with torch.cuda.graph(graph, stream=self._stream):
-        self.loss = self._body(params, _lambda, opt_state)
+      applications._CAPTURED_BACKENDS = used = []
+      try:
+        with torch.cuda.graph(graph, stream=self._stream):
+          self.loss = self._body(params, _lambda, opt_state)
+      finally:
+        applications._CAPTURED_BACKENDS = None
       opt_state.step = step0            # (the capture only recorded the step)
+      # what the recorded kernels read and the capture did not allocate: kept from here on (class docstring)
+      self._held = list(applications._WEIGHTS.values())
+      for be in used:
+        self._held += list(getattr(be, "_cond_cache", {}).values()) + [getattr(be, "_kp_work", None)]
       self.graph = graph
-      graph.replay()
-      opt_state.step += 1
+      self._replay(params, opt_state)
     else:
-      self.graph.replay()
-      opt_state.step += 1
+      self._replay(params, opt_state)
+    self._step = opt_state.step
     return self.loss, params, opt_state
+
+  def _replay(self, params, opt_state):
+    self.graph.replay()
+    opt_state.step += 1
+    # the graph's Adam wrote params.flat after the graph's own load of it: engines must re-prepare (FlowEngine.load)
+    mark_updated(params.flat)
 
 
 def make_update(loss_fn: Callable, optimizer: Adam, batch_size: int, capture: bool = False) -> Callable:

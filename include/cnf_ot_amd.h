@@ -321,7 +321,13 @@ int cnf_loss_terms_seeded(CnfModel *m, const CnfLossSpec *spec, uint64_t seed,
  * hidden layers, 5 bins; dim <= 14 -- the first layer's inputs + bias row are 16 MFMA rows, and the tile's working set
  * must fit one CU's LDS): cnf_grad_supported() tells.  A model's gradient
  * slabs are shared state: do not run two gradient calls of the same model
- * concurrently on different streams.
+ * concurrently on different streams.  More exactly: the gradient entry points of ONE CnfModel (cnf_loss_terms_grad[_multi],
+ * cnf_pass_vjp, cnf_neg_logprob_vjp, cnf_kinetic_potential_vjp, cnf_logprob_fd_vjp, cnf_score_fd_vjp) must be ORDERED
+ * on one stream, or across streams by events: the adjoint maximum, the per-piece statistics and the slabs exist once
+ * per model, not once per stream (only the table workspaces of cnf_model_reserve are per stream), and nothing in the
+ * library orders two such calls.  A step that is warmed up and captured on a side stream (solvers.CapturedUpdate)
+ * relies on its wait_stream pairs around every warm-up step, and on the capture's own fork and join, for that order
+ * against the caller's stream.
  *
  * cnf_grad_enable allocates the per-wave gradient slabs (the only allocation;
  * call once, outside any graph capture; max_blocks <= 0: a default).

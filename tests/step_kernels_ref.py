@@ -158,6 +158,38 @@ def adam_ref(p, g, mu, nu, lr, b1, b2, eps, step):
   return p - lr * (m / bc1) / (np.sqrt(v / bc2) + eps), m, v
 
 
+def adam_bounds(p, g, mu, nu, lr, b1, b2, eps, step):
+  """adam_ref's (p', mu', nu') and the float32 rounding bounds (bound_p, bound_mu, bound_nu) a kernel's results are held
+  to, with EPS = 2^-24 the relative error of one float32 rounding.
+  mu' = b1 mu + (1 - b1) g: two products and a sum (1 - b is exact in float32 for b in [1/2, 1)):
+  |d mu'| <= 3 EPS (|b1 mu| + |(1 - b1) g|); nu' has one more product and only non-negative terms: |d nu'| <= 4 EPS nu'.
+  The update U = lr (mu' / c1) / (sqrt(nu' / c2) + eps), c_i = 1 - b_i^t: powf is good to an ulp of b^t, at most
+  2^-23 b^t, so c_i carries rho_i = 2^-23 b_i^t / (1 - b_i^t) relative (the cancellation of 1 - b^t).  sqrt halves nu''s
+  4 EPS, rho_2 and the quotient's EPS and adds its own; the sum with eps, mu' / c1, the product with lr and the last
+  quotient round once each:
+      |dU| <= lr |d mu'| / (c1 (sqrt(nu' / c2) + eps)) + |U| (rho_1 + rho_2 / 2 + 8 EPS),
+  and the new parameter rounds once more: |dp| <= |dU| + EPS max(|p|, |p'|) (half an ulp).  mu' = 0 makes U = 0 and
+  the parameter exact.  Also returned: (rho_1, rho_2)."""
+  EPS = 2.0 ** -24
+  want_p, want_mu, want_nu = adam_ref(p, g, mu, nu, lr, b1, b2, eps, step)
+  lrf, b1f, b2f, epsf = (float(np.float32(v)) for v in (lr, b1, b2, eps))
+  p64, g64, mu64, nu64 = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (p, g, mu, nu))
+  bound_mu = 3 * EPS * (np.abs(b1f * mu64) + np.abs((1 - b1f) * g64))
+  bound_nu = 4 * EPS * want_nu
+  c1, c2 = 1 - b1f ** step, 1 - b2f ** step
+  rho1, rho2 = 2 * EPS * b1f ** step / c1, 2 * EPS * b2f ** step / c2
+  den = np.sqrt(want_nu / c2) + epsf
+  upd = np.abs(p64 - want_p)
+  bound_p = lrf * bound_mu / (c1 * den) + upd * (rho1 + rho2 / 2 + 8 * EPS) + EPS * np.maximum(np.abs(p64), np.abs(want_p))
+  return (want_p, want_mu, want_nu), (bound_p, bound_mu, bound_nu), (rho1, rho2)
+
+
+def worst_ratio(e, b):
+  """max e / b, a zero bound allowing no error (inf where e > 0 there)"""
+  with np.errstate(invalid="ignore", divide="ignore"):
+    return float(np.nanmax(np.where(b > 0, e / b, np.where(e > 0, np.inf, 0.0))))
+
+
 def weighted_sum_ref(v, w):
   """(math.fsum of the exact products v_i w_i, each as its rounded value and the exact remainder; sum_i |v_i w_i|)"""
   terms = []

@@ -329,18 +329,12 @@ def _adam_inputs(n, fresh, seed):
 
 
 def _adam_check(capi, dev, n, step, lr, b1, b2, device_count, fresh=False):
-  """Bounds.  mu' = b1 mu + (1 - b1) g: two products and a sum (1 - b is exact in float32 for b in [1/2, 1)):
-  |d mu'| <= 3 EPS (|b1 mu| + |(1 - b1) g|); nu' has one more product and only non-negative terms: |d nu'| <= 4 EPS nu'.
-  The update U = lr (mu' / c1) / (sqrt(nu' / c2) + eps), c_i = 1 - b_i^t: powf is good to an ulp of b^t, at most
-  2^-23 b^t, so c_i carries rho_i = 2^-23 b_i^t / (1 - b_i^t) relative (the cancellation of 1 - b^t).  sqrt halves nu''s
-  4 EPS, rho_2 and the quotient's EPS and adds its own; the sum with eps, mu' / c1, the product with lr and the last
-  quotient round once each:
-      |dU| <= lr |d mu'| / (c1 (sqrt(nu' / c2) + eps)) + |U| (rho_1 + rho_2 / 2 + 8 EPS),
-  and the new parameter rounds once more: |dp| <= |dU| + EPS max(|p|, |p'|) (half an ulp).  mu' = 0 makes U = 0 and
-  the parameter exact."""
+  """Bounds: the float32 rounding bounds of step_kernels_ref.adam_bounds, derived in its docstring (shared with
+  test_gpu_captured_step.py)."""
   lib = capi.lib()
   p, g, mu, nu = _adam_inputs(n, fresh, seed=n + step)
-  want_p, want_mu, want_nu = sk.adam_ref(p, g, mu, nu, lr, b1, b2, ADAM_EPS, step)
+  (want_p, want_mu, want_nu), (bound_p, bound_mu, bound_nu), (rho1, rho2) = sk.adam_bounds(p, g, mu, nu, lr, b1, b2,
+                                                                                         ADAM_EPS, step)
   bufs = [guarded(n, torch.float32, dev) for _ in range(4)]
   for (_, view), src in zip(bufs, (p, g, mu, nu)):
     view.copy_(torch.from_numpy(src))
@@ -366,20 +360,10 @@ def _adam_check(capi, dev, n, step, lr, b1, b2, device_count, fresh=False):
   if device_count:
     assert np.array_equal(st.cpu().numpy(), dstate("cpu", step).numpy())          # the state is read, never written
 
-  lrf, b1f, b2f, epsf = f32(lr), f32(b1), f32(b2), f32(ADAM_EPS)
-  p64, g64, mu64, nu64 = (v.astype(np.float64) for v in (p, g, mu, nu))
-  bound_mu = 3 * EPS * (np.abs(b1f * mu64) + np.abs((1 - b1f) * g64))
-  bound_nu = 4 * EPS * want_nu
-  c1, c2 = 1 - b1f ** step, 1 - b2f ** step
-  rho1, rho2 = 2 * EPS * b1f ** step / c1, 2 * EPS * b2f ** step / c2
-  den = np.sqrt(want_nu / c2) + epsf
+  p64 = p.astype(np.float64)
   upd = np.abs(p64 - want_p)
-  bound_p = lrf * bound_mu / (c1 * den) + upd * (rho1 + rho2 / 2 + 8 * EPS) + EPS * np.maximum(np.abs(p64), np.abs(want_p))
   e_mu, e_nu, e_p = np.abs(got_mu - want_mu), np.abs(got_nu - want_nu), np.abs(got_p - want_p)
-
-  def worst(e, b):
-    with np.errstate(invalid="ignore", divide="ignore"):
-      return float(np.nanmax(np.where(b > 0, e / b, np.where(e > 0, np.inf, 0.0))))
+  worst = sk.worst_ratio
 
   upd_rel = float((np.abs((got_p.astype(np.float64) - p64) - (want_p - p64))[upd > 0] / upd[upd > 0]).max()) if (upd > 0).any() else 0.0
   print(f"[adam{'_dev' if device_count else ''} n={n} step={step} b=({b1}, {b2}){' fresh' if fresh else ''}] worst err / bound: "
