@@ -195,6 +195,14 @@ SYMBOLS = {
                                       ctypes.POINTER(CnfFieldGrid), _P, _P, _P, _P, _I64, _P]),
   "cnf_point_stats": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CnfFieldGrid), _P, _P, _P,
                                      _I64, _P]),
+  # the finite-volume reference of the 2-D fp problems: coefficient block and rate, K steps per launch, stats [S, 7]
+  "cnf_fp_grid_coeffs_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_fp_grid_coeffs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_double,
+                                        ctypes.POINTER(CnfFieldGrid), _P, _I64, _P, _P]),
+  "cnf_fp_grid_steps_workspace": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_I64)]),
+  "cnf_fp_grid_steps": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _I64, ctypes.c_int32, _P, _P,
+                                       _I64, _P]),
+  "cnf_fp_grid_stats": (ctypes.c_int, [ctypes.POINTER(CnfFieldGrid), _P, ctypes.c_int32, _P, _P]),
   # importance-sampling diagnostics against a closed-form density: stats [n_slices, 5] doubles (m, s1, s2, c, n)
   "cnf_importance_workspace": (ctypes.c_int, [_I64, _I64, ctypes.c_int32, ctypes.POINTER(_I64)]),
   "cnf_importance_stats": (ctypes.c_int, [_P, ctypes.POINTER(CnfTargetSpec), _P, ctypes.c_int, _P, _I64, _I64, _P, _P, _I64,

@@ -981,6 +981,137 @@ def fp_reference_particles(dim, T, a, sigma, subtype, times, n_particles=1 << 20
   return out
 
 
+# ---- the grid reference of the 2-D fp problems ----------------------------------------------------------------------
+# The same PDE solved on density_on_grid's points by a Scharfetter-Gummel finite-volume scheme in float64: no noise
+# floor (cnf_fp_grid, include/cnf_ot_amd.h).
+FP_GRID_DRIFTS = ("ou", "gradient", "smile", "nongradient")
+FP_GRID_K = (1, 2, 4, 8)
+FP_GRID_STEPS_PER_LAUNCH = 8       # the fastest measured at 513 x 513
+
+
+def fp_grid_initial(g, var0) -> np.ndarray:
+  """Exact cell averages [ny, nx] of N(0, var0 I) on the cells of `g` (a CnfFieldGrid): a product of erf differences"""
+  s = math.sqrt(2.0 * var0)
+
+  def avg(lo, d, n):
+    c = lo + np.arange(n) * d
+    e = np.array([math.erf((v - 0.5 * d) / s) for v in c] + [math.erf((c[-1] + 0.5 * d) / s)])
+    return 0.5 * (e[1:] - e[:-1]) / d
+
+  return avg(g.lo_y, g.step_y, g.ny)[:, None] * avg(g.lo_x, g.step_x, g.nx)[None, :]
+
+
+def fp_grid_step_count(delta, rate, safety=0.9) -> int:
+  """Explicit steps between two output times `delta` apart: ceil(delta rate / safety), so that dt rate <= safety"""
+  return 0 if delta == 0.0 else max(1, int(math.ceil(delta * rate / safety)))
+
+
+def fp_reference_grid(T, a, sigma, subtype, times, grid, var0=None, rho0=None, safety=0.9, steps_per_launch=None):
+  """The 2-D fp problem's density at `times`, d rho / dt = -div(b rho) + sigma lap rho with the drift `subtype` (ou,
+  gradient = smile, nongradient; parameter a as float32), solved in float64 on `grid` -- a utils.field_grid or
+  (domain_range, n), as stats_grid takes it: cell (j, i) centred on grid point (x_i, y_j), density_on_grid's points --
+  by the Scharfetter-Gummel finite-volume scheme of cnf_fp_grid with no-flux box faces.  Start: exact cell averages of
+  N(0, var0 I) (var0 = None: fp_initial_variance(T)) or the given rho0 [ny, nx] >= 0.  Between consecutive times Delta
+  apart it takes ceil(Delta rate / safety) explicit steps, rate the largest outflow rate: each step is a convex
+  combination, so rho stays >= 0 and its sum is kept to rounding.  steps_per_launch in {1, 2, 4, 8} (None:
+  FP_GRID_STEPS_PER_LAUNCH) changes the launches, not one bit of the result.
+  Returns a dict of device tensors: times [S]; density [S, ny, nx] (float64); mass, min [S]; mean [S, 2]; cov [S, 2, 2];
+  n_steps [S] (int64); rate (0-dim); x [nx], y [ny].  The rate is read back once (8 bytes): not for graph capture.
+  ValueError before any device work for an unknown drift or one of another dimension, sigma <= 0, safety outside
+  (0, 1], times that are negative, do not ascend or are more than FP_MAX_SNAPSHOTS, a rho0 of the wrong shape or with a
+  negative entry, and steps_per_launch outside {1, 2, 4, 8}."""
+  if subtype not in _capi.DRIFTS:
+    raise ValueError(f"unknown drift {subtype!r}")
+  if subtype not in FP_GRID_DRIFTS:
+    raise ValueError(f"fp_reference_grid: drift {subtype!r} is not defined at dim 2")
+  sigma, safety = float(sigma), float(safety)
+  if not (sigma > 0.0 and math.isfinite(sigma)):
+    raise ValueError(f"fp_reference_grid: sigma must be positive, not {sigma}")
+  if not 0.0 < safety <= 1.0:
+    raise ValueError(f"fp_reference_grid: safety must lie in (0, 1], not {safety}")
+  K = FP_GRID_STEPS_PER_LAUNCH if steps_per_launch is None else steps_per_launch
+  if K not in FP_GRID_K:
+    raise ValueError(f"fp_reference_grid: steps_per_launch must be one of {FP_GRID_K}, not {steps_per_launch!r}")
+  ts = np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64).reshape(-1)
+  if ts.size < 1 or ts.size > FP_MAX_SNAPSHOTS or not np.isfinite(ts).all():
+    raise ValueError(f"fp_reference_grid: between 1 and {FP_MAX_SNAPSHOTS} finite times, not {ts.size}")
+  if ts[0] < 0.0 or (np.diff(ts) <= 0.0).any():
+    raise ValueError(f"fp_reference_grid: the times must be >= 0 and ascend: {ts.tolist()}")
+  if grid is None:
+    raise ValueError("fp_reference_grid: needs a grid")
+  g = stats_grid(grid, (0, 1), 2)
+  nx, ny, S = g.nx, g.ny, int(ts.size)
+  if rho0 is None:
+    var0 = fp_initial_variance(T) if var0 is None else float(var0)
+    if not (var0 > 0.0 and math.isfinite(var0)):
+      raise ValueError(f"fp_reference_grid: var0 must be positive, not {var0}")
+    start = fp_grid_initial(g, var0)
+  else:
+    start = np.asarray(rho0.detach().cpu() if torch.is_tensor(rho0) else rho0, dtype=np.float64)
+    if start.shape != (ny, nx):
+      raise ValueError(f"fp_reference_grid: rho0 must be [{ny}, {nx}], not {list(start.shape)}")
+    if not np.isfinite(start).all() or (start < 0.0).any():
+      raise ValueError("fp_reference_grid: rho0 must be finite and >= 0")
+  dev = torch.device("cuda", torch.cuda.current_device())
+  lib, C = _capi.lib(), _capi.ctypes
+  f64 = dict(dtype=torch.float64, device=dev)
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_fp_grid_coeffs_bytes(nx, ny, C.byref(nbytes)), "cnf_fp_grid_coeffs_bytes")
+  coef = torch.empty(nbytes.value // 8, **f64)
+  _capi.check(lib.cnf_fp_grid_steps_workspace(nx, ny, C.byref(nbytes)), "cnf_fp_grid_steps_workspace")
+  ws = torch.empty(nbytes.value // 8, **f64)
+  rate = torch.empty((), **f64)
+  density = torch.empty(S, ny, nx, **f64)
+  stats = torch.empty(S, 7, **f64)
+  cur = torch.as_tensor(np.ascontiguousarray(start)).to(dev)
+  n_steps = []
+  with _OnDevice(dev):
+    st = _stream_ptr(dev)
+    _capi.check(lib.cnf_fp_grid_coeffs(_capi.DRIFTS[subtype], 2, float(a), sigma, C.byref(g), coef.data_ptr(),
+                                       coef.numel() * 8, rate.data_ptr(), st), "cnf_fp_grid_coeffs")
+    R = float(rate)                                  # the one read-back
+    t_prev = 0.0
+    for s in range(S):
+      delta = float(ts[s]) - t_prev
+      n = fp_grid_step_count(delta, R, safety)
+      density[s].copy_(cur)
+      cur = density[s]
+      if n:
+        _capi.check(lib.cnf_fp_grid_steps(coef.data_ptr(), nx, ny, delta / n, n, K, cur.data_ptr(), ws.data_ptr(),
+                                          ws.numel() * 8, st), "cnf_fp_grid_steps")
+      n_steps.append(n)
+      t_prev = float(ts[s])
+    _capi.check(lib.cnf_fp_grid_stats(C.byref(g), density.data_ptr(), S, stats.data_ptr(), st), "cnf_fp_grid_stats")
+  mass = stats[:, 0]
+  mean = stats[:, 2:4] / mass[:, None]
+  second = torch.stack([stats[:, 4], stats[:, 5], stats[:, 5], stats[:, 6]], -1).reshape(S, 2, 2) / mass[:, None, None]
+  return {"times": torch.as_tensor(ts, device=dev), "density": density, "mass": mass, "min": stats[:, 1], "mean": mean,
+          "cov": second - mean[:, :, None] * mean[:, None, :], "stats": stats,
+          "n_steps": torch.as_tensor(n_steps, dtype=torch.int64, device=dev), "rate": rate,
+          "x": g.lo_x + g.step_x * torch.arange(nx, **f64), "y": g.lo_y + g.step_y * torch.arange(ny, **f64)}
+
+
+def fp_grid_coefficients(a, sigma, subtype, grid):
+  """The face coefficients of fp_reference_grid on `grid` as float64 device tensors (cxL, cxR [ny, nx + 1], cyL, cyR
+  [ny + 1, nx]) and the 0-dim rate: the probes' and the tests' view of cnf_fp_grid_coeffs."""
+  if subtype not in FP_GRID_DRIFTS:
+    raise ValueError(f"fp_grid_coefficients: drift {subtype!r} is not defined at dim 2")
+  g = stats_grid(grid, (0, 1), 2)
+  nx, ny = g.nx, g.ny
+  dev = torch.device("cuda", torch.cuda.current_device())
+  lib, C = _capi.lib(), _capi.ctypes
+  nbytes = C.c_int64(0)
+  _capi.check(lib.cnf_fp_grid_coeffs_bytes(nx, ny, C.byref(nbytes)), "cnf_fp_grid_coeffs_bytes")
+  coef = torch.empty(nbytes.value // 8, dtype=torch.float64, device=dev)
+  rate = torch.empty((), dtype=torch.float64, device=dev)
+  with _OnDevice(dev):
+    _capi.check(lib.cnf_fp_grid_coeffs(_capi.DRIFTS[subtype], 2, float(a), float(sigma), C.byref(g), coef.data_ptr(),
+                                       coef.numel() * 8, rate.data_ptr(), _stream_ptr(dev)), "cnf_fp_grid_coeffs")
+  nxf, nyf = ny * (nx + 1), (ny + 1) * nx
+  return (coef[:nxf].view(ny, nx + 1), coef[nxf:2 * nxf].view(ny, nx + 1), coef[2 * nxf:2 * nxf + nyf].view(ny + 1, nx),
+          coef[2 * nxf + nyf:].view(ny + 1, nx), rate)
+
+
 # ---- the particle reference of the rwpo problems --------------------------------------------------------------------
 # The Hopf-Cole formula read as an expectation (the reference's cost_rwpo, solvers.py:190-220, is its nested Monte-Carlo
 # at dim 2): with eps = 1 / beta the optimal path measure is Brownian motion of variance 2 eps t from rho0, reweighted by

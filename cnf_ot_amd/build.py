@@ -16,7 +16,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcnf_ot_amd.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")                     # one object per source; FLAGS: what they were compiled with
 # (the longest compile first: it bounds the build)
-SOURCES = ["cnf_flow.hip", "cnf_grad.hip", "cnf_grad_pwl.hip", "cnf_importance.hip", "cnf_mmd.hip", "cnf_mmd_perm.hip", "cnf_knn.hip", "cnf_interaction.hip", "cnf_interaction_vjp.hip", "cnf_stein.hip", "cnf_stein_boot.hip", "cnf_kde.hip", "cnf_hopf_cole.hip", "cnf_fp_particles.hip",
+SOURCES = ["cnf_flow.hip", "cnf_grad.hip", "cnf_grad_pwl.hip", "cnf_importance.hip", "cnf_mmd.hip", "cnf_mmd_perm.hip", "cnf_knn.hip", "cnf_interaction.hip", "cnf_interaction_vjp.hip", "cnf_stein.hip", "cnf_stein_boot.hip", "cnf_kde.hip", "cnf_hopf_cole.hip", "cnf_fp_particles.hip", "cnf_fp_grid.hip",
            "cnf_mv_particles.hip", "cnf_rwpo_particles.hip", "cnf_sinkhorn.hip", "cnf_sliced.hip", "cnf_step.hip", "cnf_model.hip", "cnf_rng.hip"]
 HEADERS = ["cnf_device.h", "cnf_terms.h", "cnf_common.h", "cnf_host.h", "cnf_flow_tile.h", "cnf_backward.h", "cnf_pwl.h",
            "cnf_pwl_build.h", "cnf_first_table.h", "cnf_fp_stats.h", "cnf_pairs.h", "cnf_interaction_pairs.h", os.path.join("..", "..", "include", "cnf_ot_amd.h")]

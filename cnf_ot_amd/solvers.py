@@ -880,6 +880,88 @@ def print_fp_knn(res: Dict[str, Any]) -> None:
     print("  {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f} | {:.4f}".format(*row))
 
 
+# ---- the flow against the Fokker-Planck equation itself, solved on a grid (fp at dim 2) ------------------------------
+
+# The box the PDE is solved in (no-flux faces), per drift: wide enough that N(0, (T + 1) / 2 I) and the solution leave
+# no mass at the faces; the smile's cubic drift makes a wider box only stiffer (the step count grows with |b| dx / sigma)
+FP_GRID_DOMAIN = {"ou": [-6.0, 6.0, -6.0, 6.0], "nongradient": [-6.0, 6.0, -6.0, 6.0], "gradient": [-4.0, 4.0, -4.0, 4.0],
+                  "smile": [-4.0, 4.0, -4.0, 4.0]}
+FP_GRID_KEYS = ("times", "l1", "rel_l2", "max_log_err", "mean_grid", "mean_flow", "trace_cov_grid", "trace_cov_flow",
+                "trace_cov_closed_form", "mass", "n_steps", "n", "domain")
+FP_GRID_MASS = 0.999     # max_log_err looks at the densest cells that hold this share of the grid solution's mass
+
+
+def evaluate_fp_grid(config, model: FlowModel, params: Params, times=None, n=257, domain=None, n_samples=1 << 18,
+                     seed=0) -> Dict[str, Any]:
+  """The flow of an fp configuration at dim 2 against the Fokker-Planck equation itself, solved in float64 on a grid
+  (applications.fp_reference_grid: no Monte-Carlo floor): per time of `times` (default: the figure's) the flow's density
+  on the grid's points (utils.density_on_grid) beside the grid solution on n (an int or (nx, ny)) points per axis of
+  `domain` (default: FP_GRID_DOMAIN of the drift).  Lists, one entry per time:
+    times
+    l1               sum |rho_flow - rho_grid| dx dy
+    rel_l2           |rho_flow - rho_grid|_2 / |rho_grid|_2
+    max_log_err      max |log rho_flow - log rho_grid| over the densest cells that hold FP_GRID_MASS of the grid's mass:
+                     the tails, where a histogram has nothing to say
+    mean_grid, mean_flow            [2] each; the flow's from n_samples samples of `seed` (utils.point_stats)
+    trace_cov_grid, trace_cov_flow  tr cov of the same
+    trace_cov_closed_form           ou: 2 ou_variance(t); None for the other drifts
+    mass, n_steps                   the grid solution's mass and its explicit steps up to that time from the one before
+  and n, domain.  ValueError before any device work for another problem type, another dimension, a drift the grid does
+  not cover (lorenz), and an interaction in the drift."""
+  g = config["general"]
+  if g["type"] != "fp":
+    raise ValueError(f"evaluate_fp_grid: defined for fp only, not {g['type']}")
+  f = config["fp"]
+  sub = f["velocity_field_type"]
+  if g["dim"] != 2 or sub not in applications.FP_GRID_DRIFTS:
+    raise ValueError(f"evaluate_fp_grid: the grid reference is defined at dim 2 for {applications.FP_GRID_DRIFTS}, "
+                     f"not for {sub} at dim {g['dim']}")
+  if _interaction_kind(config) != "none" and _interaction_role(config) == "drift":
+    raise ValueError("evaluate_fp_grid: the grid reference has no interaction term in its drift")
+  T, a, sigma = float(f["T"]), f["a"], f["sigma"]
+  ts = figure_settings(config)["t_array"] if times is None else utils._times_of(times)
+  dom = [float(v) for v in (FP_GRID_DOMAIN[sub] if domain is None else domain)]
+  grid = utils.field_grid(dom, n)
+  ref = applications.fp_reference_grid(T, a, sigma, sub, ts, grid)
+  S = len(ts)
+  want = ref["density"]
+  rho = utils.density_on_grid(model, params, ts, dom, n).double()
+  area = float((ref["x"][1] - ref["x"][0]) * (ref["y"][1] - ref["y"][0]))
+  diff = rho - want
+  # the densest cells that hold FP_GRID_MASS of the mass: sort descending, keep while the running sum stays below it
+  flat = want.reshape(S, -1)
+  order = flat.argsort(dim=1, descending=True)
+  before = flat.gather(1, order).cumsum(1) - flat.gather(1, order)
+  keep = torch.zeros_like(flat, dtype=torch.bool).scatter(1, order, before < FP_GRID_MASS * flat.sum(1, keepdim=True))
+  log_err = (rho.reshape(S, -1).clamp_min(1e-300).log() - flat.clamp_min(1e-300).log()).abs()
+  samples = torch.stack([model.apply.sample(params, cond=float(t), seed=seed, sample_shape=(int(n_samples),)) for t in ts])
+  flow = utils.point_stats(samples)
+  return {"times": [float(t) for t in ts],
+          "l1": (diff.abs().sum((1, 2)) * area).tolist(),
+          "rel_l2": (torch.linalg.norm(diff.reshape(S, -1), dim=1) / torch.linalg.norm(flat, dim=1)).tolist(),
+          "max_log_err": torch.where(keep, log_err, torch.zeros_like(log_err)).amax(1).tolist(),
+          "mean_grid": ref["mean"].tolist(), "mean_flow": flow["mean"].tolist(),
+          "trace_cov_grid": ref["cov"].diagonal(dim1=1, dim2=2).sum(1).tolist(),
+          "trace_cov_flow": flow["cov"].diagonal(dim1=1, dim2=2).sum(1).tolist(),
+          "trace_cov_closed_form": [2.0 * applications.ou_variance(float(t), a, applications.fp_initial_variance(T), sigma)
+                                    for t in ts] if sub == "ou" else None,
+          "mass": ref["mass"].tolist(), "n_steps": ref["n_steps"].tolist(),
+          "n": [int(v) for v in grid["n"]], "domain": dom}
+
+
+def print_fp_grid(res: Dict[str, Any]) -> None:
+  """evaluate_fp_grid's table, one line per time"""
+  print("errors against the grid solution of the Fokker-Planck equation ({} x {} points over {}):  t | L1 | rel L2 | "
+        "max |log rho err| ({:.1%} of the mass) | mean grid | mean flow | tr cov grid | tr cov flow | tr cov closed form | "
+        "steps".format(res["n"][0], res["n"][1], res["domain"], FP_GRID_MASS))
+  closed = res["trace_cov_closed_form"] or [float("nan")] * len(res["times"])
+  for row in zip(res["times"], res["l1"], res["rel_l2"], res["max_log_err"], res["mean_grid"], res["mean_flow"],
+                 res["trace_cov_grid"], res["trace_cov_flow"], closed, res["n_steps"]):
+    t, l1, l2, le, mg, mf, cg, cf, cc, k = row
+    print("  {:.4f} | {:.3e} | {:.3e} | {:.3e} | ({:+.4f}, {:+.4f}) | ({:+.4f}, {:+.4f}) | {:.5f} | {:.5f} | {:.5f} | {:d}".format(
+      t, l1, l2, le, mg[0], mg[1], mf[0], mf[1], cg, cf, cc, int(k)))
+
+
 # ---- the nonlocal running cost of a trained flow: its interaction energy along the path ------------------------------
 
 INTERACTION_KEYS = ("times", "energy", "floor", "running_cost", "trace_cov", "kind", "strength", "n")
@@ -1434,7 +1516,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
          fields: Optional[str] = None, path_errors: bool = False, fit: bool = False,
          two_sample: bool = False, ot_reference: bool = False, sliced: bool = False, knn: bool = False,
          interaction: bool = False, mv_path: bool = False, ksd: bool = False, field_errors: bool = False,
-         permutation_test: bool = False, ksd_test: bool = False, rwpo_particles: bool = False) -> Dict[str, Any]:
+         permutation_test: bool = False, ksd_test: bool = False, rwpo_particles: bool = False,
+         grid_reference: bool = False) -> Dict[str, Any]:
   """solvers.py:26-308 without plots: train, then print the reference's lines in its wording and return
   `evaluate`'s dict.  For ot, the density-fit KL is printed every eval_frequency steps (:108-116).  path_errors: print
   evaluate_path's table after them (rwpo at dim 2), or evaluate_fp_path's (fp).  fit: print evaluate_fit's table (the
@@ -1443,7 +1526,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
   table.  interaction (an `interaction` section with a kind): print evaluate_interaction's table.  mv_path (fp with an
   `interaction` section whose role is drift): print evaluate_mv_path's table.  ksd: print evaluate_ksd's tables.
   field_errors (fp): print evaluate_fp_fields' table.  permutation_test (fp): print evaluate_fp_permutation's table.
-  ksd_test: print evaluate_ksd_test's table.  rwpo_particles (rwpo, any dim): print evaluate_rwpo_particles' lines."""
+  ksd_test: print evaluate_ksd_test's table.  rwpo_particles (rwpo, any dim): print evaluate_rwpo_particles' lines.
+  grid_reference (fp at dim 2): print evaluate_fp_grid's table."""
   g, tr = config["general"], config["train"]
   _type, dim, seed = g["type"], g["dim"], g["seed"]
   if _type not in _SOLVING:
@@ -1465,6 +1549,9 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
                      "interacting particle reference")
   if rwpo_particles and _type != "rwpo":
     raise ValueError(f"--rwpo-particles compares an rwpo flow with the particle reference of its optimal path: not defined for {_type}")
+  if grid_reference and (_type != "fp" or dim != 2):
+    raise ValueError(f"--grid-reference compares an fp flow at dim 2 with the grid solution of its Fokker-Planck equation: "
+                     f"not defined for {_type} at dim {dim}")
   if ot_reference and _type != "ot":
     raise ValueError(f"--ot-reference compares an ot flow with Sinkhorn divergences of its samples: not defined for {_type}")
   print(_SOLVING[_type].format(dim=dim, lam=tr["_lambda"]), flush=True)
@@ -1538,6 +1625,8 @@ def main(config, epochs: Optional[int] = None, capture: bool = False, save: Opti
     print_fp_permutation(evaluate_fp_permutation(config, model, params))
   if rwpo_particles:
     print_rwpo_particles(evaluate_rwpo_particles(config, model, params))
+  if grid_reference:
+    print_fp_grid(evaluate_fp_grid(config, model, params))
   return res
 
 
@@ -1591,6 +1680,9 @@ def _parse(argv):
                  help="print the optimal energy from the particle reference of the rwpo problem, its standard error, bias "
                       "and effective sample size, and the flow's mean, covariance and histogram errors against the "
                       "reference's Brownian bridges along the path, beside their floor (rwpo, any dimension)")
+  p.add_argument("--grid-reference", action="store_true",
+                 help="print the L1, relative L2 and tail log-density errors of the flow's density against the float64 "
+                      "finite-volume solution of the Fokker-Planck equation on a grid, and both sets of moments (fp, dim 2)")
   return p.parse_args(argv)
 
 
@@ -1600,4 +1692,4 @@ if __name__ == "__main__":
        path_errors=args.path_errors, fit=args.fit, two_sample=args.two_sample, ot_reference=args.ot_reference,
        sliced=args.sliced, knn=args.knn, interaction=args.interaction, mv_path=args.mv_path, ksd=args.ksd,
        field_errors=args.field_errors, permutation_test=args.permutation_test, ksd_test=args.ksd_test,
-       rwpo_particles=args.rwpo_particles)
+       rwpo_particles=args.rwpo_particles, grid_reference=args.grid_reference)

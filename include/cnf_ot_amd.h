@@ -715,6 +715,38 @@ int cnf_point_stats(const float *pts, int64_t N, int32_t D, int32_t S,
                     const CnfFieldGrid *grid, double *sums, uint32_t *hist,
                     void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- a finite-volume reference for the 2-D Fokker-Planck problems (applications.py:279-374, drifts :310, :353-363) ----
+ * The same PDE, d rho / dt = -div(rho drift) + sigma lap rho, solved on the grid of cnf_fp_particles' histogram: points
+ * lo + i step, cell (j, i) centred on its point, arrays [ny, nx] row-major, float64.  No noise floor.
+ * Flux (Scharfetter-Gummel / Chang-Cooper): B(z) = z / expm1(z) (1 - z / 2 for |z| < 1e-8), Pe = b step / sigma with b
+ * the normal drift (CnfDrift, parameter `a`, evaluated in float64) at the face's midpoint; the face between cells i - 1
+ * and i carries F = cL rho_{i-1} - cR rho_i, cL = sigma / step^2 B(-Pe), cR = sigma / step^2 B(Pe).  The faces of the
+ * box carry no flux.  Step: rho' = rho + dt ((F_w - F_e) + (G_s - G_n)), that order, no contraction.
+ *
+ * cnf_fp_grid_coeffs writes the coefficient block `coef` (cnf_fp_grid_coeffs_bytes(nx, ny) bytes; `grid`: lo, step, nx,
+ * ny; its other members are ignored): cxL, cxR [ny, nx + 1] (face f of a row lies between cells f - 1 and f), then cyL,
+ * cyR [ny + 1, nx]; the box's faces hold zeros.  rate (one device double): the largest outflow rate, the sum of the
+ * four coefficients that multiply a cell's own rho.  A step with dt rate <= 1 is a convex combination: rho stays >= 0.
+ * cnf_fp_grid_steps advances rho [ny, nx] in place by n_steps steps of dt, steps_per_launch = K in {1, 2, 4, 8} steps
+ * per launch (a workgroup takes K steps on its tile with a halo of K cells; n_steps mod K steps run with smaller K);
+ * every K gives the same bits.  workspace: cnf_fp_grid_steps_workspace(nx, ny) bytes, the second buffer of the launches.
+ * cnf_fp_grid_stats: per snapshot of rho [S, ny, nx], stats [S, 7] = mass, min, sum rho x, y, xx, xy, yy -- the sums
+ * times step_x step_y, min the smallest cell value -- in a fixed order: two calls are bit-identical.
+ * No allocation, no synchronisation, no atomics.
+ * CNF_ERR_INVALID (nothing enqueued): D != 2; a drift other than OU, SMILE, NONGRADIENT; sigma <= 0; sigma or a not
+ * finite; nx or ny outside 1..2^14; a step <= 0; a NULL array; a block or workspace too small; dt <= 0; n_steps < 0; K
+ * outside {1, 2, 4, 8}; S outside 1..64. */
+int cnf_fp_grid_coeffs_bytes(int32_t nx, int32_t ny, int64_t *bytes);
+int cnf_fp_grid_coeffs(int32_t drift, int32_t D, float a, double sigma,
+                       const CnfFieldGrid *grid, double *coef, int64_t coef_bytes,
+                       double *rate, void *stream);
+int cnf_fp_grid_steps_workspace(int32_t nx, int32_t ny, int64_t *bytes);
+int cnf_fp_grid_steps(const double *coef, int32_t nx, int32_t ny, double dt,
+                      int64_t n_steps, int32_t steps_per_launch, double *rho,
+                      void *workspace, int64_t workspace_bytes, void *stream);
+int cnf_fp_grid_stats(const CnfFieldGrid *grid, const double *rho, int32_t S,
+                      double *stats, void *stream);
+
 /* ---- importance-sampling diagnostics against a density known in closed form ----------------------------------------
  * The reference's kl_ess (tests/test_fit_prob.py:50-56, "metrics used in the tori paper"): draw y_i from the flow,
  * weight w_i = p_target(y_i) / q_flow(y_i), and report Z = mean w, KL = mean(log q - log p) + log Z and the effective
